@@ -12,6 +12,12 @@ env-step are written to an HBM trajectory slab.  The env-steps of the timed regi
 executed by the fused step kernel in launches of --chunk env-steps; the variant launched is
 reported in config.kernel.  value = env-steps per second (BASELINE.json's metric).
 
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps, writes the
+last step's outputs when --dump-outputs is given, and prints the result line.  Every other leg
+(the 200-step-launch comparison, one launch per step, the host-driven and reference-API legs,
+16x the envs, the A2C training loop, the CPU baseline) runs only with --full; the --no-* options
+drop single legs of a --full run.
+
 Multi-GPU (torchrun): one process per GPU, envs sharded by global id (rank * envs + e) with
 no data-path collective ("scaling": "weak"); the only collectives are the barrier and the
 max-over-ranks of the elapsed time.
@@ -45,6 +51,12 @@ def parse():
                          "without it, N > 1 starts N rank processes itself (launch_ranks)")
     ap.add_argument("--steps", type=int, default=None, help="bench steps: default 20 rollout batches (step) / 4 A2C batches (a2c)")
     ap.add_argument("--warmup", type=int, default=None, help="default 5 rollout batches (step) / 3 A2C batches (a2c)")
+    ap.add_argument("--full", action="store_true",
+                    help="step workload: also run the legs beside the headline figure (200-step launches, one "
+                         "launch per step, host-driven and reference-API legs, 16x envs, A2C loop, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32 / float64; a fixed seeded sample of steps and envs, under 64 MB in all)")
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--batch-steps", type=int, default=256,
                     help="env-steps of every env per bench step (one rollout batch, train.py:59)")
@@ -290,11 +302,69 @@ def load_pmc(workload):
         return None
 
 
+DUMP_BUDGET_BYTES = 40 << 20   # of the 64 MB a dump may take
+DUMP_MAX_ENVS = 4096
+# name -> dtype on disk (int32 and f64 values exactly in float64, the 8-bit and f32 ones in float32)
+STEP_DUMP = {"obs_i32": np.float64, "obs_i8": np.float32, "obs_f32": np.float32, "masks": np.float32,
+             "rewards": np.float64, "term": np.float32, "trunc": np.float32}
+
+
+def dump_name(dirname, name, rank, world):
+    os.makedirs(dirname, exist_ok=True)
+    return os.path.join(dirname, name + ("" if world == 1 else f"_rank{rank}") + ".npy")
+
+
+def dump_sample(n_rows, n_envs, bytes_per_env_step):
+    """The fixed sample of a dump: every env up to DUMP_MAX_ENVS (else a seeded choice of them) and
+    as many of the n_rows steps as the byte budget holds, the last step always among them."""
+    rng = np.random.default_rng(0)
+    envs = np.arange(n_envs) if n_envs <= DUMP_MAX_ENVS else np.sort(rng.choice(n_envs, DUMP_MAX_ENVS, replace=False))
+    keep = max(1, min(n_rows, DUMP_BUDGET_BYTES // (bytes_per_env_step * len(envs))))
+    rows = np.arange(n_rows) if keep >= n_rows else np.sort(
+        np.concatenate([rng.choice(n_rows - 1, keep - 1, replace=False), [n_rows - 1]]))
+    return rows.astype(np.int64), envs.astype(np.int64)
+
+
+def dump_step_outputs(dirname, buf, last_k, B, rank, world):
+    """The trajectory slab rows of the last bench step (the last B env-steps, as far as the last
+    launch holds them: rows [last_k - B, last_k) of `buf`), sampled by dump_sample."""
+    lo = max(0, last_k - B)
+    N = buf.term.shape[-1]
+    per = sum(np.dtype(dt).itemsize * (getattr(buf, k).shape[1] if getattr(buf, k).dim() == 3 else 1)
+              for k, dt in STEP_DUMP.items())
+    rows, envs = dump_sample(last_k - lo, N, per)
+    dev = buf.term.device
+    r = torch.from_numpy(rows + lo).to(dev)
+    e = torch.from_numpy(envs).to(dev)
+    total = 0
+    for k, dt in STEP_DUMP.items():
+        a = getattr(buf, k).index_select(0, r).index_select(-1, e).cpu().numpy().astype(dt)
+        np.save(dump_name(dirname, k, rank, world), a)
+        total += a.nbytes
+    return {"dir": dirname, "arrays": list(STEP_DUMP), "layout": "[step, field, env] (term, trunc: [step, env])",
+            "rows_of_last_launch": (rows + lo).tolist(), "envs": len(envs), "bytes": total}
+
+
+def dump_a2c_outputs(dirname, learner, rank, world):
+    """What the last timed A2C batch left: the networks' parameters after its update, the loss
+    histories, and a sample of its reward slab."""
+    flat = lambda ps: torch.cat([p.detach().reshape(-1) for p in ps]).float().cpu().numpy()  # noqa: E731
+    out = {"actor_params": flat(learner.actors.parameters()), "critic_params": flat(learner.critic.parameters()),
+           "critic_loss_history": np.asarray(learner.critic_loss_history, np.float64)}
+    rw = learner._bufs["rewards"]                      # f64 [T, 8, N]
+    rows, envs = dump_sample(rw.shape[0], rw.shape[-1], 8 * rw.shape[1])
+    out["rewards"] = rw.index_select(0, torch.from_numpy(rows).to(rw.device)).index_select(
+        -1, torch.from_numpy(envs).to(rw.device)).cpu().numpy().astype(np.float64)
+    for k, a in out.items():
+        np.save(dump_name(dirname, k, rank, world), a)
+    return {"dir": dirname, "arrays": list(out), "bytes": int(sum(a.nbytes for a in out.values()))}
+
+
 TRAINED_NPZ = os.path.join(REPO, "tests", "golden", "trained_policy.npz")
 
 
 def a2c_throughput(env, N, world, batches, warmup, batch_size, num_orders, dist=None, group=None, dedup=True,
-                   exchange="allreduce", init="random", stats=True):
+                   exchange="allreduce", init="random", stats=True, dump=None):
     """Batched A2C training loop (a2c_vec.VecMultiAgentA2C): env-steps/s over whole batches
     (collect batch_size vector steps with the policy + GAE + one update).  dedup: the update
     runs each network once per distinct input (A2CLosses; the same gradient).  exchange: the
@@ -347,6 +417,8 @@ def a2c_throughput(env, N, world, batches, warmup, batch_size, num_orders, dist=
                    "the env step of each 64-env tile, features and masks written in HBM; two env-group streams) -> "
                    "fp64 GAE kernel -> grouped full-batch update (8 actors + critic, Adam); reference a2c.py "
                    "loop: ~130 env-steps/s on one CPU core (SURVEY.md)"}
+    if dump:
+        out["dump_outputs"] = dump_a2c_outputs(dump, learner, dist.get_rank() if dist else 0, world)
     if world > 1:
         grad_bytes = 4 * sum(p.numel() for p in list(learner.actors.parameters()) + list(learner.critic.parameters()))
         if exchange == "gather":
@@ -462,7 +534,7 @@ def main():
     if args.workload == "a2c":
         res = a2c_throughput(env, N, world, args.steps, args.warmup, args.batch_size, 25, dist,
                              dist.group.WORLD if dist else None, dedup=not args.no_dedup, exchange=args.exchange,
-                             init=args.init)
+                             init=args.init, dump=args.dump_outputs)
         if rank == 0:
             out = {"metric": "env-steps/sec of the A2C training loop (BASELINE configs 4/5)",
                    "value": res["value"], "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
@@ -496,10 +568,12 @@ def main():
     buf = vec_env.Buffers(chunk, N, dev, infos=False)
     stream = torch.cuda.current_stream(dev)
 
+    last = {"k": 0}                           # env-steps of the last launch of run()
+
     def run(nsteps, step0, timing=None, chunk=chunk, buf=buf):
         done = 0
         while done < nsteps:
-            k = min(chunk, nsteps - done)
+            k = last["k"] = min(chunk, nsteps - done)
             if timing is not None:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(stream)
@@ -537,9 +611,10 @@ def main():
     total_env_steps = args.steps * B * N * world
     value = total_env_steps / elapsed
     achieved = ALGO_BYTES_FUSED * N * steps_per_launch / (avg_launch_ms * 1e-3) / 1e9
+    dumped = dump_step_outputs(args.dump_outputs, buf, last["k"], B, rank, world) if args.dump_outputs else None
     # the same workload in 200-step launches (r01's first headline configuration), rank-local
     chunk_200 = None
-    if chunk != 200 and args.steps * B >= 200 and not args.no_chunk_compare:
+    if args.full and chunk != 200 and args.steps * B >= 200 and not args.no_chunk_compare:
         buf200 = vec_env.Buffers(200, N, dev, infos=False)
         s1 = run(200, s0 + args.steps * B, chunk=200, buf=buf200)
         torch.cuda.synchronize()
@@ -556,7 +631,7 @@ def main():
 
     # one-launch-per-step mode (actions resident in HBM, k_step): the RL-loop path
     per_step = None
-    if not args.no_step_mode:
+    if args.full and not args.no_step_mode:
         K = 200
         acts = torch.randint(0, 256, (K, 8, N), dtype=torch.int32, device=dev)
         nact = torch.tensor([3, 8, 3, 3, 3, 3, 3, 3], dtype=torch.int32, device=dev).view(1, 8, 1)
@@ -592,7 +667,7 @@ def main():
 
     # the reference-API path itself (FJSPParallelEnv.step with dict actions, one env)
     dropin = None
-    if rank == 0 and world == 1 and not args.no_dropin:
+    if args.full and rank == 0 and world == 1 and not args.no_dropin:
         try:
             dropin = dropin_latency(dev)
         except Exception as e:   # the headline metric does not depend on this leg
@@ -601,7 +676,7 @@ def main():
     # the same kernel at 16x the envs (65 536 on this GPU): how far the env-step approaches the
     # HBM roofline once occupancy allows (the headline stays the 4 096-env workload)
     scale = None
-    if world == 1 and not args.no_scale:
+    if args.full and world == 1 and not args.no_scale:
         try:
             NS = 16 * N
             sch = min(chunk, 256)   # 32-bit output offsets: K x envs x 64 B < 4 GiB per launch
@@ -629,7 +704,7 @@ def main():
             scale = {"error": f"{type(e).__name__}: {e}"}
 
     a2c = None
-    if world == 1 and not args.no_a2c:
+    if args.full and world == 1 and not args.no_a2c:
         try:
             aenv = vec_env.FJSPVecEnv(N, device=dev)
             # four warm-up batches: the first collect / update carry one-time costs (graph
@@ -651,7 +726,7 @@ def main():
             a2c = {"error": f"{type(e).__name__}: {e}"}
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline(args)
 
     workload = f"fjsp_step_{N}envs"
@@ -708,6 +783,8 @@ def main():
             "a2c_training": a2c,
             "scale_16x_envs": scale,
             "state_bytes_per_env": env.state_bytes_per_env(),
+            "full": bool(args.full),
+            "dump_outputs": dumped,
         }
         print(json.dumps(out), flush=True)
     if dist:

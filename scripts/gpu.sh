@@ -4,7 +4,8 @@
 # stages:
 #   suite             the whole -m gpu suite (one process), then smoke()
 #   tests:<expr>      pytest -m gpu -k <expr> (',' for ' ')
-#   bench             the driver-form bench line (N=1)
+#   bench             the driver-form bench line (N=1): the headline figure alone
+#   bench_full        the same with --full: every other leg of the benchmark beside it
 #   bench_a2c[:args]  bench.py --workload a2c (extra args after ':' with ',' for ' ')
 #   py:<script,args>  python3 <script> <args> (',' for ' '), stdout to <stage-index>.json
 #   pyenv:<VAR=VAL+..>:<script,args>  the same with environment variables
@@ -38,6 +39,9 @@ for stage in "$@"; do
     bench)
       timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_$i.json" 2> "$OUT/bench_$i.err"
       rc=$?; tail -c 800 "$OUT/bench_$i.json" ;;
+    bench_full)
+      timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_full_$i.json" 2> "$OUT/bench_full_$i.err"
+      rc=$?; tail -c 800 "$OUT/bench_full_$i.json" ;;
     bench_a2c)
       timeout -k 10 600 python3 bench.py --workload a2c $args > "$OUT/bench_a2c_$i.json" 2> "$OUT/bench_a2c_$i.err"
       rc=$?; tail -c 1200 "$OUT/bench_a2c_$i.json" ;;

@@ -173,27 +173,60 @@ def _bare_learner(seed=0):
     return learner
 
 
-def test_reference_checkpoint_loads_if_present():
-    """The reference's own checkpoints/model.pt through load_model (torch.load(weights_only=
-    True) with the numpy scalar / int64 dtype allowlist; a2c.py:733-775): the reference tree is
-    absent on the GPU box, where the weights travel as tests/golden/trained_policy.npz."""
-    import os
-    path = "/root/reference/checkpoints/model.pt"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present (GPU box): covered by the trained_policy.npz tests")
-    learner = _bare_learner()
-    learner.load_model(path)
-    ck = A.load_checkpoint(path)
-    assert ck["act_dims"] == dict(zip(spec.AGENTS, A.N_ACTIONS)) and ck["global_obs_dim"] == 38
-    assert all(type(v) is int for v in ck["act_dims"].values())
+def _reference_layout_checkpoint(path):
+    """A checkpoint in the layout the reference's save_model writes (a2c.py:733-775) with the
+    trained weights of tests/golden/trained_policy.npz: per-agent OrderedDicts of tensors, the
+    critic's state dict, obs_dims as Python ints and act_dims as numpy int64 scalars (what the
+    reference pickles from `action_space.n`, and what the loader's allowlist is for)."""
+    from collections import OrderedDict
     z = np.load(f"{P.GOLDEN}/trained_policy.npz")
-    for i, a in enumerate(spec.AGENTS):
-        for k, v in ck["actor_nets"][a].items():
-            assert torch.equal(learner.actors.actor_state_dict(i)[k], v), (a, k)
-            assert np.array_equal(z[f"w_actor.{a}.{k}"], v.numpy()), (a, k)
-    for k, v in ck["critic_net"].items():
-        assert torch.equal(learner.critic.state_dict()[k], v), k
-        assert np.array_equal(z[f"w_critic.{k}"], v.numpy()), k
+    w = lambda prefix: OrderedDict((k[len(prefix):], torch.from_numpy(z[k].copy()))  # noqa: E731
+                                   for k in z.files if k.startswith(prefix))
+    torch.save({"actor_nets": {a: w(f"w_actor.{a}.") for a in spec.AGENTS},
+                "critic_net": w("w_critic."),
+                "obs_dims": dict(zip(spec.AGENTS, (int(d) for d in A.OBS_DIMS))),
+                "act_dims": dict(zip(spec.AGENTS, (np.int64(n) for n in A.N_ACTIONS))),
+                "global_obs_dim": 38, "possible_agents": list(spec.AGENTS)}, str(path) + ".np")
+    # the reference's file was pickled under numpy 1.x, where the scalar's constructor is named
+    # numpy.core.multiarray.scalar; numpy 2 writes numpy._core: spell it as the reference's file
+    import zipfile
+    with zipfile.ZipFile(str(path) + ".np") as zin, zipfile.ZipFile(str(path), "w", zipfile.ZIP_STORED) as zout:
+        for n in zin.namelist():
+            b = zin.read(n)
+            if n.endswith("data.pkl"):
+                b = b.replace(b"cnumpy._core.multiarray\nscalar\n", b"cnumpy.core.multiarray\nscalar\n")
+                assert b.count(b"cnumpy.core.multiarray\nscalar\n") == 1      # memoised after its first use
+            zout.writestr(n, b)
+
+
+def test_reference_checkpoint_loads_if_present(tmp_path):
+    """A checkpoint as the reference writes it through load_model (torch.load(weights_only=
+    True) with the numpy scalar / int64 dtype allowlist; a2c.py:733-775): one in the reference's
+    layout built from tests/golden/trained_policy.npz, and the reference's own
+    checkpoints/model.pt where FJSP_REFERENCE_DIR names a checkout of the reference."""
+    import os
+    built = tmp_path / "model.pt"
+    _reference_layout_checkpoint(built)
+    paths = [str(built)]
+    own = os.path.join(os.environ.get("FJSP_REFERENCE_DIR", ""), "checkpoints", "model.pt")
+    if os.environ.get("FJSP_REFERENCE_DIR") and os.access(own, os.R_OK):
+        paths.append(own)
+    z = np.load(f"{P.GOLDEN}/trained_policy.npz")
+    for path in paths:
+        learner = _bare_learner()
+        learner.load_model(path)
+        ck = A.load_checkpoint(path)
+        assert ck["act_dims"] == dict(zip(spec.AGENTS, A.N_ACTIONS)) and ck["global_obs_dim"] == 38
+        assert all(type(v) is int for v in ck["act_dims"].values())
+        for i, a in enumerate(spec.AGENTS):
+            assert len(ck["actor_nets"][a]) == 6, a
+            for k, v in ck["actor_nets"][a].items():
+                assert torch.equal(learner.actors.actor_state_dict(i)[k], v), (a, k)
+                assert np.array_equal(z[f"w_actor.{a}.{k}"], v.numpy()), (a, k)
+        assert len(ck["critic_net"]) == 8
+        for k, v in ck["critic_net"].items():
+            assert torch.equal(learner.critic.state_dict()[k], v), k
+            assert np.array_equal(z[f"w_critic.{k}"], v.numpy()), k
 
 
 def test_checkpoint_loader_refuses_other_globals(tmp_path):
