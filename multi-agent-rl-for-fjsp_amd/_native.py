@@ -15,7 +15,8 @@ REPO = os.path.dirname(HERE)
 # FJSP_LIB selects a diagnostic build (e.g. libfjsp_stamps.so); default: the product library
 LIB_PATH = os.environ.get("FJSP_LIB") or os.path.join(HERE, "libfjsp.so")
 SRC = os.path.join(HERE, "csrc", "fjsp_hip.hip")
-SRCS = [SRC, os.path.join(HERE, "csrc", "fjsp_policy.hip"), os.path.join(HERE, "csrc", "fjsp_group.hip")]
+SRCS = [SRC, os.path.join(HERE, "csrc", "fjsp_policy.hip"), os.path.join(HERE, "csrc", "fjsp_group.hip"),
+        os.path.join(HERE, "csrc", "fjsp_episode.hip")]
 HEADERS = [os.path.join(HERE, "csrc", h) for h in ("fjsp_env.h", "fjsp_stepdev.h", "fjsp_stamps.h")] + [
     os.path.join(REPO, "include", "fjsp.h")]
 
@@ -76,7 +77,8 @@ EXPORTS = ["fjsp_abi_version", "fjsp_last_error", "fjsp_default_config", "fjsp_c
            "fjsp_a2c_critic_backward", "fjsp_gae_shared",
            "fjsp_a2c_policy_step", "fjsp_a2c_group_temp_bytes", "fjsp_a2c_group_sort", "fjsp_a2c_group_runs",
            "fjsp_a2c_run_sums_bytes", "fjsp_a2c_run_sums", "fjsp_a2c_critic_fused", "fjsp_a2c_shard_keys", "fjsp_a2c_record_head", "fjsp_a2c_pack_mfma", "fjsp_a2c_slab_stats",
-           "fjsp_a2c_wgrad", "fjsp_server_start", "fjsp_server_step", "fjsp_server_step_actions", "fjsp_server_stop"]
+           "fjsp_a2c_wgrad", "fjsp_server_start", "fjsp_server_step", "fjsp_server_step_actions", "fjsp_server_stop",
+           "fjsp_episode_temp_bytes", "fjsp_episode_scan"]
 POLICY_ACTOR_DPAD, POLICY_CRITIC_DPAD = 16, 48
 POLICY_ACTOR_FLOATS = 3 * 256 * 16 // 2 + 256 + 3 * 256 * 256 // 2 + 256 + 8 * 256 + 16
 POLICY_CRITIC_FLOATS = 3 * 256 * 48 // 2 + 256 + 3 * 256 * 256 // 2 + 256 + 3 * 128 * 256 // 2 + 128 + 128 + 16
@@ -209,6 +211,8 @@ def lib():
         "fjsp_a2c_pack_mfma": (I, [P, I, I, I, I, P, P]),
         "fjsp_a2c_slab_stats": (I, [P, P, I, I, P, P, P, P]),
         "fjsp_a2c_wgrad": (I, [P, I, ctypes.c_int64, P, I, ctypes.c_int64, ctypes.c_int64, P, I, P, I, ctypes.c_int64, P]),
+        "fjsp_episode_temp_bytes": (I, [I, I, ctypes.POINTER(U64)]),
+        "fjsp_episode_scan": (I, [P, P, P, P, P, I, I, U32, ctypes.c_int64, P, P, P, ctypes.c_int64, P, P, U64, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

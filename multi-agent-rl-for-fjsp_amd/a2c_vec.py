@@ -1248,7 +1248,7 @@ class VecMultiAgentA2C:
 
     def __init__(self, env, batch_size=256, gamma=0.99, lamb=0.95, lr_actor=3e-4, lr_critic=1e-3,
                  use_gae=True, entropy_coef=0.01, max_grad_norm=0.5, hidden=256, seed=None, group=None,
-                 use_graph=None, fused_policy=True, exchange="allreduce", dedup=True):
+                 use_graph=None, fused_policy=True, exchange="allreduce", dedup=True, track_episodes=False):
         self.env = env
         self.device = env.device
         self.N = env.num_envs
@@ -1276,6 +1276,11 @@ class VecMultiAgentA2C:
         self.actor_loss_history = {a: [] for a in AGENTS}
         self.critic_loss_history = []
         self.episode_end_timesteps = []
+        self.overall_rewards = []
+        # episode accounting on the device (episodes.EpisodeLog; learn's a2c.py:311-313,346-376):
+        # off by default, the collect / update path is then unchanged
+        self.track_episodes = bool(track_episodes)
+        self.episode_log = None
         self._bufs = None
         # None: decided per collect (_graph_on); True / False: always / never replay a captured graph
         self.use_graph = None if use_graph is None else bool(use_graph) and self.device.type == "cuda"
@@ -1320,6 +1325,14 @@ class VecMultiAgentA2C:
             "trunc": z(T, N, dt=torch.uint8),
             "status": z(T, N, dt=torch.int32),
         }
+        if self.track_episodes:
+            from .episodes import EpisodeLog
+            # room for learn()'s drain interval: 4 batches at one episode per 16 steps and env
+            self.episode_log = EpisodeLog(N, dev, env_id_base=self.env.env_id_base,
+                                          capacity=max(65536, 4 * N * (T // 16 + 1)))
+            if not self.fused_step:   # fjsp_step writes the infos; the fused launch's outputs have no room
+                b["orders_completed"] = z(T, N, dt=torch.int32)
+                b["packaged"] = z(T, N, dt=torch.int32)
         outs = []
         for t in range(T):
             o = nat.fjsp_out()
@@ -1329,6 +1342,9 @@ class VecMultiAgentA2C:
             o.status = b["status"][t].data_ptr()
             o.next_masks = b["masks"][t + 1].data_ptr()
             o.feats = b["feats"][t + 1].data_ptr()
+            if "orders_completed" in b:
+                o.orders_completed = b["orders_completed"][t].data_ptr()
+                o.packaged = b["packaged"][t].data_ptr()
             outs.append(o)
         b["outs"] = outs
         self._bufs = b
@@ -1351,6 +1367,9 @@ class VecMultiAgentA2C:
         nat.check(nat.lib().fjsp_reset(self.env.handle, None if s is None else ctypes.c_void_p(s.data_ptr()),
                                        None, int(num_orders), ctypes.byref(o)))
         self.num_orders = int(num_orders)
+        if self.episode_log is not None:
+            self.episode_log.reset()   # every env starts a new episode,
+            self.episode_log.step0 = 0  # and end_step counts from this reset (a2c.py:278 global_timestep = 0)
 
     # ------------------------------------------------------------ predict
     @torch.no_grad()
@@ -1654,16 +1673,48 @@ class VecMultiAgentA2C:
         b["feats"][0].copy_(b["feats"][self.batch_size])
         b["masks"][0].copy_(b["masks"][self.batch_size])
 
+    def account_episodes(self):
+        """Scan the batch just collected into the episode log (track_episodes=True): one
+        fjsp_episode_scan over the slab's rewards / term / trunc (and the infos slabs of the
+        unfused collect), on the current stream, outside the collect and its graph."""
+        if self.episode_log is None:
+            raise RuntimeError("account_episodes needs track_episodes=True and an allocated rollout (reset())")
+        b = self._bufs
+        self.episode_log.scan(b["rewards"], b["term"], b["trunc"], b.get("orders_completed"), b.get("packaged"))
+
+    def episode_summary(self):
+        """Drain the episode log: extends overall_rewards with the episodes' totals (a2c.py:348-349)
+        and episode_end_timesteps with end_step * N, the shard's env-steps consumed when each ended
+        (a2c.py:350 in the unit learn(total_timesteps) counts in), in log order; returns the
+        records (EpisodeLog.pop(): global env ids, so ranks can concatenate their logs)."""
+        if self.episode_log is None:
+            raise RuntimeError("episode_summary needs track_episodes=True and an allocated rollout (reset())")
+        rec = self.episode_log.pop()
+        self.overall_rewards.extend(rec["total"].tolist())
+        self.episode_end_timesteps.extend((rec["end_step"] * self.N).tolist())
+        return rec
+
     def learn(self, total_timesteps, num_orders=25, seeds=None, deterministic=False, action_fn=None):
         """learn (a2c.py:254-388) on N envs: total_timesteps counts env-steps of this shard
-        (N per vector step); an update every batch_size vector steps."""
+        (N per vector step); an update every batch_size vector steps.  With track_episodes the
+        finished episodes of every batch are logged on the device; episode_summary() drains them."""
         self.reset(seeds=seeds, num_orders=num_orders)
-        steps = 0
+        if self.track_episodes:   # a2c.py:274,279: both lists start empty in every learn()
+            self.episode_summary()
+            self.overall_rewards, self.episode_end_timesteps = [], []
+        steps = batches = 0
         while steps < total_timesteps:
             self.collect(deterministic, action_fn)
+            if self.track_episodes:
+                self.account_episodes()
+                batches += 1
+                if batches % 4 == 0:   # drain before the log can fill (the only synchronisation)
+                    self.episode_summary()
             self.update()
             self.roll_over()
             steps += self.batch_size * self.N
+        if self.track_episodes:
+            self.episode_summary()
         return self
 
     @torch.no_grad()

@@ -1,0 +1,309 @@
+// fjsp_episode.hip — episode accounting over a rollout slab (include/fjsp.h: fjsp_episode_scan).
+//
+// MultiAgentA2C.learn's per-episode bookkeeping (a2c.py:311-313 episode_rewards[agent] += reward,
+// :346-350 total = sum(episode_rewards.values()), episode_end_timesteps, :373 the printed steps)
+// for every env of a [T][8][N] slab, on the device.  Three launches, ordered by the stream only
+// (no flags, no waits between workgroups, no atomics):
+//   k_episode_count    one wave per 64 envs x EP_U rows: per row the popcount of the ballot of
+//                      (term | trunc) -> temp[t][w], u32 [T][W], W = ceil(N / 64), and per env the
+//                      chunk's flags as one word (2 bits per row), u32 [ceil(T / EP_U)][64 W]
+//   k_episode_offsets  one workgroup: temp <- its exclusive scan in (t, w) order (the row-major
+//                      order a sequential reader of the slab meets the episode ends in), the
+//                      count at entry kept behind the table, *count advanced by the total
+//   k_episode_scan     one workgroup of 8 waves per 64 envs, wave a = agent a's running sum of the
+//                      64 envs (one lane per env), forward over t with the loads of EP_U rows in one
+//                      batch and the next batch issued before the scan (as k_gae).  Every wave reads
+//                      the same flag words, so every wave derives the same rank temp[t][w] +
+//                      popc(ballot & lanes below) of an episode end by itself; wave a stores
+//                      by_agent[a].  Only
+//                      `total` needs the eight sums in one place: they go through LDS, one barrier
+//                      pair per EP_U rows (unconditional: every wave runs the same T loop), and wave
+//                      j % 8 writes the record head of row j's ends (three 16-byte stores).
+// The arithmetic is one fp64 add per (step, agent) and the left-to-right sum of the eight, in the
+// reference's order; the library is built with -ffp-contract=off.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/fjsp.h"
+
+int fjsp_internal_fail(const char* msg);   // fjsp_hip.hip
+
+static_assert(sizeof(fjsp_episode_rec) == 112, "fjsp_episode_rec is 7 x 16 bytes");
+
+namespace {
+
+constexpr int EP_A = FJSP_NUM_AGENTS;
+constexpr int EP_U = 16;       // rows per wave of k_episode_count = per load batch of k_episode_scan
+constexpr int EPO_THREADS = 1024;
+
+__device__ __forceinline__ int lanes_below(uint64_t ballot, int lane) {
+    return __popcll(ballot & ((1ull << lane) - 1ull));
+}
+
+__global__ void __launch_bounds__(256) k_episode_count(const uint8_t* __restrict__ term,
+                                                       const uint8_t* __restrict__ trunc, int T, int N, int W,
+                                                       uint32_t* __restrict__ cnt, uint32_t* __restrict__ flags) {
+    const int lane = threadIdx.x & 63;
+    const long long g = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int chunks = (T + EP_U - 1) / EP_U;
+    if (g >= (long long)W * chunks) return;   // whole waves only: no lane of a live wave leaves
+    const int w = (int)(g % W), t0 = (int)(g / W) * EP_U;
+    const int e = w * 64 + lane;
+    uint8_t te[EP_U], tr[EP_U];
+#pragma unroll
+    for (int j = 0; j < EP_U; j++) {
+        te[j] = tr[j] = 0;
+        if (e < N && t0 + j < T) {
+            te[j] = term[(size_t)(t0 + j) * N + e];
+            tr[j] = trunc[(size_t)(t0 + j) * N + e];
+        }
+    }
+    uint32_t f = 0;   // bits 2j, 2j + 1 = row t0 + j terminated, truncated
+#pragma unroll
+    for (int j = 0; j < EP_U; j++) {
+        const uint32_t fj = (te[j] ? 1u : 0u) | (tr[j] ? 2u : 0u);
+        f |= fj << (2 * j);
+        const uint64_t b = __ballot(fj != 0);
+        if (lane == 0 && t0 + j < T) cnt[(size_t)(t0 + j) * W + w] = (uint32_t)__popcll(b);
+    }
+    flags[(size_t)(g / W) * ((size_t)W * 64) + e] = f;   // lanes e >= N: 0, inside the padded row
+}
+
+// Exclusive scan of cnt[0, L) in place (L = T W < 2^31 / 64, so the sums fit 32 bits): thread i
+// owns the elements [i per, (i + 1) per).  base[0] <- *count (the scan kernel's seq base), *count
+// advanced by the slab's total.
+__global__ void __launch_bounds__(EPO_THREADS) k_episode_offsets(uint32_t* __restrict__ cnt, int L,
+                                                                 long long* __restrict__ base,
+                                                                 long long* __restrict__ count) {
+    __shared__ uint32_t wsum[EPO_THREADS / 64];
+    const int i = threadIdx.x, lane = i & 63, wave = i >> 6;
+    const int per = (L + EPO_THREADS - 1) / EPO_THREADS;
+    const int lo = min(i * per, L), hi = min(lo + per, L);
+    uint32_t s = 0;
+    for (int k = lo; k < hi; k++) s += cnt[k];
+    uint32_t inc = s;   // inclusive scan of the threads' sums: within the wave, then over the waves
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(inc, d);
+        if (lane >= d) inc += o;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (int k = 0; k < EPO_THREADS / 64; k++) {
+        if (k < wave) before += wsum[k];
+        total += wsum[k];
+    }
+    uint32_t run = before + inc - s;
+    for (int k = lo; k < hi; k++) {
+        const uint32_t c = cnt[k];
+        cnt[k] = run;
+        run += c;
+    }
+    if (i == 0) {
+        const long long c0 = *count;
+        base[0] = c0;
+        *count = c0 + (long long)total;
+    }
+}
+
+struct EpChunk {
+    double r[EP_U];
+    uint32_t off[EP_U];
+    uint32_t f;   // k_episode_count's flag word: 2 bits per row (terminated, truncated), 0 past the slab
+};
+
+// The loads of rows t0 .. t0 + EP_U - 1 (rows past the slab clamped to its last row: never used,
+// and no branch around a load).  GUARD: the workgroup holding lanes e >= N, which load nothing
+// from the slab (their flag words are 0 in temp's padded rows).
+template <bool GUARD>
+__device__ __forceinline__ void ep_load(EpChunk& c, const double* __restrict__ r, const uint32_t* __restrict__ flags,
+                                        const uint32_t* __restrict__ offs, int t0, int T, int N, int W, int a, int e,
+                                        int w, bool live) {
+    const int ch = (t0 < T ? t0 : T - 1) / EP_U;
+    c.f = flags[(size_t)ch * ((size_t)W * 64) + e];
+#pragma unroll
+    for (int j = 0; j < EP_U; j++) {
+        const int t = t0 + j < T ? t0 + j : T - 1;
+        // wave-uniform row pointers + the lane's 32-bit column: scalar base, vector offset
+        const double* __restrict__ rr = r + ((size_t)t * EP_A + a) * N;
+        c.off[j] = offs[(size_t)t * W + w];
+        c.r[j] = 0.0;
+        if (!GUARD || live) c.r[j] = rr[e];
+    }
+}
+
+struct EpArgs {
+    const int32_t* oc;
+    const int32_t* pk;
+    fjsp_episode_rec* recs;
+    long long cap, base, step0;
+    uint32_t gid0;
+    int T, N;
+};
+
+// Rows t0 .. t0 + EP_U - 1 of one agent's 64 envs; sh[j][a][lane] = the agent's sum at an end in
+// row j.  Two barriers, reached by every wave of the workgroup for every chunk.  The episode's
+// length follows from the flag word alone: the rows since the chunk's previous end, or the open
+// episode's steps at the chunk's start (len) plus the rows up to this one.
+__device__ __forceinline__ void ep_scan(const EpChunk& c, const uint32_t* __restrict__ offs, int t0, const EpArgs& p,
+                                        int W, int a, int w, int e, int lane, double& acc, int& len,
+                                        double (*sh)[EP_A][64]) {
+#pragma unroll
+    for (int j = 0; j < EP_U; j++) {
+        const bool done = ((c.f >> (2 * j)) & 3u) != 0;   // never set past the slab
+        const uint64_t b = __ballot(done);
+        if (t0 + j < p.T) acc = acc + c.r[j];             // wave-uniform
+        if (done) {
+            const long long seq = p.base + (long long)c.off[j] + lanes_below(b, lane);
+            if ((unsigned long long)seq < (unsigned long long)p.cap) p.recs[seq].by_agent[a] = acc;
+            sh[j][a][lane] = acc;
+            acc = 0.0;
+        }
+    }
+    __syncthreads();
+    for (int h = 0; h < EP_U / EP_A; h++) {   // wave a writes the heads of rows a and a + 8
+        const int j = a + EP_A * h;
+        const uint32_t fj = (c.f >> (2 * j)) & 3u;
+        const uint64_t b = __ballot(fj != 0);
+        if (fj != 0) {
+            const size_t t = (size_t)(t0 + j);
+            const long long seq = p.base + (long long)offs[t * W + w] + lanes_below(b, lane);
+            if ((unsigned long long)seq < (unsigned long long)p.cap) {
+                double total = 0.0;
+#pragma unroll
+                for (int k = 0; k < EP_A; k++) total = total + sh[j][k][lane];
+                const uint32_t prior = c.f & ((1u << (2 * j)) - 1u);
+                const int length = prior ? j - ((31 - __clz(prior)) >> 1) : len + j + 1;
+                const size_t at = t * p.N + e;
+                const int oc = p.oc ? p.oc[at] : -1, pk = p.pk ? p.pk[at] : -1;
+                const long long end = p.step0 + (long long)t + 1;
+                uint4* q = reinterpret_cast<uint4*>(p.recs + seq);
+                q[0] = make_uint4(p.gid0 + (uint32_t)e, (uint32_t)length, (uint32_t)end,
+                                  (uint32_t)((unsigned long long)end >> 32));
+                q[1] = make_uint4((uint32_t)seq, (uint32_t)((unsigned long long)seq >> 32), fj, (uint32_t)oc);
+                const unsigned long long tb = (unsigned long long)__double_as_longlong(total);
+                q[2] = make_uint4((uint32_t)pk, 0u, (uint32_t)tb, (uint32_t)(tb >> 32));
+            }
+        }
+    }
+    const int rows = min(EP_U, p.T - t0);
+    len = c.f ? rows - 1 - ((31 - __clz(c.f)) >> 1) : len + rows;
+    __syncthreads();
+}
+
+template <bool GUARD>
+__device__ __forceinline__ void ep_body(const double* __restrict__ r, const uint32_t* __restrict__ flags,
+                                        const uint32_t* __restrict__ offs, const EpArgs& p, int W,
+                                        double* __restrict__ accp, int32_t* __restrict__ lenp,
+                                        double (*sh)[EP_A][64]) {
+    const int lane = threadIdx.x & 63;
+    const int a = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int w = blockIdx.x, e = w * 64 + lane;
+    const int T = p.T, N = p.N;
+    const bool live = !GUARD || e < N;
+    double acc = 0.0;
+    int len = 0;
+    if (live) {
+        acc = accp[(size_t)a * N + e];
+        len = lenp[e];
+    }
+    EpChunk A, B;
+    int t0 = 0;
+    ep_load<GUARD>(A, r, flags, offs, 0, T, N, W, a, e, w, live);
+    for (;;) {   // A holds t0.., B is loaded before A's scan, and the other way round
+        ep_load<GUARD>(B, r, flags, offs, t0 + EP_U, T, N, W, a, e, w, live);
+        ep_scan(A, offs, t0, p, W, a, w, e, lane, acc, len, sh);
+        t0 += EP_U;
+        if (t0 >= T) break;
+        ep_load<GUARD>(A, r, flags, offs, t0 + EP_U, T, N, W, a, e, w, live);
+        ep_scan(B, offs, t0, p, W, a, w, e, lane, acc, len, sh);
+        t0 += EP_U;
+        if (t0 >= T) break;
+    }
+    if (live) {
+        accp[(size_t)a * N + e] = acc;
+        if (a == 0) lenp[e] = len;
+    }
+}
+
+__global__ void __launch_bounds__(64 * EP_A) k_episode_scan(const double* __restrict__ r,
+                                                            const uint32_t* __restrict__ flags,
+                                                            const uint32_t* __restrict__ offs,
+                                                            const long long* __restrict__ base, EpArgs p, int W,
+                                                            double* __restrict__ accp,
+                                                            int32_t* __restrict__ lenp) {
+    __shared__ double sh[EP_U][EP_A][64];
+    p.base = base[0];
+    if ((int)blockIdx.x * 64 + 64 <= p.N) ep_body<false>(r, flags, offs, p, W, accp, lenp, sh);
+    else ep_body<true>(r, flags, offs, p, W, accp, lenp, sh);
+}
+
+// temp: the offsets table u32 [T][W] (padded to 16 bytes), 16 bytes for the count at entry, the
+// flag words u32 [ceil(T / EP_U)][64 W]
+bool ep_temp_layout(int32_t T, int32_t N, uint64_t* table, uint64_t* total) {
+    const int64_t W = ((int64_t)N + 63) / 64, L = (int64_t)T * W;
+    if (L * 64 > INT32_MAX) return false;
+    *table = ((uint64_t)L * 4 + 15) & ~(uint64_t)15;
+    *total = *table + 16 + (uint64_t)((T + EP_U - 1) / EP_U) * (uint64_t)W * 64 * 4;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fjsp_episode_temp_bytes(int32_t T, int32_t N, uint64_t* bytes) {
+    if (T <= 0 || N <= 0) return fjsp_internal_fail("fjsp_episode_temp_bytes: T and N must be > 0");
+    if (!bytes) return fjsp_internal_fail("fjsp_episode_temp_bytes: null pointer");
+    uint64_t table, total;
+    if (!ep_temp_layout(T, N, &table, &total)) return fjsp_internal_fail("fjsp_episode_temp_bytes: T * N must be < 2^31");
+    *bytes = total;
+    return 0;
+}
+
+int fjsp_episode_scan(const double* rewards, const uint8_t* term, const uint8_t* trunc, const int32_t* orders_completed,
+                      const int32_t* packaged, int32_t T, int32_t N, uint32_t env_gid0, int64_t step0, double* acc,
+                      int32_t* len, fjsp_episode_rec* recs, int64_t cap, int64_t* count, void* temp, uint64_t temp_bytes,
+                      void* stream) {
+    if (T <= 0 || N <= 0) return fjsp_internal_fail("fjsp_episode_scan: T and N must be > 0");
+    if (cap < 0) return fjsp_internal_fail("fjsp_episode_scan: cap must be >= 0");
+    if (!rewards || !term || !trunc || !acc || !len || !count || !temp || (cap > 0 && !recs))
+        return fjsp_internal_fail("fjsp_episode_scan: null buffer");
+    uint64_t table, total;
+    if (!ep_temp_layout(T, N, &table, &total)) return fjsp_internal_fail("fjsp_episode_scan: T * N must be < 2^31");
+    if (temp_bytes < total) return fjsp_internal_fail("fjsp_episode_scan: temp buffer too small");
+    if ((((uintptr_t)recs | (uintptr_t)temp) & 15u) != 0)
+        return fjsp_internal_fail("fjsp_episode_scan: recs and temp must be 16-byte aligned");
+    const int W = (int)(((int64_t)N + 63) / 64);   // T W 64 < 2^31 (checked above)
+    const int L = T * W;
+    uint32_t* offs = (uint32_t*)temp;
+    long long* base = (long long*)((char*)temp + table);
+    uint32_t* flags = (uint32_t*)((char*)temp + table + 16);
+    const hipStream_t st = (hipStream_t)stream;
+    const long long waves = (long long)W * ((T + EP_U - 1) / EP_U);
+    hipLaunchKernelGGL(k_episode_count, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, term, trunc, T, N, W, offs,
+                       flags);
+    hipLaunchKernelGGL(k_episode_offsets, dim3(1), dim3(EPO_THREADS), 0, st, offs, L, base, (long long*)count);
+    EpArgs p;
+    p.oc = orders_completed;
+    p.pk = packaged;
+    p.recs = recs;
+    p.cap = cap;
+    p.base = 0;
+    p.step0 = step0;
+    p.gid0 = env_gid0;
+    p.T = T;
+    p.N = N;
+    hipLaunchKernelGGL(k_episode_scan, dim3((unsigned)W), dim3(64 * EP_A), 0, st, rewards, flags, offs, base, p, W,
+                       acc, len);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        fjsp_internal_fail(hipGetErrorString(e));
+        return -2;
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -237,6 +237,28 @@ class FJSPVecEnv:
                 "products_packaged": pick(b.packaged), "total_orders": num_orders,
                 "rewards_by_agent": by_agent, "total_reward": np.cumsum(by_agent, axis=0)[-1]}
 
+    def evaluate_episodes(self, policy="heuristic", num_orders=5, steps=500, seeds=None, action_seed=0, chunk=256):
+        """Every finished episode of every env over `steps` vector steps from a reset, with
+        auto-reset (an env starts its next episode at once; a2c.py:346-381): rollout(chunk, ...)
+        into one reused Buffers, each followed by EpisodeLog.scan on the device.  Returns
+        EpisodeLog.pop()'s dict of records (env, length, end_step, total, by_agent [8, n], ...).
+        Only the records reach the host; no reward slab is copied."""
+        from .episodes import EpisodeLog
+        steps, chunk = int(steps), max(1, min(int(chunk), int(steps)))
+        self.reset(seeds=seeds, num_orders=num_orders)
+        # room for one episode per 16 steps and env (the shortest heuristic episodes take ~30);
+        # what does not fit is counted in the result's `dropped`, never written
+        log = EpisodeLog(self.num_envs, self.device, env_id_base=self.env_id_base,
+                         capacity=max(65536, self.num_envs * (steps // 16 + 1)))
+        b = Buffers(chunk, self.num_envs, self.device, infos=True)
+        done = 0
+        while done < steps:
+            k = min(chunk, steps - done)
+            self.rollout(k, action_seed=action_seed, step0=done, policy=policy, autoreset=True, buffers=b)
+            log.scan(b.rewards[:k], b.term[:k], b.trunc[:k], b.orders_completed[:k], b.packaged[:k])
+            done += k
+        return log.pop()
+
     def pack_a2c(self, feats=None, masks=None):
         """a2c features f32 [38, N] and masks int8 [29, N] of the current observations
         (MultiAgentA2C._get_global_state, a2c.py:153-166)."""
