@@ -49,7 +49,27 @@ extern "C" {
 #define FJSP_MAX_ORDERS 64     /* num_orders limit per episode */
 #define FJSP_ACTION_ABSENT 255 /* agent missing from the action dict (no execute_action call) */
 
-/* status bits (per env, sticky until reset) */
+/* status bits (per env).  The contract every step path keeps (tests/test_gpu_status.py compares
+ * each of them with the oracle bit for bit):
+ *   - a bit is sticky within its episode: once set it stays set in every status emitted until the
+ *     episode ends;
+ *   - the step that ends an episode (term | trunc) still carries that episode's bits; with
+ *     auto-reset the first step of the next episode starts from a clean word;
+ *   - every reset path clears the word: auto-reset inside any step kernel, fjsp_reset with or
+ *     without a mask or seeds;
+ *   - after a launch the env's state word (fjsp_read_env().status, fjsp_snapshot) equals the last
+ *     status it emitted (0 if that step ended its episode and auto-reset is on), and a restored
+ *     snapshot carries it on.
+ * DIVERGED marks an env whose outputs no longer follow the reference (drop it from the batch until
+ * its next episode); OBS_OVERFLOW / PKG_WAIT / SLOT_OVERFLOW / SPIN_TIMEOUT give the reason and
+ * come with DIVERGED.  TRAY_LOST, PROD_LOST and OVERWRITE record reference behaviour and leave the
+ * env exact.
+ * OBS_OVERFLOW is reachable inside a valid episode (a packaging station that never starts, 128
+ * products queued by step 248; tests/overflow_scripts.py).  SLOT_OVERFLOW is unreachable under
+ * fjsp_check_config's limits while episodes end at their truncation (at most one tray per step:
+ * 254 trays for 255 slots); kept as a guard for callers that step past the truncation with
+ * autoreset = 0.  k_step_ag's private copies of the int8 check are not executed by any test (its
+ * uniform-random actions cannot be scripted). */
 #define FJSP_STATUS_DIVERGED     0x1u   /* a path the reference would raise on / that is not emulated */
 #define FJSP_STATUS_OBS_OVERFLOW 0x2u   /* int8 obs > 127 (numpy OverflowError in the reference) */
 #define FJSP_STATUS_PKG_WAIT     0x4u   /* packaging request exceeded Resource capacity (not emulated) */

@@ -93,6 +93,127 @@ def chunk_digests(get_record, steps, chunk):
     return row
 
 
+STATUS_BITS = {"TRAY_LOST": 0x8, "PROD_LOST": 0x10, "OVERWRITE": 0x20}
+
+# The status configurations (tests/test_gpu_status.py, tests/test_hostsim_logic.py): env seeds
+# arange(n) * 11 + 2; "target" = the bit the configuration exists to provoke in comparable envs
+# ("flagged": PKG_WAIT | DIVERGED, i.e. env-steps that leave the comparison).  C's action seed
+# was searched with the oracle alone (0..5999, 200 envs x 260 steps): 4602 is the first at which
+# PROD_LOST appears in unflagged envs of at least 4 different 16-env blocks under both random
+# policies, with nothing flagged (see test_gpu_status.py's docstring for the counts).
+STATUS_SEED_MUL, STATUS_SEED_ADD = 11, 2
+STATUS_CFGS = {
+    "A": dict(cfg={}, num_orders=30, action_seed=13, target="OVERWRITE"),
+    "B": dict(cfg={"storage_capacity": 0}, num_orders=12, action_seed=13, target="TRAY_LOST"),
+    "C": dict(cfg={"packaging_capacity": 2, "tray_capacity": 2, "mask_tray_capacity": 2, "pt_packaging": 250,
+                   "pt_small": 10, "pt_big": 10}, num_orders=20, action_seed=4602, target="PROD_LOST"),
+    "D": dict(cfg={"packaging_capacity": 2, "pt_packaging": 200}, num_orders=20, action_seed=13, target="flagged"),
+    "E": dict(cfg={"packaging_capacity": 2, "pt_packaging": 200, "storage_capacity": 1, "max_episode_steps": 90},
+              num_orders=20, action_seed=13, target="TRAY_LOST"),
+}
+
+
+def status_seeds(n):
+    return (np.arange(n, dtype=np.int64) * STATUS_SEED_MUL + STATUS_SEED_ADD).astype(np.uint32)
+
+
+def status_conditions(name, r, what=""):
+    """The conditions every status comparison of configuration `name` must meet, on
+    status_parity's result: no env-step excluded in A, B and C, at most 5 % in D and E, and at
+    least 50 env-steps carrying the targeted bit (so that no test passes on an empty comparison)."""
+    c = STATUS_CFGS[name]
+    if name in "ABC":
+        assert r["flagged"] == 0 and r["excluded"] == 0.0, (what, r)
+    else:
+        assert r["excluded"] <= 0.05, (what, r)
+    hit = r["flagged"] if c["target"] == "flagged" else r["counts"][c["target"]]
+    assert hit >= 50, (what, c["target"], r)
+
+
+def _first(bad):
+    """(step, env) of the first set element of a [steps, n] bool array, for assertion messages."""
+    t, e = np.argwhere(bad)[0]
+    return int(t), int(e)
+
+
+def status_parity(got_status, rec, what="", got_ended=None):
+    """The kernels' per-env status words against the oracle's, over [steps, n] env-steps.
+
+    got_status: uint32 [steps, n] as a step kernel (or the host build of fjsp_env.h) emitted them;
+    rec: the oracle's records of the same env-steps (O.rollout's [steps, n] array, or any mapping
+    with "status", "term" and "trunc"); got_ended: the kernel's own term | trunc of those env-steps.
+    An env-step is comparable when neither side flags a path
+    the closed form does not emulate: FJSP_STATUS_DIVERGED here, ST_EXCEPTION | ST_OBS_OVERFLOW |
+    ST_PKG_WAIT there.  Asserted:
+      - the two flagged sets are equal (up to the reference raising, see below);
+      - the reference-behaviour bits (TRAY_LOST | PROD_LOST | OVERWRITE, 0x38) are equal on every
+        comparable env-step: set at the same step, sticky to the episode's last step (the step
+        that ends the episode still carries them), clean at the next episode's first step;
+      - SLOT_OVERFLOW (0x40) and SPIN_TIMEOUT (0x80) are zero everywhere, as is the oracle's own
+        limit bit;
+      - the reason bits (OBS_OVERFLOW | PKG_WAIT, 0x6) are equal at the FIRST flagged step of an
+        env's episode.  Only there: from that step on the kernel stops emulating the env while
+        the oracle's event heap goes on, so the oracle may add reasons later (a waiting packaging
+        Request and later the reference raising) that the kernel's frozen view never meets.
+        (Row 0 has no history: a flagged env there counts as a first flagged step, and a raise
+        there as the raise's first step.  A one-row call, as the host tests make per step,
+        therefore compares the reason bits at every flagged step and cannot see DIVERGED being
+        dropped inside an episode; the whole-rollout call with got_ended does.)
+    Returns {"counts": {bit name: comparable env-steps carrying it in the oracle}, "comparable",
+    "flagged", "flagged_envs", "excluded" (share of env-steps that are not comparable)}."""
+    from oracle import oracle as O
+    got = np.asarray(got_status).astype(np.uint32)
+    want = np.asarray(rec["status"]).astype(np.uint32)
+    assert got.ndim == 2 and got.shape == want.shape, (what, got.shape, want.shape)
+    ended = (np.asarray(rec["term"]) | np.asarray(rec["trunc"])).astype(bool)
+    assert not (want & 0x80000000).any(), (what, "the oracle hit one of its own limits")
+    g_div = (got & 1) != 0
+    o_div = (want & (O.ST_EXCEPTION | O.ST_OBS_OVERFLOW | O.ST_PKG_WAIT)) != 0
+    # Where the reference raises (ST_EXCEPTION) its process is gone: the oracle zeroes that env's
+    # records from then on and never resets it, while the kernel's env stays flagged to the end
+    # of its episode and starts the next one clean.  Such an env leaves the comparison (it
+    # counts as excluded) only after the kernel flagged it at the very step of the oracle's
+    # raise and then came back clean, which it may do only right after a step that ended its
+    # episode (checked when got_ended is given).
+    exc = (want & O.ST_EXCEPTION) != 0
+    raised = np.logical_or.accumulate(exc, axis=0)
+    first_raise = raised.copy()
+    first_raise[1:] &= ~raised[:-1]
+    bad = first_raise & ~g_div
+    assert not bad.any(), (what, "the reference raises, DIVERGED is not set, at (step, env)", _first(bad),
+                           hex(got[_first(bad)]), hex(want[_first(bad)]))
+    back = raised & ~g_div           # (never at the raise itself, by the assertion above)
+    if got_ended is not None:
+        prev_end = np.zeros_like(back)
+        prev_end[1:] = np.asarray(got_ended).astype(bool)[:-1]
+        was = np.zeros_like(back)
+        was[1:] = g_div[:-1]
+        bad = back & was & ~prev_end
+        assert not bad.any(), (what, "DIVERGED dropped inside an episode at (step, env)", _first(bad))
+    dead = np.logical_or.accumulate(back, axis=0)
+    bad = (g_div != o_div) & ~dead
+    assert not bad.any(), (what, "flagged sets differ first at (step, env)", _first(bad),
+                           hex(got[_first(bad)]), hex(want[_first(bad)]))
+    g_div = g_div | o_div            # (differs from g_div only where dead)
+    bad = (got & 0xC0) != 0
+    assert not bad.any(), (what, "SLOT_OVERFLOW / SPIN_TIMEOUT at (step, env)", _first(bad), hex(got[_first(bad)]))
+    ok = ~g_div
+    bad = ok & ((got & 0x38) != (want & 0x38))
+    assert not bad.any(), (what, "status & 0x38 differs first at (step, env)", _first(bad),
+                           hex(got[_first(bad)]), hex(want[_first(bad)]), int(bad.sum()))
+    # comparable env-steps carry nothing but the three reference-behaviour bits
+    bad = ok & ((got & ~np.uint32(0x38)) != 0)
+    assert not bad.any(), (what, "stray bits at (step, env)", _first(bad), hex(got[_first(bad)]))
+    first = g_div.copy()
+    first[1:] &= ~g_div[:-1] | ended[:-1]
+    bad = first & ((got & 0x6) != (want & 0x6))
+    assert not bad.any(), (what, "reason bits differ at a first flagged (step, env)", _first(bad),
+                           hex(got[_first(bad)]), hex(want[_first(bad)]))
+    return {"counts": {k: int((ok & ((want & b) != 0)).sum()) for k, b in STATUS_BITS.items()},
+            "comparable": int(ok.sum()), "flagged": int(g_div.sum()), "flagged_envs": int(g_div.any(0).sum()),
+            "excluded": float(g_div.mean()) if g_div.size else 0.0}
+
+
 def param_shapes():
     """Shapes of the learner's parameters in flat_grads order (8 stacked actors, then the critic)."""
     import importlib

@@ -58,9 +58,9 @@ class HS:
         self.L.hs_reset(self.h, s.ctypes.data, num_orders, self.i32.ctypes.data, self.i8.ctypes.data,
                         self.f32.ctypes.data, self.mk.ctypes.data)
 
-    def step(self, acts):
+    def step(self, acts, autoreset=1):
         a = np.ascontiguousarray(acts, np.uint8)
-        self.L.hs_step(self.h, a.ctypes.data, 1, *[x.ctypes.data for x in (
+        self.L.hs_step(self.h, a.ctypes.data, autoreset, *[x.ctypes.data for x in (
             self.i32, self.i8, self.f32, self.mk, self.rew, self.term, self.trunc, self.res, self.st,
             self.ri32, self.ri8, self.rf32, self.rmk)])
 
@@ -71,18 +71,32 @@ class HS:
     (0, {"storage_capacity": 2}, 5, 32, 500),
     (1, {"tray_capacity": 3, "max_episode_steps": 50}, 3, 32, 500),
     (1, {"packaging_capacity": 2, "num_trays": 40}, 20, 32, 600),
+    (0, "B", None, 200, 260),
+    (1, "B", None, 200, 260),
+    (0, "C", None, 200, 260),
+    (1, "C", None, 200, 260),
+    (0, "E", None, 200, 260),
+    (1, "E", None, 200, 260),
 ])
 def test_closed_form_vs_oracle(L, policy, cfg, norders, n, steps):
+    seeds, aseed, scfg = np.arange(n, dtype=np.uint32) + 100, 0, None
+    if isinstance(cfg, str):   # a status configuration (parity_util.STATUS_CFGS), with its seeds
+        scfg, c = cfg, P.STATUS_CFGS[cfg]
+        cfg, norders, aseed, seeds = c["cfg"], c["num_orders"], c["action_seed"], P.status_seeds(n)
     hs = HS(L, n, cfg)
-    seeds = np.arange(n, dtype=np.uint32) + 100
     hs.reset(seeds, norders)
-    rec, rst, _ = O.rollout(n, steps, seeds=seeds, gid0=0, num_orders=norders, policy=policy,
+    rec, rst, _ = O.rollout(n, steps, seeds=seeds, gid0=0, num_orders=norders, policy=policy, action_seed=aseed,
                             record_resets=True, **cfg)
     masks = hs.mk.copy()
+    status, ended = np.zeros((steps, n), np.uint32), np.zeros((steps, n), bool)
     for t in range(steps):
-        acts = np.stack([O.actions(0, e, t, masks[e] if policy == 1 else None) for e in range(n)])
+        acts = np.stack([O.actions(aseed, e, t, masks[e] if policy == 1 else None) for e in range(n)])
         hs.step(acts)
         R = rec[t]
+        status[t], ended[t] = hs.st, (hs.term | hs.trunc) != 0
+        # every status bit of this step against the oracle's (the flagged sets, the reference-
+        # behaviour bits on comparable envs, no stray bits)
+        P.status_parity(status[t:t + 1], rec[t:t + 1], t)
         # the kernel flags (and stops emulating) paths the oracle emulates by the event heap:
         # a packaging Request that waits (users == capacity) or the reference raising
         k_div = (hs.st & 1) != 0
@@ -94,6 +108,60 @@ def test_closed_form_vs_oracle(L, policy, cfg, norders, n, steps):
             a, b = mine[ok_env], np.asarray(R[name])[ok_env]
             assert a.tobytes() == np.ascontiguousarray(b).tobytes(), (t, name)
         masks = hs.rmk.copy()
+    # the whole rollout at once: also the reason bits at each episode's first flagged step
+    r = P.status_parity(status, rec, (cfg, policy), got_ended=ended)
+    print(f"test_closed_form_vs_oracle {cfg} policy={policy}: {r}")
+    if scfg:
+        P.status_conditions(scfg, r)
+        if scfg == "E":
+            assert ended.sum() >= 2 * n, "E is there for the bits cleared at auto-resets"
+
+
+def test_obs_overflow_script(L):
+    """FJSP_STATUS_OBS_OVERFLOW, reached inside a valid episode by tests/overflow_scripts.py's
+    controller (the 128th queued product at a packaging station that never starts): the host build
+    flags OBS_OVERFLOW | DIVERGED at the oracle's step, writes the same wrapped int8 (-128), keeps
+    the bits to the episode's truncation and starts the next episode clean."""
+    from tests import overflow_scripts as S
+    acts, seeds, judge, tf = S.obs_overflow_case()
+    hs = HS(L, 3, S.OBS_CFG)
+    hs.reset(seeds, S.OBS_ORDERS)
+    T = len(acts)
+    status, ended, i8 = np.zeros((T, 3), np.uint32), np.zeros((T, 3), bool), np.zeros((T, 3, 12), np.int8)
+    for t in range(T):
+        hs.step(acts[t].T)
+        status[t], ended[t], i8[t] = hs.st, (hs.term | hs.trunc) != 0, hs.i8
+        ok = (hs.st & 1) == 0
+        ok[1] &= t < tf          # the oracle's env 1 is gone once the reference has raised
+        for name, mine in (("obs_i32", hs.i32), ("obs_i8", hs.i8), ("masks", hs.mk), ("rewards", hs.rew),
+                           ("results", hs.res)):
+            assert np.ascontiguousarray(mine[ok]).tobytes() == np.ascontiguousarray(judge[t][name][ok]).tobytes(), (t, name)
+    S.check_obs_overflow(status, i8, ended, judge, tf)
+
+
+def test_slot_overflow_script(L):
+    """FJSP_STATUS_SLOT_OVERFLOW cannot occur inside an episode (at most 254 trays for 255 slots);
+    a caller that steps past the truncation without a reset reaches it at the 256th tray: equal to
+    the oracle up to there, then SLOT_OVERFLOW | DIVERGED (the oracle has no arena and goes on),
+    the tray is dropped rather than written past the arena, and a reset clears the word."""
+    from tests import overflow_scripts as S
+    acts, recs = S.slot_overflow_script()
+    hs = HS(L, 1, S.SLOT_CFG)
+    hs.reset([S.SLOT_SEED], S.SLOT_ORDERS)
+    for t in range(len(acts)):
+        hs.step(acts[t:t + 1], autoreset=0)
+        if t < 255:
+            assert hs.st[0] == 0, t
+            for name, mine in (("obs_i32", hs.i32), ("obs_i8", hs.i8), ("masks", hs.mk), ("rewards", hs.rew),
+                               ("results", hs.res), ("trunc", hs.trunc)):
+                assert np.ascontiguousarray(mine[0]).tobytes() == np.ascontiguousarray(recs[t][name]).tobytes(), (t, name)
+        else:
+            assert hs.st[0] == 0x41 and recs[t]["status"] == 0, t
+            assert hs.i32[0, 14] == 255            # ready_trays stays at the arena's 255 slots
+    assert recs["trunc"][253:].all() and not recs["trunc"][:253].any()
+    hs.reset([S.SLOT_SEED], S.SLOT_ORDERS)
+    hs.step(acts[:1], autoreset=0)
+    assert hs.st[0] == 0 and np.ascontiguousarray(hs.i32[0]).tobytes() == recs[0]["obs_i32"].tobytes()
 
 
 @pytest.mark.parametrize("tr", P.load_traces() + P.load_scenarios(), ids=lambda t: t.name)
@@ -161,6 +229,7 @@ def test_property_random_configs_and_actions(L):
             a = np.array(a, np.uint8)
             hs.step(a[None])
             r = o.step(a)
+            P.status_parity(hs.st.reshape(1, 1), {k: np.asarray(r[k]).reshape(1, 1) for k in ("status", "term", "trunc")})
             if r["status"] & (O.ST_EXCEPTION | O.ST_PKG_WAIT | O.ST_OBS_OVERFLOW):
                 break
             for name, mine in (("obs_i32", hs.i32), ("obs_i8", hs.i8), ("masks", hs.mk), ("rewards", hs.rew),
