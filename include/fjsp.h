@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FJSP_ABI_VERSION 12
+#define FJSP_ABI_VERSION 13
 
 #define FJSP_NUM_AGENTS 8      /* pickup, agv, small, big, pkg_blue_1, pkg_blue_2, pkg_red, pkg_green */
 #define FJSP_OBS_I32 20        /* pickup 7 + agv 13 (position = 2) int32 observation fields */
@@ -181,9 +181,7 @@ int fjsp_destroy(fjsp_handle* h);
 int fjsp_set_stream(fjsp_handle* h, void* hip_stream);
 /* Tuning knobs: "fused_lds" (-1/0/1, default -1 = auto, on while N <= 16384: stage the per-env
  * tables of k_step_many in LDS, one 64-env workgroup per CU); "pipeline" (0/1, default 1: lean
- * outputs use the two-wave pipelined kernel); "staged_stores" (0/1, default 0: k_step_many stages each
- * step's obs / masks / rewards / term / trunc / status in LDS and writes them as 16-byte
- * chunks; used when only those outputs are requested, N % 64 == 0 and rows are aligned);
+ * outputs use the two-wave pipelined kernel; ABI 13 removed "staged_stores", now an unknown option);
  * "timing" (0/1, default 1: bracket fjsp_step / fjsp_step_many launches with hipEvents for
  * fjsp_last_kernel_ms; set 0 while capturing the calls into a hipGraph); "predraw" (0/1,
  * default 1: the pipelined kernel with LDS tables and auto-reset draws every env's next order

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("FJSP_LIB") or os.path.join(HERE, "libfjsp.so")
 SRC = os.path.join(HERE, "csrc", "fjsp_hip.hip")
 SRCS = [SRC, os.path.join(HERE, "csrc", "fjsp_policy.hip"), os.path.join(HERE, "csrc", "fjsp_group.hip"),
         os.path.join(HERE, "csrc", "fjsp_episode.hip")]
-HEADERS = [os.path.join(HERE, "csrc", h) for h in ("fjsp_env.h", "fjsp_stepdev.h", "fjsp_stamps.h")] + [
+HEADERS = [os.path.join(HERE, "csrc", h) for h in ("fjsp_env.h", "fjsp_select.h", "fjsp_stepdev.h", "fjsp_stamps.h")] + [
     os.path.join(REPO, "include", "fjsp.h")]
 
 # the drop-in facade's host helper (CPython extension, no GPU code): csrc/fjsp_facade.c
@@ -83,7 +83,7 @@ POLICY_ACTOR_DPAD, POLICY_CRITIC_DPAD = 16, 48
 POLICY_ACTOR_FLOATS = 3 * 256 * 16 // 2 + 256 + 3 * 256 * 256 // 2 + 256 + 8 * 256 + 16
 POLICY_CRITIC_FLOATS = 3 * 256 * 48 // 2 + 256 + 3 * 256 * 256 // 2 + 256 + 3 * 128 * 256 // 2 + 128 + 128 + 16
 CRITIC_FUSED_PW = 2 * 256 + 2 * 128 + 4   # floats per tile of fjsp_a2c_critic_fused's partial sums
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _lib = None
 

@@ -36,6 +36,7 @@ namespace fjsp {
 FJSP_DEV float __uint_as_float_fjsp(uint32_t u) { float f; __builtin_memcpy(&f, &u, 4); return f; }
 FJSP_DEV uint32_t __float_as_uint_fjsp(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
 
+constexpr int BLOCK = 64;   // lanes of a wavefront = envs of a full workgroup
 constexpr int NA = 8;
 constexpr int NI32 = 20, NI8 = 12, NF32 = 6, NMASK = 29;
 constexpr int MAX_ORDERS = 64;

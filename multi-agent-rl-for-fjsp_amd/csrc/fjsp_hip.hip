@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "fjsp_env.h"
+#include "fjsp_select.h"
 #include "fjsp_stamps.h"
 #include "fjsp_stepdev.h"
 #include "../../include/fjsp.h"
@@ -141,86 +142,6 @@ __device__ __forceinline__ void synth_actions(uint64_t seed, uint32_t gid, uint3
 }
 
 // One full env step + outputs at trajectory index t; handles auto-reset.
-// Per-wave LDS staging tile of one step's lean outputs ([F][64] per field block).  The step
-// writes it with ds_write (StageSink), then the wave copies each block out as whole 16-byte
-// chunks: ~15 global_store_dwordx4 (every instruction 1 KiB contiguous) instead of ~85
-// scalar-per-lane stores.  Requires N % 64 == 0 and 16-byte aligned outputs (host-checked).
-struct alignas(16) StageTile {
-    int32_t i32[NI32 * BLOCK];
-    float f32[NF32 * BLOCK];
-    double rew[NA * BLOCK];
-    uint32_t status[BLOCK];
-    int8_t i8[NI8 * BLOCK];
-    int8_t mask[NMASK * BLOCK];
-    uint8_t term[BLOCK];
-    uint8_t trunc[BLOCK];
-};
-struct StageSink {
-    StageTile* tl;
-    int lane;
-    __device__ __forceinline__ void i32(int f, int v) { tl->i32[f * BLOCK + lane] = v; }
-    __device__ __forceinline__ void i8(int f, int v) { tl->i8[f * BLOCK + lane] = (int8_t)v; }
-    __device__ __forceinline__ void f32(int f, float v) { tl->f32[f * BLOCK + lane] = v; }
-    __device__ __forceinline__ void mask(int f, int v) { tl->mask[f * BLOCK + lane] = (int8_t)v; }
-};
-// Copy ROWS rows of ROWBYTES from the tile to global rows spaced `gstride` bytes apart.
-template <int ROWS, int ROWBYTES>
-__device__ __forceinline__ void copy_rows(const void* tile, void* gbase, size_t gstride, int lane) {
-    constexpr int CPR = ROWBYTES / 16;
-    constexpr int TOTAL = ROWS * CPR;
-    const uint8_t* src = (const uint8_t*)tile;
-    uint8_t* dst = (uint8_t*)gbase;
-#pragma unroll
-    for (int c0 = 0; c0 < TOTAL; c0 += BLOCK) {
-        const int c = c0 + lane;
-        if (c < TOTAL) {
-            const int r = c / CPR, off = (c - r * CPR) * 16;
-            const uint4 v = *(const uint4*)(src + r * ROWBYTES + off);
-            *(uint4*)(dst + (size_t)r * gstride + off) = v;
-        }
-    }
-}
-__device__ __forceinline__ void copy_out(const StageTile& tl, const fjsp_out& out, uint32_t t, size_t n, int blk,
-                                         int lane) {
-    const size_t col = (size_t)blk * BLOCK;
-    if (out.obs_i32) copy_rows<NI32, 4 * BLOCK>(tl.i32, out.obs_i32 + (size_t)t * NI32 * n + col, n * 4, lane);
-    if (out.obs_f32) copy_rows<NF32, 4 * BLOCK>(tl.f32, out.obs_f32 + (size_t)t * NF32 * n + col, n * 4, lane);
-    if (out.rewards) copy_rows<NA, 8 * BLOCK>(tl.rew, out.rewards + (size_t)t * NA * n + col, n * 8, lane);
-    if (out.status) copy_rows<1, 4 * BLOCK>(tl.status, out.status + (size_t)t * n + col, n * 4, lane);
-    if (out.obs_i8) copy_rows<NI8, BLOCK>(tl.i8, out.obs_i8 + (size_t)t * NI8 * n + col, n, lane);
-    if (out.masks) copy_rows<NMASK, BLOCK>(tl.mask, out.masks + (size_t)t * NMASK * n + col, n, lane);
-    if (out.term) copy_rows<1, BLOCK>(tl.term, out.term + (size_t)t * n + col, n, lane);
-    if (out.trunc) copy_rows<1, BLOCK>(tl.trunc, out.trunc + (size_t)t * n + col, n, lane);
-}
-
-// Lean + LDS-staged variant of step_and_emit (obs, masks, rewards, term, trunc, status).
-__device__ __forceinline__ void step_and_emit_staged(Env& E, const Tables& T, const Cfg& C, const DevState& S, int e,
-                                                     const int* act, int autoreset, const fjsp_out& out, uint32_t t,
-                                                     StageTile* tl, int lane) {
-    uint32_t res[NA];
-    const double g8 = env_advance<true>(E, T, C, act, nullptr, res);
-#pragma unroll
-    for (int a = 0; a < NA; a++) tl->rew[a * BLOCK + lane] = g8 + local_reward(C, a, res[a], act[a]);
-    FJSP_STAMP(E, 3);
-    StageSink sink{tl, lane};
-    observe(E, C, sink);
-    FJSP_STAMP(E, 4);
-    const int nord = E.norders();
-    const int all_done = E.ncompleted() == nord && nord > 0 && E.next_order() == nord;
-    const int truncated = E.step() >= C.max_steps;
-    tl->term[lane] = (uint8_t)all_done;
-    tl->trunc[lane] = (uint8_t)truncated;
-    tl->status[lane] = E.status();
-    __syncthreads();
-    copy_out(*tl, out, t, (size_t)S.n, blockIdx.x, lane);
-    __syncthreads();
-    FJSP_STAMP(E, 5);
-    E.set_step(E.step() + 1);
-    if (autoreset && (all_done || truncated))
-        E = env_reset_cold(E, T, C, S, e, nord);   // reset(seed=None) continues the MT stream
-    FJSP_STAMP(E, 6);
-}
-
 // EPW: envs per workgroup (64, 32 or 16; lanes >= EPW idle; option "step_envs").  Fewer envs per
 // wave would shorten the union of the lanes' branches and spread 4 096 envs over all 256 CUs; it
 // measured slower (fjsp_step), so 64 stays the default.
@@ -422,11 +343,9 @@ __device__ __forceinline__ void tables_copy_in(const DevState& S, const Tables& 
 // the whole launch (one 64-lane workgroup = 64 envs, 97.5 KB of LDS), so the linked-list
 // walks and order-word read-modify-writes of the step are ds_* round trips (~100 cycles)
 // instead of L2/HBM round trips; only the used prefix is copied in and out.
-template <bool LDS, bool FULL, bool STAGED = false>
+template <bool LDS, bool FULL>
 __global__ void __launch_bounds__(BLOCK) k_step_many(DevState S, Cfg C, int K, uint64_t seed, uint32_t gid0,
                                                      uint32_t step0, int mode, int autoreset, fjsp_out out) {
-    struct NoTile { int unused; };
-    __shared__ typename std::conditional<STAGED, StageTile, NoTile>::type s_tile;
     __shared__ uint32_t s_orders[LDS ? MAX_ORDERS * BLOCK : 1];
     __shared__ uint16_t s_code[LDS ? MAX_SLOTS * BLOCK : 1];
     __shared__ uint8_t s_next[LDS ? MAX_SLOTS * BLOCK : 1];
@@ -459,10 +378,7 @@ __global__ void __launch_bounds__(BLOCK) k_step_many(DevState S, Cfg C, int K, u
         int act[NA];
         synth_actions(seed, gid0 + (uint32_t)e, step0 + (uint32_t)k, mode, E, T, C, act);
         FJSP_STAMP(E, 0);
-        if constexpr (STAGED)
-            step_and_emit_staged(E, T, C, S, e, act, autoreset, out, (uint32_t)k, &s_tile, lane);
-        else
-            step_and_emit<true, FULL>(E, T, C, S, e, act, nullptr, autoreset, out, (uint32_t)k);
+        step_and_emit<true, FULL>(E, T, C, S, e, act, nullptr, autoreset, out, (uint32_t)k);
     }
     if constexpr (LDS) {
         for (int o = 0; o < E.norders(); o++) S.orders[(size_t)o * S.n + e] = T.orders[o * BLOCK];
@@ -1200,7 +1116,8 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
 // E1+K, E2+E3 (0.6 % faster than AM+K, E1+PD; other pairings measured within noise)
 constexpr int AG_LAYOUT[8] = {0, 1, 2, 3, 6, 5, 4, 7};
 constexpr int AG_AM = AG_LAYOUT[0], AG_P = AG_LAYOUT[1], AG_E1 = AG_LAYOUT[2], AG_E2 = AG_LAYOUT[3], AG_K = AG_LAYOUT[4],
-              AG_E0 = AG_LAYOUT[5], AG_PD = AG_LAYOUT[6], AG_E3 = AG_LAYOUT[7], AG_WAVES = 8;
+              AG_E0 = AG_LAYOUT[5], AG_PD = AG_LAYOUT[6], AG_E3 = AG_LAYOUT[7];
+static_assert(AG_WAVES == 8, "one wave per role of AG_LAYOUT (AG_WAVES: fjsp_select.h)");
 // packaging-owned state words (K): W1, W13..W16 (packaging run lists), W20..W29
 constexpr uint32_t K_WORDS = (1u << 1) | (0xFu << 13) | (0x3FFu << 20);
 // masks per emit wave: pickup [0,3) | the AGV's pickup / drop [9,11) | the AGV's moves [3,9),
@@ -2014,21 +1931,14 @@ struct fjsp_handle {
     int timed;
     double* lut_dev;
     double lut_host[RLUT_SIZE];
-    int use_lds;     // fused kernel variant (fjsp_set_option "fused_lds")
-    int use_staged;  // LDS-staged wide output stores (fjsp_set_option "staged_stores")
+    StepOpts opts;   // kernel-variant knobs (fjsp_set_option; fjsp_select.h)
     int timing;      // hipEvent bracketing of step launches (off while graph-capturing)
-    int use_pipe;    // two-wave pipelined k_step_many for lean outputs (fjsp_set_option "pipeline")
-    int use_pg;      // pre-draw wave in the pipelined kernel (fjsp_set_option "predraw")
-    int use_ag;      // agent-group pipeline k_step_ag for uniform-random actions (fjsp_set_option "agents")
-    int ag_epw;      // k_step_ag envs per workgroup: 64 / 32 / 16, 0 = auto (fjsp_set_option "ag_envs")
-    int step_epw;    // k_step envs per workgroup: 64 / 32 / 16, 0 = 64 (fjsp_set_option "step_envs")
     const char* last_kernel;   // name of the last step kernel launched (fjsp_last_kernel)
     uint32_t env_id_base;      // global id of env 0 (fjsp_set_option "env_id_base")
     // fjsp_a2c_policy_step's tile hand-off: [ntiles] arrival counters (zero between launches),
     // then [ntiles][8][16] action words; outside the state block (not part of a snapshot)
     uint32_t* tiles;
     int ntiles;
-    int test_stall;   // option "test_stall" (tests): launch the STALL builds of the multi-wave kernels
     // step server (fjsp_server_*): the persistent k_step_server, its control block in host memory
     ServerCtl* srv;
     uint32_t* srv_relay;      // device words: workgroup 0 relays each request / stop to the others
@@ -2079,6 +1989,15 @@ struct DeviceGuard {
         if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
     }
 };
+
+// f(std::integral_constant<int, EPW>) for the envs-per-workgroup template argument of k_step and
+// k_step_ag (16, 32 or 64: what fjsp_set_option admits and fjsp_select.h chooses)
+template <class F>
+static void with_epw(int epw, F&& f) {
+    if (epw == 16) f(std::integral_constant<int, 16>{});
+    else if (epw == 32) f(std::integral_constant<int, 32>{});
+    else f(std::integral_constant<int, 64>{});
+}
 
 extern "C" {
 
@@ -2169,16 +2088,13 @@ int fjsp_create(const fjsp_config* cfg, int32_t num_envs, int32_t device, void* 
     h->device = device;
     h->stream = (hipStream_t)hip_stream;
     // kernel-variant defaults (fjsp_set_option changes them per handle; every variant is
-    // byte-identical): LDS tables auto (every workgroup a CU), direct stores, the pipelined /
-    // pre-draw / agent-group kernels on, k_step_ag's envs per workgroup auto, per-launch events on
-    h->use_lds = -1;
-    h->use_staged = 0;
+    // byte-identical): LDS tables auto (every workgroup a CU), the pipelined / pre-draw /
+    // agent-group kernels on, k_step_ag's envs per workgroup auto, per-launch events on
+    h->opts.fused_lds = -1;
+    h->opts.pipeline = 1;
+    h->opts.predraw = 1;
+    h->opts.agents = 1;
     h->timing = 1;
-    h->use_pipe = 1;
-    h->use_pg = 1;
-    h->use_ag = 1;
-    h->ag_epw = 0;
-    h->step_epw = 0;
     h->dcfg.step_size = c.step_size;
     h->dcfg.max_steps = c.max_episode_steps;
     h->dcfg.tray_cap = c.tray_capacity;
@@ -2274,19 +2190,18 @@ int fjsp_set_option(fjsp_handle* h, const char* name, int64_t value) {
     if (!strncmp(name, "policy_", 7) || !strcmp(name, "wgrad_waves")) return fjsp_internal_policy_option(name, value);
     if (!h) return fail("null handle (only the policy_* and wgrad_waves options are library-wide)");
     SERVER_QUIESCE(h);
-    if (!strcmp(name, "fused_lds")) { h->use_lds = value < 0 ? -1 : value != 0; return 0; }
-    if (!strcmp(name, "staged_stores")) { h->use_staged = value != 0; return 0; }
-    if (!strcmp(name, "pipeline")) { h->use_pipe = value != 0; return 0; }
-    if (!strcmp(name, "predraw")) { h->use_pg = value != 0; return 0; }
-    if (!strcmp(name, "agents")) { h->use_ag = value != 0; return 0; }
+    if (!strcmp(name, "fused_lds")) { h->opts.fused_lds = value < 0 ? -1 : value != 0; return 0; }
+    if (!strcmp(name, "pipeline")) { h->opts.pipeline = value != 0; return 0; }
+    if (!strcmp(name, "predraw")) { h->opts.predraw = value != 0; return 0; }
+    if (!strcmp(name, "agents")) { h->opts.agents = value != 0; return 0; }
     if (!strcmp(name, "step_envs")) {
         if (value != 0 && value != 16 && value != 32 && value != 64) return fail("step_envs must be 0, 16, 32 or 64");
-        h->step_epw = (int)value;
+        h->opts.step_envs = (int)value;
         return 0;
     }
     if (!strcmp(name, "ag_envs")) {
         if (value != 0 && value != 16 && value != 32 && value != 64) return fail("ag_envs must be 0, 16, 32 or 64");
-        h->ag_epw = (int)value;
+        h->opts.ag_envs = (int)value;
         return 0;
     }
     if (!strcmp(name, "timing")) { h->timing = value != 0; if (!h->timing) h->timed = 0; return 0; }
@@ -2304,7 +2219,7 @@ int fjsp_set_option(fjsp_handle* h, const char* name, int64_t value) {
         const uint32_t v = (uint32_t)value;
         HIPCHK(hipStreamSynchronize(h->stream));
         HIPCHK(hipMemcpy(h->S.words + (size_t)NWORDS * h->n + AUX_TEST_STALL, &v, 4, hipMemcpyHostToDevice));
-        h->test_stall = value != 0;
+        h->opts.test_stall = value != 0;
         return 0;
     }
     if (!strcmp(name, "env_id_base")) {
@@ -2361,33 +2276,17 @@ int fjsp_step(fjsp_handle* h, const uint8_t* actions, const uint8_t* agent_order
         }
     }
     DeviceGuard g(h->device);
-    // 64 envs per workgroup unless the option says otherwise: at 4 096 envs 16- / 32-env
-    // workgroups (all 256 CUs busy) measured slower, 8.58 / 8.32 against 7.61 us per launch
-    // (profiles/r06/kstep/ab_step_envs_4096.json): the step is not bound by its lanes' branch union
-    const int epw = h->step_epw ? h->step_epw : 64;
-    const dim3 grid((h->n + epw - 1) / epw);
+    const KStepPlan p = select_step(h->n, canon, h->opts);
     const fjsp_out o = out ? *out : kNoOut;
     if (h->timing) HIPCHK(hipEventRecord(h->ev0, h->stream));
-#define FJSP_LAUNCH_STEP(CN)                                                                                      \
-    do {                                                                                                           \
-        if (epw == 16)                                                                                             \
-            hipLaunchKernelGGL((k_step<CN, 16>), grid, dim3(BLOCK), 0, h->stream, h->S, h->dcfg, actions, packed, \
-                               autoreset, o);                                                                      \
-        else if (epw == 32)                                                                                        \
-            hipLaunchKernelGGL((k_step<CN, 32>), grid, dim3(BLOCK), 0, h->stream, h->S, h->dcfg, actions, packed, \
-                               autoreset, o);                                                                      \
-        else                                                                                                       \
-            hipLaunchKernelGGL((k_step<CN, 64>), grid, dim3(BLOCK), 0, h->stream, h->S, h->dcfg, actions, packed, \
-                               autoreset, o);                                                                      \
-    } while (0)
-    if (canon) {
-        h->last_kernel = "k_step<canon>";
-        FJSP_LAUNCH_STEP(true);
-    } else {
-        h->last_kernel = "k_step<ordered>";
-        FJSP_LAUNCH_STEP(false);
-    }
-#undef FJSP_LAUNCH_STEP
+    h->last_kernel = p.name;
+    with_epw(p.epw, [&](auto epw) {
+        constexpr int EPW = decltype(epw)::value;
+        auto launch = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(p.grid), dim3(BLOCK), 0, h->stream, h->S, h->dcfg, actions, packed, autoreset, o);
+        };
+        p.canon ? launch(k_step<true, EPW>) : launch(k_step<false, EPW>);
+    });
     HIPCHK(hipGetLastError());
     if (h->timing) {
         HIPCHK(hipEventRecord(h->ev1, h->stream));
@@ -2553,77 +2452,37 @@ int fjsp_step_many(fjsp_handle* h, int32_t K, uint64_t action_seed, uint32_t env
     const uint64_t row_bytes = o.feats ? 4ull * NFEAT : 64ull;
     if ((uint64_t)K * (uint64_t)h->n * row_bytes >= (1ull << 32)) return fail("K * num_envs too large for one launch");
     DeviceGuard g(h->device);
-    dim3 grid((h->n + BLOCK - 1) / BLOCK);
     if (h->timing) HIPCHK(hipEventRecord(h->ev0, h->stream));
     const bool full = o.results || o.orders_completed || o.packaged || o.sim_time || o.next_i32 || o.next_i8 ||
                       o.next_f32 || o.next_masks || o.feats;
+    const StepPlan p = select_step_many(h->n, K, action_mode, autoreset, full, h->opts);
+    h->last_kernel = p.kernel.name;
+    const dim3 grid(p.grid), block(p.waves * BLOCK);
     auto launch = [&](auto kern) {
-        hipLaunchKernelGGL(kern, grid, dim3(BLOCK), 0, h->stream, h->S, h->dcfg, K, action_seed, env_gid0, step0,
-                           action_mode, autoreset, o);
+        hipLaunchKernelGGL(kern, grid, block, 0, h->stream, h->S, h->dcfg, K, action_seed, env_gid0, step0, action_mode,
+                           autoreset, o);
     };
-    // staged stores need whole 64-env blocks and 16-byte aligned output rows
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
-    const bool staged = h->use_staged && !full && h->n % BLOCK == 0 && al16(o.obs_i32) && al16(o.obs_i8) &&
-                        al16(o.obs_f32) && al16(o.masks) && al16(o.rewards) && al16(o.term) && al16(o.trunc) &&
-                        al16(o.status);
-    // LDS tables (97.5 KB per 64-env workgroup) pay while every workgroup has a CU of its own
-    const bool lds = h->use_lds < 0 ? h->n <= 256 * BLOCK : h->use_lds != 0;
-    const bool two_emit = h->n <= 256 * BLOCK;
-    // the pre-draw wave pays while the CUs have a free SIMD (and only with auto-reset)
-    const bool pg = h->use_pg && lds && two_emit && autoreset;
-    // the agent-group pipeline: state-independent (uniform-random) actions, LDS tables, pre-draw;
-    // also for 16 384 < N <= 32 768, where its 64-env workgroups run in two rounds and still beat
-    // k_step_pipe<1emit> (24 576 envs 3.17 against 3.75, 32 768 3.20-3.59 against 3.87 ms per
-    // 1 024-step launch; 49 152: 4.85 against 4.37-4.72; profiles/r04/ag_two_rounds_ab.json)
-    const bool ag_wide = h->n > 256 * BLOCK && h->n <= 512 * BLOCK && h->use_lds != 0 && h->use_pg && autoreset;
-    const bool ag = h->use_ag && h->use_pipe && !full && !staged && (pg || ag_wide) &&
-                    action_mode == FJSP_ACTIONS_UNMASKED;
-    h->last_kernel = ag ? "k_step_ag<lds,predraw>"
-                   : (h->use_pipe && !full && !staged)
-                         ? (lds ? (two_emit ? (pg ? "k_step_pipe<lds,2emit,predraw>" : "k_step_pipe<lds,2emit>")
-                                            : "k_step_pipe<lds,1emit>")
-                                : (two_emit ? "k_step_pipe<2emit>" : "k_step_pipe<1emit>"))
-                   : full ? (lds ? "k_step_many<lds,full>" : "k_step_many<full>")
-                   : staged ? (lds ? "k_step_many<lds,staged>" : "k_step_many<staged>")
-                   : (lds ? "k_step_many<lds>" : "k_step_many");
-    if (ag) {
-        // envs per workgroup: auto = the fewest that still give every workgroup a CU of its own
-        // for long launches (1.30 -> 1.22 us per step at 4 096 envs); 64 for launches of fewer
-        // than 64 steps, whose time is mostly the per-workgroup fixed cost (K = 20: 36.6 against
-        // 39.9 us in rocprof)
-        int epw = h->ag_epw;
-        if (epw == 0) epw = K < 64 ? 64 : h->n <= 256 * 16 ? 16 : h->n <= 256 * 32 ? 32 : 64;
-        const dim3 agrid((h->n + epw - 1) / epw);
-        auto launch_ag = [&](auto kern) {
-            hipLaunchKernelGGL(kern, agrid, dim3(AG_WAVES * BLOCK), 0, h->stream, h->S, h->dcfg, K, action_seed,
-                               env_gid0, step0, autoreset, o);
-        };
-        if (h->test_stall) {
-            if (epw == 16) launch_ag(k_step_ag<16, true>);
-            else if (epw == 32) launch_ag(k_step_ag<32, true>);
-            else launch_ag(k_step_ag<64, true>);
-        } else if (epw == 16) launch_ag(k_step_ag<16>);
-        else if (epw == 32) launch_ag(k_step_ag<32>);
-        else launch_ag(k_step_ag<64>);
-    } else if (h->use_pipe && !full && !staged) {
-        // a second emit wave pays while the CUs are not full (N <= 16384 at 64 envs per CU)
-        const bool two = two_emit;
-        auto launch_pipe = [&](auto kern, int waves) {
-            hipLaunchKernelGGL(kern, grid, dim3(waves * BLOCK), 0, h->stream, h->S, h->dcfg, K, action_seed, env_gid0,
-                               step0, action_mode, autoreset, o);
-        };
-        if (lds && two && pg && h->test_stall) launch_pipe(k_step_pipe<true, 2, true, true>, 4);
-        else if (lds && two && pg) launch_pipe(k_step_pipe<true, 2, true>, 4);
-        else if (lds) two ? launch_pipe(k_step_pipe<true, 2>, 3) : launch_pipe(k_step_pipe<true, 1>, 2);
-        else two ? launch_pipe(k_step_pipe<false, 2>, 3) : launch_pipe(k_step_pipe<false, 1>, 2);
-    } else if (lds) {
-        if (full) launch(k_step_many<true, true>);
-        else if (staged) launch(k_step_many<true, false, true>);
-        else launch(k_step_many<true, false>);
-    } else {
-        if (full) launch(k_step_many<false, true>);
-        else if (staged) launch(k_step_many<false, false, true>);
-        else launch(k_step_many<false, false>);
+    auto launch_ag = [&](auto kern) {   // uniform-random actions only: no action_mode
+        hipLaunchKernelGGL(kern, grid, block, 0, h->stream, h->S, h->dcfg, K, action_seed, env_gid0, step0, autoreset, o);
+    };
+    switch (p.variant) {
+    case SV_MANY: launch(k_step_many<false, false>); break;
+    case SV_MANY_LDS: launch(k_step_many<true, false>); break;
+    case SV_MANY_FULL: launch(k_step_many<false, true>); break;
+    case SV_MANY_LDS_FULL: launch(k_step_many<true, true>); break;
+    case SV_PIPE_1EMIT: launch(k_step_pipe<false, 1>); break;
+    case SV_PIPE_2EMIT: launch(k_step_pipe<false, 2>); break;
+    case SV_PIPE_LDS_1EMIT: launch(k_step_pipe<true, 1>); break;
+    case SV_PIPE_LDS_2EMIT: launch(k_step_pipe<true, 2>); break;
+    case SV_PIPE_LDS_2EMIT_PREDRAW:
+        p.stall ? launch(k_step_pipe<true, 2, true, true>) : launch(k_step_pipe<true, 2, true>);
+        break;
+    case SV_AG:
+        with_epw(p.epw, [&](auto epw) {
+            constexpr int EPW = decltype(epw)::value;
+            p.stall ? launch_ag(k_step_ag<EPW, true>) : launch_ag(k_step_ag<EPW>);
+        });
+        break;
     }
     HIPCHK(hipGetLastError());
     if (h->timing) {

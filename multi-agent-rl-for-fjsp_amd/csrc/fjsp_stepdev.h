@@ -12,7 +12,6 @@
 
 namespace fjsp {
 
-constexpr int BLOCK = 64;
 constexpr int MT_N = 624;
 
 struct DevState {
