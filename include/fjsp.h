@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FJSP_ABI_VERSION 13
+#define FJSP_ABI_VERSION 14
 
 #define FJSP_NUM_AGENTS 8      /* pickup, agv, small, big, pkg_blue_1, pkg_blue_2, pkg_red, pkg_green */
 #define FJSP_OBS_I32 20        /* pickup 7 + agv 13 (position = 2) int32 observation fields */
@@ -387,14 +387,6 @@ int fjsp_a2c_policy_step(fjsp_handle* h, const float* feats, const int8_t* masks
                          const float* critic_w, const uint64_t* seed, uint32_t env_gid0, uint32_t step,
                          int32_t deterministic, uint8_t* actions, float* values, int32_t autoreset,
                          const fjsp_out* out, int32_t env_begin, int32_t env_count, void* hip_stream);
-/* The critic's forward over n samples for the A2C update (a2c.py:692-699 critic(global_states)
- * over the batch; a2c_vec._CriticGrouped): x f32 [n][40] (ABI 8: sample-major rows, 38
- * features + 2 ignored words, the layout of fjsp_a2c_group_keys' rows; ABI 7 took [38][n]
- * feature rows), critic_w packed as for fjsp_a2c_policy -> values f32 [n] and the post-ReLU hidden
- * layers the backward reads, h1 / h2 f32 [n][256], h3 f32 [n][128] (sample-major).  Same
- * arithmetic as fjsp_a2c_policy's values.  Stream-ordered. */
-int fjsp_a2c_critic_forward(const float* x, int32_t n, const float* critic_w, float* h1, float* h2, float* h3,
-                            float* values, void* stream);
 /* The shard learner's combiner keys (multi-agent-rl-for-fjsp_amd/shard_learner.py, exchange="shard";
  * a2c.py:647-731 with the learner sharded by network; ABI 9): per (agent a, sample s = t n + e)
  * info [8][S] i32 = the agent's action-mask bits | action << 8 and the record key tk [8][S] =
@@ -428,12 +420,16 @@ int fjsp_a2c_record_head(const float* pu, int32_t umax, const int64_t* inv, int3
                          const double* wsum, const int32_t* cnt, float inv_count, float ent_coef, float* grad,
                          double* sums, void* stream);
 /* The grouped update's critic loss and its backward in one pass over n distinct global states
- * (a2c.py:683-699 critic(global_states), 713-722 calc_critic_loss; ABI 9): x f32 [n][40] as for
- * fjsp_a2c_critic_forward, coef f64 [n][3] = (a, b, c) with state u's share of the loss
- * a/2 V^2 + b V + c (a = 2 n_u / count, b = -2 sum R / (8 count), c = sum R^2 / (8 count)), so
- * dL / dV = a V + b; critic_w, w3t, w2t packed as for fjsp_a2c_policy / fjsp_a2c_critic_backward.
+ * (a2c.py:683-699 critic(global_states), 713-722 calc_critic_loss; ABI 9): x f32 [n][40] =
+ * sample-major rows, 38 features + 2 ignored words (the layout of fjsp_a2c_group_keys' rows);
+ * coef f64 [n][3] = (a, b, c) with state u's share of the loss a/2 V^2 + b V + c (a = 2 n_u /
+ * count, b = -2 sum R / (8 count), c = sum R^2 / (8 count)), so dL / dV = a V + b; critic_w the
+ * FJSP_POLICY_CRITIC_FLOATS buffer of fjsp_a2c_policy (P(W1 [256][48]) | b1 | P(W2) | b2 | P(W3) |
+ * b3 | W4 | b4 [16]); w3t = P(W3^T [256][128]), 3 * 256 * 128 / 2 floats, and w2t = P(W2^T
+ * [256][256]), 3 * 256 * 256 / 2 floats, the same three-bf16-plane MFMA order P (fjsp_a2c_pack_mfma
+ * with transposed = 1).  Same forward arithmetic as fjsp_a2c_policy's values.
  * Writes h1 / h2 f32 [n][256] (post-ReLU), g3 [n][128], g2 / g1 [n][256] (the pre-activation
- * gradients: the split-K weight gradients' operands), per 32-state tile part f32 [tiles][772] =
+ * gradients: fjsp_a2c_wgrad's operands), per 32-state tile part f32 [tiles][772] =
  * layer 1 | 2 | 3 bias gradients (256 | 256 | 128), w4's gradient (128), b4's gradient, 3 zeros,
  * loss f64 [tiles] (partial sums), values f32 [n] (may be NULL).  x, h1, h2, g3, g2, g1, part
  * 16-byte aligned.  Stream-ordered. */
@@ -451,14 +447,6 @@ int fjsp_a2c_critic_fused(const float* x, int32_t n, const float* critic_w, cons
  * deterministic.  g, x 16-byte aligned.  Stream-ordered. */
 int fjsp_a2c_wgrad(const float* g, int32_t m, int64_t ldg, const float* x, int32_t nx, int64_t ldx, int64_t U,
                    float* part, int32_t P, float* out, int32_t nout, int64_t ldo, void* stream);
-/* The critic's backward through its two 256-wide ReLU layers for the A2C update (a2c.py:692-699
- * critic_loss.backward(); a2c_vec._CriticGrouped): g3 f32 [n][128] (layer 3's pre-activation
- * gradient, fjsp_a2c_value_head_grad), h1 / h2 from fjsp_a2c_critic_forward, w3t / w2t = W3^T
- * [256][128] / W2^T [256][256] packed as the forward's weights -> g2 = (g3 W3) * [h2 > 0], g1 =
- * (g2 W2) * [h1 > 0] f32 [n][256] and their column sums per 32-sample tile, bias_part2 /
- * bias_part1 f32 [ceil(n / 32)][256].  Stream-ordered. */
-int fjsp_a2c_critic_backward(const float* g3, const float* h1, const float* h2, int32_t n, const float* w3t,
-                             const float* w2t, float* g2, float* g1, float* bias_part2, float* bias_part1, void* stream);
 /* Grouping keys of the A2C update (a2c.py:647-703 _update over a batch; a2c_vec.A2CLosses
  * dedup): feats f32 [T][38][n] (the rollout's a2c features) -> keys u64 [9][T * n], row a < 8
  * a hash of actor a's padded input (its a2c.py:118-134 observation block, zero-padded to 13

@@ -98,22 +98,10 @@ class _LinearSplitK(torch.autograd.Function):
         return gx, gW, gy.sum(0) if gb is None else gb, None
 
 
-def _critic_wgrad(gy, x, nx=None):
-    """A critic layer's weight gradient gy^T x[:, :nx]: on the GPU one fjsp_a2c_wgrad launch (the
-    samples' contraction on the matrix cores, f32-level products, deterministic; r06), else the
-    split-K GEMM."""
-    if gy.is_cuda and wgrad_kernel_on:
-        return critic_wgrad(gy, x, nx)
-    return _splitk_wgrad(gy, x if nx is None else x[:, :nx])
-
-
-wgrad_kernel_on = True   # False: the critic's weight gradients as split-K hipBLASLt GEMMs (A/B)
-
-
 def _wgrad_fits(gy, x):
     """fjsp_a2c_wgrad takes this gy^T x (contiguous rows, a supported layer shape): the critic's
     layers and the long-batch actor's 256-wide hidden layer (_LinearSplitK)."""
-    if not (gy.is_cuda and wgrad_kernel_on and gy.dim() == 2 and x.dim() == 2 and gy.is_contiguous()
+    if not (gy.is_cuda and gy.dim() == 2 and x.dim() == 2 and gy.is_contiguous()
             and x.is_contiguous() and x.shape[1] % 4 == 0):
         return False
     m, nx = gy.shape[1], x.shape[1]
@@ -204,66 +192,11 @@ def _relu_bias_grad(gy, y):
     return g, part.sum(0)
 
 
-class _CriticGrouped(torch.autograd.Function):
-    """The critic (38 -> 256 -> 256 -> 128 -> 1, ReLUs) over a long batch of distinct global states
-    on the GPU: the forward in one fused kernel (fjsp_a2c_critic_forward: f32 operands as bf16
-    planes on the matrix cores, as the policy kernel's values), which also writes the hidden
-    layers; the backward: the value-head kernel, both 256-wide ReLU layers' input gradients in one
-    kernel (fjsp_a2c_critic_backward, the same split arithmetic), split-K weight gradients
-    (hipBLASLt; a matrix-core kernel for them measured slower).
-    x f32 [U, 40] (sample-major rows: 38 features, 2 zeros) -> v [U]."""
-
-    @staticmethod
-    def forward(ctx, x, W1, b1, W2, b2, W3, b3, W4, b4):
-        U = x.shape[0]
-        dev = x.device
-        cw = pack_critic_weights(W1, b1, W2, b2, W3, b3, W4, b4)
-        h1 = torch.empty(U, W2.shape[1], dtype=torch.float32, device=dev)
-        h2 = torch.empty(U, W2.shape[0], dtype=torch.float32, device=dev)
-        h3 = torch.empty(U, W3.shape[0], dtype=torch.float32, device=dev)
-        v = torch.empty(U, dtype=torch.float32, device=dev)
-        V = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        nat.check(nat.lib().fjsp_a2c_critic_forward(V(x), U, V(cw), V(h1), V(h2), V(h3), V(v), ctypes.c_void_p(stream)))
-        ctx.save_for_backward(x, W2, W3, W4, h1, h2, h3)
-        return v
-
-    @staticmethod
-    def backward(ctx, gv):
-        x, W2, W3, W4, h1, h2, h3 = ctx.saved_tensors
-        B, C = h3.shape
-        gvc = gv.reshape(-1).contiguous()
-        w4 = W4.reshape(-1).contiguous()
-        g3 = torch.empty_like(h3)
-        part = torch.empty(-(-B // 128), 2 * C + 4, dtype=torch.float32, device=h3.device)
-        stream = torch.cuda.current_stream(h3.device).cuda_stream
-        V = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        nat.check(nat.lib().fjsp_a2c_value_head_grad(V(h3), V(gvc), V(w4), B, V(g3), V(part), ctypes.c_void_p(stream)))
-        ps = part.sum(0)
-        gW3 = _splitk_wgrad(g3, h2)
-        if critic_bwd_fused:
-            # both 256-wide ReLU layers' input gradients in one pass (fjsp_a2c_critic_backward)
-            w3t, w2t = pack_mfma(W3.detach().t()).reshape(-1), pack_mfma(W2.detach().t()).reshape(-1)
-            g2, g1 = torch.empty_like(h2), torch.empty_like(h1)
-            nt = -(-B // 32)
-            bp2 = torch.empty(nt, h2.shape[1], dtype=torch.float32, device=h2.device)
-            bp1 = torch.empty(nt, h1.shape[1], dtype=torch.float32, device=h1.device)
-            nat.check(nat.lib().fjsp_a2c_critic_backward(V(g3), V(h1), V(h2), B, V(w3t), V(w2t), V(g2), V(g1), V(bp2),
-                                                         V(bp1), ctypes.c_void_p(stream)))
-            gb2, gb1 = bp2.sum(0), bp1.sum(0)
-        else:
-            g2, gb2 = _relu_bias_grad((g3 @ W3).contiguous(), h2)
-            g1, gb1 = _relu_bias_grad((g2 @ W2).contiguous(), h1)
-        gW2 = _splitk_wgrad(g2, h1)
-        gW1 = _splitk_wgrad(g1, x[:, :GLOBAL_DIM])
-        return (None, gW1, gb1, gW2, gb2, gW3, ps[:C], ps[C:2 * C].view(1, C), ps[2 * C:2 * C + 1])
-
-
 class _CriticOnePass(torch.autograd.Function):
     """The grouped update's critic loss and its gradients in one kernel pass over the distinct
     global states (fjsp_a2c_critic_fused: forward, value gradient from the per-state loss
     coefficients, value head and the two 256-wide layers' backward; a2c.py:683-699, 713-722); the
-    three split-K weight gradients in backward (a loss-only call pays for none of them).  x f32
+    three weight gradients (fjsp_a2c_wgrad) in backward (a loss-only call pays for none).  x f32
     [U, 40] (sample-major rows), coef f64 [U, 3] = (a, b, c) with state u's loss a/2 V^2 + b V + c
     (critic_coef) -> the critic loss (0-d f32); backward returns the gradients, scaled by the
     loss's gradient."""
@@ -282,9 +215,10 @@ class _CriticOnePass(torch.autograd.Function):
 
 @torch.no_grad()
 def critic_onepass_grads(x, h1, h2, g1, g2, g3, ps):
-    """The critic's gradients W1, b1, W2, b2, W3, b3, W4, b4 from fjsp_a2c_critic_fused's outputs."""
-    return (_critic_wgrad(g1, x, GLOBAL_DIM), ps[:256], _critic_wgrad(g2, h1), ps[256:512],
-            _critic_wgrad(g3, h2), ps[512:640], ps[640:768].view(1, 128), ps[768:769])
+    """The critic's gradients W1, b1, W2, b2, W3, b3, W4, b4 from fjsp_a2c_critic_fused's outputs
+    (GPU only, as the kernel): the weight gradients one fjsp_a2c_wgrad launch each."""
+    return (critic_wgrad(g1, x, GLOBAL_DIM), ps[:256], critic_wgrad(g2, h1), ps[256:512],
+            critic_wgrad(g3, h2), ps[512:640], ps[640:768].view(1, 128), ps[768:769])
 
 
 @torch.no_grad()
@@ -358,33 +292,12 @@ def critic_onepass(critic, x, coef):
                                 n[4].bias, n[6].weight, n[6].bias)
 
 
-# Implementation switches of the grouped update (module attributes, set from Python by the A/B
-# scripts and the tests; every setting computes the same losses and gradients):
-# the critic through the fused forward kernel (False: PyTorch GEMMs)
-critic_fused = True
-# ... and its loss, forward and backward in one pass per distinct state (fjsp_a2c_critic_fused;
-# False: the forward kernel, the per-sample loss through autograd, the value head and backward kernels)
-critic_onepass_on = True
-
-# its backward through the two 256-wide layers in one kernel (False: GEMMs + ReLU kernels)
-critic_bwd_fused = True
-
-
 def feature_rows(f3):
     """feats f32 [T, 38, N] -> the sample-major rows f32 [T*N, 40] (zero-padded) that
     group_keys writes on the GPU (for callers without them)."""
     T, _, N = f3.shape
     return torch.nn.functional.pad(f3.permute(0, 2, 1).reshape(T * N, GLOBAL_DIM),
                                    (0, GROUP_ROW - GLOBAL_DIM)).contiguous()
-
-
-def critic_grouped(critic, x):
-    """v [U] of the critic over the rows of x f32 [U, 40] (distinct global states, sample-major,
-    38 features + 2 zeros: feature_rows / group_keys' rows)."""
-    n = critic.net
-    assert x.shape[1] == GROUP_ROW
-    return _CriticGrouped.apply(x.contiguous(), n[0].weight, n[0].bias, n[2].weight, n[2].bias, n[4].weight,
-                                n[4].bias, n[6].weight, n[6].bias)
 
 
 def mlp_forward(seq, x):
@@ -479,14 +392,6 @@ class ActorStack(nn.Module):
         pr = torch.nn.functional.pad(pr, (0, umax - u2))
         pb = torch.nn.functional.pad(pb, (0, umax - ub))[None]
         return torch.cat([pr[:big], pb, pr[big:]])
-
-    def forward_grouped(self, x, keys=None):
-        """forward on x [8, 13, S], each actor run once per distinct observation of its agent,
-        the probabilities gathered back per sample (A2CLosses dedup); keys [8, S] = row_keys(x)."""
-        g = RowGroups(row_keys(x) if keys is None else keys)
-        if not bool((torch.gather(x, 2, g.rep[:, None, :].expand_as(x)) == x).all()):
-            return self(x)
-        return g.gather(self.forward_rows(x, g))
 
     @torch.no_grad()
     def load_actor_nets(self, nets):
@@ -1041,18 +946,13 @@ class A2CLosses:
         # the critic first: its GEMMs keep the GPU busy while the host issues the actors' many
         # small launches (after the grouping's host synchronisations the queue is empty)
         critic_loss = None
-        if gc is not None and feats.is_cuda and critic_fused and critic_onepass_on and gc.gsorted is not None:
+        if gc is not None and feats.is_cuda and gc.gsorted is not None:
             critic_loss = critic_onepass(critic, rows.index_select(0, gc.first[0]), critic_coef(gc, r3, count))
             v = None
-        elif gc is not None and feats.is_cuda and gc.first.shape[1] >= 65536 and critic_fused:
-            vu = critic_grouped(critic, rows.index_select(0, gc.first[0])).reshape(1, 1, -1)
-            v = gc.gather(vu).reshape(-1)                            # [S]
-        elif gc is not None and feats.is_cuda:
-            vu = mlp_forward(critic.net, rows.index_select(0, gc.first[0])[:, :GLOBAL_DIM]).reshape(1, 1, -1)
-            v = gc.gather(vu).reshape(-1)                            # [S]
         elif gc is not None:
-            vu = mlp_forward(critic.net, gt[:, gc.first[0]].t()).reshape(1, 1, -1)
-            v = gc.gather(vu).reshape(-1)                            # [S]
+            # the CPU, or a GPU batch of >= 2^31 key elements (RowGroups' torch grouping)
+            xu = rows.index_select(0, gc.first[0])[:, :GLOBAL_DIM] if feats.is_cuda else gt[:, gc.first[0]].t()
+            v = gc.gather(mlp_forward(critic.net, xu).reshape(1, 1, -1)).reshape(-1)   # [S]
         else:
             v = mlp_forward(critic.net, gt.t()).reshape(-1)
         norm = count > 1
@@ -1109,7 +1009,7 @@ def pack_mfma(W):
     fjsp_a2c_pack_mfma (bit-equal to the torch formulation below); W may be a transposed view of
     a contiguous [..., K, R] tensor."""
     *lead, R, K = W.shape
-    if W.is_cuda and W.dtype == torch.float32 and R % 32 == 0 and K % 16 == 0 and pack_kernel_on:
+    if W.is_cuda and W.dtype == torch.float32 and R % 32 == 0 and K % 16 == 0:
         B = 1
         for d in lead:
             B *= d
@@ -1128,9 +1028,6 @@ def pack_mfma(W):
     return pack_mfma_torch(W)
 
 
-pack_kernel_on = True   # False: the weight packing in torch ops (A/B)
-
-
 def pack_mfma_torch(W):
     """pack_mfma in torch ops (CPU, and the GPU test's reference)."""
     *lead, R, K = W.shape
@@ -1144,7 +1041,7 @@ def pack_mfma_torch(W):
 @torch.no_grad()
 def pack_critic_weights(W1, b1, W2, b2, W3, b3, W4, b4):
     """The critic's layers (networks.CentralizedCriticNetwork: 38 -> 256 -> 256 -> 128 -> 1) -> the
-    flat buffer fjsp_a2c_policy / fjsp_a2c_critic_forward read (include/fjsp.h)."""
+    flat buffer fjsp_a2c_policy / fjsp_a2c_critic_fused read (include/fjsp.h)."""
     z = W1.new_zeros
     w1 = torch.cat([W1, z(W1.shape[0], nat.POLICY_CRITIC_DPAD - W1.shape[1])], dim=1)   # [256, 48]
     return torch.cat([pack_mfma(w1).reshape(-1), b1.reshape(-1), pack_mfma(W2).reshape(-1), b2.reshape(-1),

@@ -367,37 +367,45 @@ __device__ __forceinline__ void actor_block(const PolicyArgs& A, int j, int& rol
     }
 }
 
-// The critic on a tile of 32 envs: layers 1 and 2 one 32-row tile per wave, layer 3 (128 rows)
-// on waves 0..3, the value head from layer 3's accumulators.  SAVE (the A2C update's forward,
-// fjsp_a2c_critic_forward): the post-ReLU hidden layers also go to HBM, h1 / h2 [n][256] and
-// h3 [n][128] f32, sample-major (what the backward reads).
-struct CriticSave {
-    float* h1;
-    float* h2;
-    float* h3;
+// The packed critic buffer (fjsp_a2c_policy's critic_w, include/fjsp.h) as its layers' operands.
+struct CriticW {
+    const bf16x8* W1;   // P(W1 zero-padded to [256][48])
+    const float* B1;    // [256]
+    const bf16x8* W2;   // P(W2 [256][256])
+    const float* B2;    // [256]
+    const bf16x8* W3;   // P(W3 [128][256]): [4 row tiles][16][NP][64][8]
+    const float* B3;    // [128]
+    const float* W4;    // [128]
+    const float* B4;    // [1]
 };
-template <bool SAVE, bool ROWS = false>
+__device__ __forceinline__ CriticW critic_weights(const float* wb) {
+    CriticW w;
+    w.W1 = reinterpret_cast<const bf16x8*>(wb);
+    w.B1 = wb + NP * HID * C_DPAD / 2;
+    w.W2 = reinterpret_cast<const bf16x8*>(w.B1 + HID);
+    w.B2 = w.B1 + HID + NP * HID * HID / 2;
+    w.W3 = reinterpret_cast<const bf16x8*>(w.B2 + HID);
+    w.B3 = w.B2 + HID + NP * 128 * HID / 2;
+    w.W4 = w.B3 + 128;
+    w.B4 = w.W4 + 128;
+    return w;
+}
+
+// The critic on a tile of 32 envs: layers 1 and 2 one 32-row tile per wave, layer 3 (128 rows)
+// on waves 0..3, the value head from layer 3's accumulators.
 __device__ __forceinline__ void critic_tile(const PolicyArgs& A, int tile, unsigned char* s_mem, int tid, int lane,
-                                            int wave, const CriticSave& sv) {
+                                            int wave) {
     __bf16* s_x = reinterpret_cast<__bf16*>(s_mem);              // inputs [NP][TC][XSC]
     __bf16* s_h = reinterpret_cast<__bf16*>(s_mem + X_BYTES);    // h1, then h2 [NP][TC][HSC]
     float* s_part = reinterpret_cast<float*>(s_mem);             // value partials [4][TC] (after layer 1)
     const int n = A.n, e0 = tile * TC;
-    const float* wb = A.critic_w;
-    const bf16x8* W1 = reinterpret_cast<const bf16x8*>(wb);
-    const float* B1 = wb + NP * HID * C_DPAD / 2;
-    const bf16x8* W2 = reinterpret_cast<const bf16x8*>(B1 + HID);
-    const float* B2 = B1 + HID + NP * HID * HID / 2;
-    const bf16x8* W3 = reinterpret_cast<const bf16x8*>(B2 + HID);     // [4 row tiles][16][NP][64][8]
-    const float* B3 = B2 + HID + NP * 128 * HID / 2;                  // [128]
-    const float* W4 = B3 + 128;                                       // [128]
-    const float* B4 = W4 + 128;                                       // [1]
+    const auto [W1, B1, W2, B2, W3, B3, W4, B4] = critic_weights(A.critic_w);
     float xv[XI];
-    inputs_load<TC, C_DPAD, ROWS>(A.feats, n, e0, 0, 38, tid, xv);
+    inputs_load<TC, C_DPAD>(A.feats, n, e0, 0, 38, tid, xv);
     WRing<C_DPAD / 16> r1;
     wring_start(r1, wblocks<C_DPAD / 16, C_DPAD / 16>(W1, wave, 0, lane));
     const Row16 b1 = load_rows(B1, 32 * wave, lane);
-    inputs_store<TC, C_DPAD, ROWS>(xv, tid, s_x);
+    inputs_store<TC, C_DPAD>(xv, tid, s_x);
     __syncthreads();
     PST(3, __builtin_amdgcn_s_memtime());
     f32x16 a[1];
@@ -407,7 +415,6 @@ __device__ __forceinline__ void critic_tile(const PolicyArgs& A, int tile, unsig
     WRing<HID / 16> r2;
     wring_start(r2, wblocks<HID / 16, HID / 16>(W2, wave, 0, lane));
     store_planes<HSC, HPC>(a[0], 32 * wave, 0, b1, s_h, lane);
-    if (SAVE) store_rows_f32(a[0], 32 * wave, b1, sv.h1, HID, e0, n, lane);
     const Row16 b2 = load_rows(B2, 32 * wave, lane);
     __syncthreads();
     PST(5, __builtin_amdgcn_s_memtime());
@@ -420,13 +427,11 @@ __device__ __forceinline__ void critic_tile(const PolicyArgs& A, int tile, unsig
     const Row16 b3 = load_rows(B3, 32 * rt3, lane), w4 = load_rows(W4, 32 * rt3, lane);
     __syncthreads();                               // every wave has read h1
     store_planes<HSC, HPC>(a[0], 32 * wave, 0, b2, s_h, lane);
-    if (SAVE) store_rows_f32(a[0], 32 * wave, b2, sv.h2, HID, e0, n, lane);
     __syncthreads();
     PST(7, __builtin_amdgcn_s_memtime());
     if (wave < 4) {
         zero_acc<1>(a);
         mfma_rows<HID / 16, HSC, HPC, 1>(r3, wblocks<HID / 16, HID / 16>(W3, rt3, 0, lane), s_h, 0, lane, a);
-        if (SAVE) store_rows_f32(a[0], 32 * rt3, b3, sv.h3, 128, e0, n, lane);
         // the value head: this lane's 16 rows of h3, the other half-wave's (lane ^ 32), then the
         // four row tiles through LDS
         float v = 0.0f;
@@ -705,7 +710,7 @@ __global__ void __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(4, 4)
     PST(12, __builtin_amdgcn_s_getreg(20 | (31 << 11)));
     PST(13, role);
     int act = 0;
-    if (role == NAG) critic_tile<false>(A, b, s_mem, tid, lane, wave, CriticSave{});
+    if (role == NAG) critic_tile(A, b, s_mem, tid, lane, wave);
     else actor_tile(A, role, tile, s_mem, tid, lane, wave, act);
     PST(9, __builtin_amdgcn_s_memtime());
     PST(10, __builtin_amdgcn_s_memrealtime());
@@ -912,7 +917,7 @@ __global__ void __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(4, 4)
     PST(0, __builtin_amdgcn_s_memrealtime());
     PST(1, __builtin_amdgcn_s_memtime());
     if (b < A.nc) {
-        critic_tile<false>(A, 2 * A.tile0 + b, s_mem, tid, lane, wave, CriticSave{});
+        critic_tile(A, 2 * A.tile0 + b, s_mem, tid, lane, wave);
         return;
     }
     int role, tile, half = -1;
@@ -967,73 +972,36 @@ __global__ void __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(4, 4)
     PST(15, __builtin_amdgcn_s_memtime());
 }
 
-// The critic's forward over n samples for the A2C update (values + the saved hidden layers), on
-// sample-major input rows [n][GROW].
-__global__ void __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(4, 4)))
-k_critic_fwd(PolicyArgs A, CriticSave sv) {
-    __shared__ __attribute__((aligned(16))) unsigned char s_mem[LDS_BYTES];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    critic_tile<true, true>(A, (int)blockIdx.x, s_mem, tid, lane, wave, sv);
-}
-
-// The critic's backward through layers 3 and 2 for the A2C update (a2c_vec._CriticGrouped): on a
-// tile of 32 samples, g2 = (g3 W3) * [h2 > 0] and g1 = (g2 W2) * [h1 > 0], the input gradients of
-// the two 256-wide ReLU layers, with W3^T / W2^T packed like the forward's weights and the
-// upstream gradient split into bf16 planes in LDS; g2 and g1 go to HBM (the split-K weight
-// gradients read them) with per-tile column sums (the bias gradients).  One pass instead of two
-// GEMMs and two ReLU / bias-gradient passes.
-struct CriticBwd {
-    const float* g3;    // [n][128] layer 3's pre-activation gradient (fjsp_a2c_value_head_grad)
-    const float* h1;    // [n][256] post-ReLU hidden layers of the forward
-    const float* h2;
-    const float* w3t;   // P(W3^T [256][128]), NP * 256 * 128 / 2 floats
-    const float* w2t;   // P(W2^T [256][256])
-    float* g2;          // [n][256]
+// The grouped update's critic in ONE pass per 32-state tile (fjsp_a2c_critic_fused; a2c.py:683-699,
+// 713-722 over the batch's distinct global states, networks.py:41-61).  The critic loss of a batch
+// whose distinct state u occurs n_u times is sum_u sum_{samples, agents} (V_u - R)^2 / (8 count), a
+// quadratic in V_u: loss_u = a_u / 2 V^2 + b_u V + c_u with a_u = 2 n_u / count, b_u = -2 sum R /
+// (8 count), c_u = sum R^2 / (8 count) (coef [n][3], f64, summed per group by the caller), so
+// dL / dV_u = a_u V_u + b_u is known as soon as the forward has V_u, and the backward runs in the
+// same workgroup: forward as critic_tile (x -> h1 -> h2 -> h3 -> V; the ReLU masks of h1 / h2 kept
+// as 16 bits per lane, the C/D positions the backward's g1 / g2 tiles use), then gv (f64), g3 =
+// gv w4 [h3 > 0] from layer 3's accumulators, g2 = (g3 W3) [h2 > 0] and g1 = (g2 W2) [h1 > 0] on
+// the matrix cores: W3^T / W2^T packed like the forward's weights, the upstream gradient split
+// into bf16 planes in LDS (the forward's split arithmetic).  Out: h1, h2, g3, g2, g1 (the weight
+// gradients' operands, fjsp_a2c_wgrad), per tile the bias gradients and w4's / b4's gradients, the
+// loss; nothing else is written or re-read: h3 and the ReLU masks never leave the workgroup, 4.7 KB
+// of HBM traffic per state.
+struct CriticFused {
+    const double* coef;   // [n][3]: a, b, c
+    const float* w3t;     // P(W3^T [256][128]), NP * 256 * 128 / 2 floats
+    const float* w2t;     // P(W2^T [256][256])
+    float* h1;            // [n][256] post-ReLU
+    float* h2;
+    float* g3;            // [n][128] layer 3's pre-activation gradient
+    float* g2;            // [n][256] pre-activation gradients of layers 2 / 1
     float* g1;
-    float* bp2;         // [tiles][256] column sums of g2 / g1 per tile
-    float* bp1;
-    int n;
+    float* part;          // [tiles][FPW]: b1 | b2 | b3 grads, w4 grad [128], b4 grad, 3 zeros
+    double* loss;         // [tiles]
+    float* values;        // [n] or null
 };
+constexpr int FPW = 2 * HID + 2 * 128 + 4;
 constexpr int GS3 = 128 + 8;   // bf16 stride of the g3 planes [NP][TC][GS3]
 static_assert(NP * TC * GS3 * 2 <= H_BYTES && NP * HPC * 2 <= H_BYTES, "backward planes");
-// this lane's 16 values of rows row0.. (C/D layout) at sample column col of a sample-major
-// [n][ld] f32 matrix (0 past n)
-__device__ __forceinline__ void load_tile_rows(const float* __restrict__ m, int ld, int col, int n, int row0, int lane,
-                                               float v[16]) {
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (col < n) q = *reinterpret_cast<const float4*>(m + (size_t)col * ld + row0 + 8 * g + 4 * (lane >> 5));
-        v[4 * g] = q.x; v[4 * g + 1] = q.y; v[4 * g + 2] = q.z; v[4 * g + 3] = q.w;
-    }
-}
-// g = acc * [h > 0] -> HBM (sample-major [n][256]) and, for the tile's 32 samples, the column
-// sums into bp[row] (lanes 0 / 32 after a butterfly over each half-wave)
-__device__ __forceinline__ void relu_grad_out(f32x16& acc, const float h[16], float* __restrict__ g, float* __restrict__ bp,
-                                              int col, int n, int row0, int lane) {
-#pragma unroll
-    for (int r = 0; r < 16; r++) acc[r] = h[r] > 0.0f ? acc[r] : 0.0f;
-    if (col < n) {
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-            *reinterpret_cast<float4*>(g + (size_t)col * HID + row0 + 8 * q + 4 * (lane >> 5)) =
-                make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
-    }
-    float t[16];
-#pragma unroll
-    for (int r = 0; r < 16; r++) t[r] = acc[r];   // columns past n are 0 (h loaded as 0)
-#pragma unroll
-    for (int o = 1; o < 32; o <<= 1)
-#pragma unroll
-        for (int r = 0; r < 16; r++) t[r] += __shfl_xor(t[r], o);
-    if ((lane & 31) == 0) {
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-            *reinterpret_cast<float4*>(bp + row0 + 8 * q + 4 * (lane >> 5)) =
-                make_float4(t[4 * q], t[4 * q + 1], t[4 * q + 2], t[4 * q + 3]);
-    }
-}
 // a tile's f32 gradient (rows row0.., the C/D layout) -> bf16 planes [NP][TC][ST] (no ReLU, no bias)
 template <int ST, int PL>
 __device__ __forceinline__ void store_planes_raw(const f32x16& acc, int k0, __bf16* out, int lane) {
@@ -1055,86 +1023,6 @@ __device__ __forceinline__ void store_planes_raw(const f32x16& acc, int k0, __bf
         *reinterpret_cast<bf16x4*>(out + 2 * PL + col * ST + k) = pl;
     }
 }
-__global__ void __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(4, 4))) k_critic_bwd(CriticBwd B) {
-    __shared__ __attribute__((aligned(16))) __bf16 s_g[H_BYTES / 2];   // g3 planes, then g2 planes
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tile = blockIdx.x, e0 = tile * TC, n = B.n;
-    const int col = e0 + (lane & 31);
-    const bf16x8* W3T = reinterpret_cast<const bf16x8*>(B.w3t);
-    const bf16x8* W2T = reinterpret_cast<const bf16x8*>(B.w2t);
-    WRing<8> r3;
-    wring_start(r3, wblocks<8, 8>(W3T, wave, 0, lane));
-    float hv[16];
-    load_tile_rows(B.h2, HID, col, n, 32 * wave, lane, hv);
-    // g3 [32 samples][128] -> planes: thread t: sample t / 16, 8 consecutive features
-    {
-        const int sl = tid >> 4, f0 = (tid & 15) * 8, c = e0 + sl;
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) v[i] = 0.0f;
-        if (c < n) {
-            const float4 a = *reinterpret_cast<const float4*>(B.g3 + (size_t)c * 128 + f0);
-            const float4 b = *reinterpret_cast<const float4*>(B.g3 + (size_t)c * 128 + f0 + 4);
-            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-        }
-        bf16x8 ph, pm, pl;
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            __bf16 x0, x1, x2;
-            split3(v[i], x0, x1, x2);
-            ph[i] = x0;
-            pm[i] = x1;
-            pl[i] = x2;
-        }
-        constexpr int PL3 = TC * GS3;
-        *reinterpret_cast<bf16x8*>(s_g + sl * GS3 + f0) = ph;
-        *reinterpret_cast<bf16x8*>(s_g + PL3 + sl * GS3 + f0) = pm;
-        *reinterpret_cast<bf16x8*>(s_g + 2 * PL3 + sl * GS3 + f0) = pl;
-    }
-    __syncthreads();
-    f32x16 a[1];
-    zero_acc<1>(a);
-    mfma_rows<8, GS3, TC * GS3, 1>(r3, wblocks<8, 8>(W3T, wave, 0, lane), s_g, 0, lane, a);
-    WRing<16> r2;
-    wring_start(r2, wblocks<16, 16>(W2T, wave, 0, lane));
-    relu_grad_out(a[0], hv, B.g2, B.bp2 + (size_t)tile * HID, col, n, 32 * wave, lane);
-    load_tile_rows(B.h1, HID, col, n, 32 * wave, lane, hv);
-    __syncthreads();                               // every wave has read the g3 planes
-    store_planes_raw<HSC, HPC>(a[0], 32 * wave, s_g, lane);
-    __syncthreads();
-    zero_acc<1>(a);
-    mfma_rows<16, HSC, HPC, 1>(r2, wblocks<16, 16>(W2T, wave, 0, lane), s_g, 0, lane, a);
-    relu_grad_out(a[0], hv, B.g1, B.bp1 + (size_t)tile * HID, col, n, 32 * wave, lane);
-}
-
-// The grouped update's critic in ONE pass per 32-state tile (fjsp_a2c_critic_fused; a2c.py:683-699,
-// 713-722 over the batch's distinct global states, networks.py:41-61).  The critic loss of a batch
-// whose distinct state u occurs n_u times is sum_u sum_{samples, agents} (V_u - R)^2 / (8 count), a
-// quadratic in V_u: loss_u = a_u / 2 V^2 + b_u V + c_u with a_u = 2 n_u / count, b_u = -2 sum R /
-// (8 count), c_u = sum R^2 / (8 count) (coef [n][3], f64, summed per group by the caller), so
-// dL / dV_u = a_u V_u + b_u is known as soon as the forward has V_u, and the backward runs in the
-// same workgroup: forward as critic_tile (x -> h1 -> h2 -> h3 -> V; the ReLU masks of h1 / h2 kept
-// as 16 bits per lane, the C/D positions the backward's g1 / g2 tiles use), then gv (f64), g3 =
-// gv w4 [h3 > 0] from layer 3's accumulators, g2 = (g3 W3) [h2 > 0] and g1 = (g2 W2) [h1 > 0] on
-// the matrix cores (split-bf16, as k_critic_bwd).  Out: h1, h2, g3, g2, g1 (the split-K weight
-// gradients' operands), per tile the bias gradients and w4's / b4's gradients, the loss; nothing
-// else is written or re-read (the three-kernel path wrote h3, read it back for the value head and
-// read h1 / h2 / g3 again for the backward: 8 KB per state against 4.7 KB here).
-struct CriticFused {
-    const double* coef;   // [n][3]: a, b, c
-    const float* w3t;     // P(W3^T [256][128]), as CriticBwd
-    const float* w2t;     // P(W2^T [256][256])
-    float* h1;            // [n][256] post-ReLU
-    float* h2;
-    float* g3;            // [n][128] layer 3's pre-activation gradient
-    float* g2;            // [n][256] pre-activation gradients of layers 2 / 1
-    float* g1;
-    float* part;          // [tiles][FPW]: b1 | b2 | b3 grads, w4 grad [128], b4 grad, 3 zeros
-    double* loss;         // [tiles]
-    float* values;        // [n] or null
-};
-constexpr int FPW = 2 * HID + 2 * 128 + 4;
 // the column (sample) sums of a lane's 16 rows over the tile's 32 columns -> bp[row] (lanes 0 / 32)
 __device__ __forceinline__ void col_sums_out(float t[16], float* __restrict__ bp, int row0, int lane) {
 #pragma unroll
@@ -1182,18 +1070,10 @@ k_critic_fused(PolicyArgs A, CriticFused F) {
     float* s_part = reinterpret_cast<float*>(s_mem);             // value partials [4][TC] (after layer 1)
     float* s_gv = reinterpret_cast<float*>(s_mem + X_BYTES + H_BYTES);   // [TC] dL / dV
     float* part = F.part + (size_t)tile * FPW;
-    const float* wb = A.critic_w;
-    const bf16x8* W1 = reinterpret_cast<const bf16x8*>(wb);
-    const float* B1 = wb + NP * HID * C_DPAD / 2;
-    const bf16x8* W2 = reinterpret_cast<const bf16x8*>(B1 + HID);
-    const float* B2 = B1 + HID + NP * HID * HID / 2;
-    const bf16x8* W3 = reinterpret_cast<const bf16x8*>(B2 + HID);
-    const float* B3 = B2 + HID + NP * 128 * HID / 2;
-    const float* W4 = B3 + 128;
-    const float* B4 = W4 + 128;
+    const auto [W1, B1, W2, B2, W3, B3, W4, B4] = critic_weights(A.critic_w);
     const bf16x8* W3T = reinterpret_cast<const bf16x8*>(F.w3t);
     const bf16x8* W2T = reinterpret_cast<const bf16x8*>(F.w2t);
-    // ---- forward (critic_tile<SAVE, ROWS> with the ReLU masks kept)
+    // ---- forward (critic_tile on sample-major input rows, h1 / h2 also to HBM, the ReLU masks kept)
     float xv[XI];
     inputs_load<TC, C_DPAD, true>(A.feats, n, e0, 0, 38, tid, xv);
     WRing<C_DPAD / 16> r1;
@@ -1285,7 +1165,7 @@ k_critic_fused(PolicyArgs A, CriticFused F) {
         col_sums_out(tw, part + 2 * HID + 128, 32 * rt3, lane);
     }
     __syncthreads();
-    // ---- g2 = (g3 W3) [h2 > 0], g1 = (g2 W2) [h1 > 0] (k_critic_bwd's products)
+    // ---- g2 = (g3 W3) [h2 > 0], g1 = (g2 W2) [h1 > 0]
     zero_acc<1>(a);
     mfma_rows<8, GS3, PL3, 1>(rb3, wblocks<8, 8>(W3T, wave, 0, lane), s_h, 0, lane, a);
     WRing<16> rb2;
@@ -2230,21 +2110,6 @@ extern "C" int fjsp_debug_policy_stamps(unsigned long long* out, int32_t clear) 
 }
 #endif
 
-extern "C" int fjsp_a2c_critic_forward(const float* x, int32_t n, const float* critic_w, float* h1, float* h2,
-                                       float* h3, float* values, void* stream) {
-    if (n <= 0) return fjsp_internal_fail("fjsp_a2c_critic_forward: n must be > 0");
-    if (!x || !critic_w || !h1 || !h2 || !h3 || !values) return fjsp_internal_fail("fjsp_a2c_critic_forward: null buffer");
-    if ((uintptr_t)x & 15u) return fjsp_internal_fail("fjsp_a2c_critic_forward: x must be 16-byte aligned");
-    PolicyArgs A{x, nullptr, n, nullptr, critic_w, nullptr, 0u, 0u, 0, nullptr, values, nullptr, (n + TC - 1) / TC, 0};
-    hipLaunchKernelGGL(k_critic_fwd, dim3((unsigned)A.nc), dim3(NTHR), 0, (hipStream_t)stream, A, CriticSave{h1, h2, h3});
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        fjsp_internal_fail(hipGetErrorString(err));
-        return -2;
-    }
-    return 0;
-}
-
 extern "C" int fjsp_a2c_critic_fused(const float* x, int32_t n, const float* critic_w, const float* w3t,
                                      const float* w2t, const double* coef, float* h1, float* h2, float* g3, float* g2,
                                      float* g1, float* part, double* loss, float* values, void* stream) {
@@ -2300,22 +2165,6 @@ extern "C" int fjsp_a2c_wgrad(const float* g, int32_t m, int64_t ldg, const floa
     }
     hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((m * nout + 255) / 256)), dim3(256), 0, st, part, P, m, npad, nout,
                        out, ldo);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        fjsp_internal_fail(hipGetErrorString(err));
-        return -2;
-    }
-    return 0;
-}
-
-extern "C" int fjsp_a2c_critic_backward(const float* g3, const float* h1, const float* h2, int32_t n, const float* w3t,
-                                        const float* w2t, float* g2, float* g1, float* bias_part2, float* bias_part1,
-                                        void* stream) {
-    if (n <= 0) return fjsp_internal_fail("fjsp_a2c_critic_backward: n must be > 0");
-    if (!g3 || !h1 || !h2 || !w3t || !w2t || !g2 || !g1 || !bias_part2 || !bias_part1)
-        return fjsp_internal_fail("fjsp_a2c_critic_backward: null buffer");
-    const CriticBwd B{g3, h1, h2, w3t, w2t, g2, g1, bias_part2, bias_part1, n};
-    hipLaunchKernelGGL(k_critic_bwd, dim3((unsigned)((n + TC - 1) / TC)), dim3(NTHR), 0, (hipStream_t)stream, B);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) {
         fjsp_internal_fail(hipGetErrorString(err));

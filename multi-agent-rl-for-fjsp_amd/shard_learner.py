@@ -388,7 +388,7 @@ def owner_losses(actors, critic, recv, rank, world, count, entropy_coef):
         la = -(w * logp).sum() / count - entropy_coef * (nrec * ent).sum() / count
         al = al + torch.nn.functional.one_hot(torch.tensor(a, device=dev), NA).float() * la
     g = _regroup(crec[:, 0:2].contiguous().view(torch.int64).reshape(-1))
-    if g is not None and crec.is_cuda and A.critic_fused and A.critic_onepass_on and g.gsorted is not None:
+    if g is not None and crec.is_cuda and g.gsorted is not None:
         # the critic's share in one pass per distinct state (fjsp_a2c_critic_fused): the records of
         # one state (from every source rank) merged into its sample count and return sums
         xs = crec[:, 8:8 + A.GLOBAL_DIM]
@@ -405,10 +405,7 @@ def owner_losses(actors, critic, recv, rank, world, count, entropy_coef):
         u = g.U[0]
         x = torch.nn.functional.pad(xs.index_select(0, g.first[0, :u]).contiguous().view(torch.float32),
                                     (0, A.GROUP_ROW - A.GLOBAL_DIM))                     # [u, 40]
-        if x.is_cuda and u >= 65536 and A.critic_fused:
-            vu = A.critic_grouped(critic, x)
-        else:
-            vu = A.mlp_forward(critic.net, x[:, :A.GLOBAL_DIM]).reshape(-1)
+        vu = A.mlp_forward(critic.net, x[:, :A.GLOBAL_DIM]).reshape(-1)
         um = g.first.shape[1]
         vu = torch.nn.functional.pad(vu.reshape(1, 1, -1), (0, um - u))
         v = g.gather(vu).reshape(-1).double()                                             # [Rc]

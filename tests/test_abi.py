@@ -4,6 +4,8 @@ import ctypes
 import os
 import re
 
+import pytest
+
 from tests import gpu_util as G
 
 
@@ -20,7 +22,10 @@ def test_library_exports_every_symbol():
     L = G.native.lib()
     for name in _declared():
         assert hasattr(L, name), name
-    assert L.fjsp_abi_version() == G.native.ABI_VERSION == 13
+    assert L.fjsp_abi_version() == G.native.ABI_VERSION == 14
+    for gone in ("forward", "backward"):   # ABI 14: the grouped critic's three-kernel entries left
+        with pytest.raises(AttributeError):
+            getattr(L, "fjsp_a2c_critic_" + gone)
 
 
 def test_config_validation_without_gpu():

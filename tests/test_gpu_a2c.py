@@ -613,40 +613,49 @@ def _reference_losses_f64(A, spec, feats, masks, actions, ret, adv, seed, entrop
     return al, cl
 
 
-def test_fused_critic_forward_backward_matches_torch(M):
-    """The grouped update's critic (a2c_vec._CriticGrouped: fjsp_a2c_critic_forward, then the
-    value-head / ReLU-bias kernels and split-K weight gradients) against a float64 evaluation of
-    the same network, beside the PyTorch-GEMM path (mlp_forward): values at most 3x that f32
-    path's error (+1e-7 relative), every parameter gradient within max(3x its error, 3e-3)
-    relative.  Both f32 paths flip a ReLU unit here and there whose pre-activation is within
-    rounding of 0 (scripts/diag_critic_fused.py: one per layer of 70 001 x 256 for either path, the
-    activations themselves within 7e-7 of float64), and one flipped unit of one sample moves a
-    weight gradient summed over 70 001 samples by ~3e-4 relative; a layout or indexing error
-    moves it by O(1)."""
+def test_critic_fused_values_match_float64(M):
+    """fjsp_a2c_critic_fused's optional values output (the Python path passes NULL) against a
+    float64 evaluation of the same network, beside the PyTorch-GEMM path (mlp_forward): max |v -
+    v64| / max |v64| at most 3x that f32 path's (+1e-7).  U = 70 001: many tiles and a ragged last
+    one; U = 33: one full 32-state tile and a tile holding one state, whose values buffer of 64
+    keeps its sentinel past the last state.  No gradient is compared here: both f32 paths flip a
+    ReLU unit here and there whose pre-activation is within rounding of 0, which a sum over 70 001
+    samples absorbs (test_critic_onepass_matches_float64) and a sum over 33 does not."""
     import copy
+    import ctypes
     A = M["A"]
-    torch.manual_seed(3)
-    _, critic = A.init_networks(seed=1, device="cuda")
-    U = 70001
-    xT = (torch.rand(38, U, device="cuda") * torch.randint(0, 30, (38, 1), device="cuda")).float()
-    w = torch.randn(U, device="cuda")
-    c64 = copy.deepcopy(critic).double()
-    v64 = c64.net(xT.double().t()).reshape(-1)
-    (v64 * w.double()).sum().backward()
-    g64 = [p.grad for p in c64.parameters()]
-    res = {}
-    xr = torch.nn.functional.pad(xT.t(), (0, 2)).contiguous()   # the kernel's sample-major rows
-    for name, fwd in (("fused", lambda: A.critic_grouped(critic, xr)),
-                      ("torch", lambda: A.mlp_forward(critic.net, xT.t()).reshape(-1))):
-        critic.zero_grad(set_to_none=True)
-        v = fwd()
-        (v * w).sum().backward()
-        res[name] = (float((v.double() - v64).abs().max() / v64.abs().max()),
-                     [float((p.grad.double() - g).norm() / g.norm()) for p, g in zip(critic.parameters(), g64)])
-    ef, et = res["fused"], res["torch"]
-    assert ef[0] <= 3 * et[0] + 1e-7, (ef[0], et[0])
-    for a, b in zip(ef[1], et[1]):
-        assert a <= max(3 * b, 3e-3), (ef[1], et[1])
+    for U in (70001, 33):
+        torch.manual_seed(3)
+        _, critic = A.init_networks(seed=1, device="cuda")
+        xT = (torch.rand(38, U, device="cuda") * torch.randint(0, 30, (38, 1), device="cuda")).float()
+        nu = torch.randint(1, 6, (U,), device="cuda").double()
+        sr = torch.randn(U, device="cuda", dtype=torch.float64) * nu * 8 * 3
+        sr2 = sr * sr / (8 * nu) + torch.rand(U, device="cuda", dtype=torch.float64) * 50
+        coef = A.critic_coef_sums(nu, sr, sr2, float(nu.sum()))
+        with torch.no_grad():
+            v64 = copy.deepcopy(critic).double().net(xT.double().t()).reshape(-1)
+            vt = A.mlp_forward(critic.net, xT.t()).reshape(-1)
+            n = critic.net
+            cw = A.pack_critic_weights(*[t for i in (0, 2, 4, 6) for t in (n[i].weight, n[i].bias)])
+            w3t, w2t = A.pack_mfma(n[4].weight.t()).reshape(-1), A.pack_mfma(n[2].weight.t()).reshape(-1)
+        xr = torch.nn.functional.pad(xT.t(), (0, 2)).contiguous()   # the kernel's sample-major rows
+        tiles = -(-U // 32)
+        E = lambda *sh: torch.empty(*sh, dtype=torch.float32, device="cuda")  # noqa: E731
+        h1, h2, g2, g1, g3, part = E(U, 256), E(U, 256), E(U, 256), E(U, 256), E(U, 128), E(tiles, A.nat.CRITIC_FUSED_PW)
+        loss = torch.empty(tiles, dtype=torch.float64, device="cuda")
+        SENT = -12345.0
+        vals = torch.full((32 * tiles,), SENT, device="cuda")
+        V = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        A.nat.check(A.nat.lib().fjsp_a2c_critic_fused(V(xr), U, V(cw), V(w3t), V(w2t), V(coef), V(h1), V(h2), V(g3), V(g2),
+                                                      V(g1), V(part), V(loss), V(vals),
+                                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        torch.cuda.synchronize()
+        ef = float((vals[:U].double() - v64).abs().max() / v64.abs().max())
+        et = float((vt.double() - v64).abs().max() / v64.abs().max())
+        print(f"U={U}: fused {ef:.3e}, torch {et:.3e}")
+        assert ef <= 3 * et + 1e-7, (ef, et)
+        assert vals.numel() > U and (U != 33 or vals.numel() == 64)
+        assert bool((vals[U:] == SENT).all())
 
 
 def test_shard_keys_kernel_equals_torch(M):
@@ -758,11 +767,12 @@ def test_critic_onepass_matches_float64(M):
     """The one-pass critic (a2c_vec._CriticOnePass: fjsp_a2c_critic_fused's forward, value
     gradient from the per-state loss coefficients, value-head and hidden-layer backward in one
     kernel, then the split-K weight gradients) against a float64 evaluation of the same loss,
-    sum_u a_u/2 V_u^2 + b_u V_u + c_u, beside the three-kernel path (critic_grouped + autograd of
-    the same loss): loss within 1e-6 relative, every gradient within max(3x the three-kernel
-    path's error, 3e-3) relative (ReLU units within rounding of 0 flip in either f32 path, see
-    test_fused_critic_forward_backward_matches_torch); a padding state (0 coefficients)
-    contributes nothing."""
+    sum_u a_u/2 V_u^2 + b_u V_u + c_u, beside the PyTorch-GEMM path (mlp_forward + autograd of the
+    same loss): loss within 1e-6 relative, every gradient within max(3x the PyTorch-GEMM path's
+    error, 3e-3) relative.  Both f32 paths flip a ReLU unit here and there whose pre-activation is
+    within rounding of 0 (the activations themselves within 7e-7 of float64), and one flipped unit
+    of one sample moves a weight gradient summed over 70 001 samples by ~3e-4 relative; a layout or
+    indexing error moves it by O(1).  A padding state (0 coefficients) contributes nothing."""
     import copy
     A = M["A"]
     torch.manual_seed(4)
@@ -783,14 +793,14 @@ def test_critic_onepass_matches_float64(M):
     xr = torch.nn.functional.pad(xT.t(), (0, 2)).contiguous()
     res = {}
     for name, fwd in (("onepass", lambda: A.critic_onepass(critic, xr, coef)),
-                      ("three_kernel", lambda: (lambda v: (0.5 * coef[:, 0] * v * v + coef[:, 1] * v + coef[:, 2]).sum())(
-                          A.critic_grouped(critic, xr).double()))):
+                      ("torch", lambda: (lambda v: (0.5 * coef[:, 0] * v * v + coef[:, 1] * v + coef[:, 2]).sum())(
+                          A.mlp_forward(critic.net, xT.t()).reshape(-1).double()))):
         critic.zero_grad(set_to_none=True)
         loss = fwd()
         loss.backward()
         res[name] = (float(loss), [p.grad.detach().clone() for p in critic.parameters()])
     lo, go = res["onepass"]
-    lt, gt = res["three_kernel"]
+    lt, gt = res["torch"]
     assert abs(lo - float(l64)) <= 1e-6 * abs(float(l64)), (lo, float(l64))
     for p_o, p_t, g in zip(go, gt, g64):
         eo = float((p_o.double() - g).norm() / g.norm())
@@ -821,7 +831,7 @@ def test_wgrad_kernel_matches_float64(M, m, nx, nout, U):
     et = float((A._splitk_wgrad(g, x[:, :nout]).double() - ref).norm() / ref.norm())
     assert e <= max(3 * et, 2e-6), (e, et)
     assert torch.equal(gw, A.critic_wgrad(g, x, nout))
-    assert torch.equal(gw, A._critic_wgrad(g, x, nout if nout != nx else None))
+    assert torch.equal(gw, A.critic_wgrad(g, x, None if nout == nx else nout))
     L = A.nat.lib()
     try:   # the 8-wave kernel (library-wide option "wgrad_waves"): the same bits
         assert L.fjsp_set_option(None, b"wgrad_waves", 8) == 0
