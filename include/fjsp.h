@@ -508,6 +508,23 @@ int fjsp_a2c_run_sums(const float* vals, int32_t J, const int32_t* rowmap, const
 int fjsp_a2c_actor_head(const float* pu, int32_t umax, const int64_t* inv, int32_t T, int32_t n, const int8_t* masks,
                         const uint8_t* actions, const double* adv, const float* adv_mean, const float* adv_std,
                         float inv_count, float ent_coef, float* grad, double* sums, void* stream);
+/* The PPO loss head of the grouped update (ppo_vec.ppo_update).  The clipped objective is an
+ * extension: the reference has A2C only; the nearest reference lines are a2c.py:204-220 (masked
+ * probabilities) and :705-731 (entropy, calc_actor_loss), which this entry computes exactly as
+ * fjsp_a2c_actor_head does (same operands, same layouts).  In addition: logp_old f32 [8][T * n] =
+ * the behaviour policy's log-probability of each (agent, sample)'s action, or NULL = record mode
+ * (ratio 1: the gradient is fjsp_a2c_actor_head's bit for bit); logp_out f32 [8][T * n] or NULL
+ * receives the current log-probabilities (record mode's output is the later epochs' logp_old);
+ * clip_eps in (0, 1).  Per (agent, sample): r = exp(logp - logp_old), surr = min(r adv,
+ * clamp(r, 1 - clip_eps, 1 + clip_eps) adv), and the loss -(sum surr) / count - ent_coef (sum
+ * entropy) / count.  Out: grad f32 [29][T * n] as fjsp_a2c_actor_head (a sample the clip holds
+ * contributes the entropy term only) and sums f64 [8][ceil(T * n / 256)][4] = per agent and block
+ * of 256 samples (sum surr, sum entropy, sum (r - 1) - (logp - logp_old) = the approximate KL's
+ * terms, number of clipped samples); the caller adds the blocks.  Stream-ordered. */
+int fjsp_a2c_actor_head_ppo(const float* pu, int32_t umax, const int64_t* inv, int32_t T, int32_t n, const int8_t* masks,
+                            const uint8_t* actions, const double* adv, const float* adv_mean, const float* adv_std,
+                            const float* logp_old, float* logp_out, float clip_eps, float inv_count, float ent_coef,
+                            float* grad, double* sums, void* stream);
 /* ReLU backward fused with the bias gradient (the critic backward of the A2C update,
  * a2c.py:713-722 calc_critic_loss through the 256-256-128 ReLU layers): gy, y f32 [rows][cols]
  * (y = the layer's ReLU output), cols 128 or 256.  Out: g f32 [rows][cols] = gy where y > 0

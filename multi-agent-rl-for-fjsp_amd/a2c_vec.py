@@ -369,6 +369,13 @@ class ActorStack(nn.Module):
         runs alone and the others stacked on the second-largest count (padding columns are
         computed and never gathered).  cols(agents, idx [k, u]) -> [k, 13, u] may stand in for x
         (the inputs of just the representatives)."""
+        return self.forward_reps(*self.rep_inputs(x, g, cols))
+
+    @staticmethod
+    def rep_inputs(x, g, cols=None):
+        """forward_rows' gathers, which depend on the batch alone (not on the weights): (the agent
+        with the most groups, the other agents' indices, their representatives' inputs [7, 13, u2],
+        the big agent's [13, ub], Umax)."""
         U = g.U
         umax = g.first.shape[1]
         big = max(range(NA), key=lambda a: U[a])
@@ -383,6 +390,11 @@ class ActorStack(nn.Module):
         else:
             xr = cols(ridx, fr)
             xb = cols(_index_tensor((big,), ridx.device), g.first[big:big + 1, :ub])[0]
+        return big, ridx, xr, xb, umax
+
+    def forward_reps(self, big, ridx, xr, xb, umax):
+        """forward_rows' networks on rep_inputs' gathered inputs -> probabilities [8, 8, Umax]."""
+        u2, ub = xr.shape[2], xb.shape[1]
         h = torch.relu(torch.baddbmm(self.b1[ridx], self.W1[ridx], xr))
         h = torch.relu(torch.baddbmm(self.b2[ridx], self.W2[ridx], h))
         pr = torch.softmax(torch.baddbmm(self.b3[ridx], self.W3[ridx], h) + self.logit_pad[ridx], dim=1)
@@ -774,27 +786,33 @@ class _ActorHead(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gl):
         (grad,) = ctx.saved_tensors
-        g = ctx.g
-        S = grad.shape[1]
-        umax = g.ends.shape[1]
-        if g.gsorted is not None:   # the device grouping: one run-sum pass (fjsp_a2c_run_sums)
-            row_agent = _index_tensor(tuple(a for a in range(NA) for _ in range(N_ACTIONS[a])), grad.device)
-            rs = run_sums(grad, row_agent, gl.to(grad.dtype)[row_agent], g)              # [29, Umax]
-            out = torch.zeros(NA * 8, umax, dtype=grad.dtype, device=grad.device)
-            out[_valid_rows(grad.device)] = rs
-            return out.view(NA, 8, umax), None, None, None, None, None, None, None, None
-        # each agent's rows in its sorted sample order, scaled by the agent's loss gradient
-        srt = torch.empty_like(grad)
-        for a in range(NA):
-            o, k = MASK_OFFS[a], N_ACTIONS[a]
-            torch.gather(grad[o:o + k], 1, g.perm[a].expand(k, S), out=srt[o:o + k])
+        return actor_head_group_grads(grad, ctx.g, gl), None, None, None, None, None, None, None, None
+
+
+def actor_head_group_grads(grad, g, gl):
+    """The loss heads' backward: the per-sample gradients grad f32 [29, S] (the valid (agent, action)
+    rows), each scaled by its agent's loss gradient gl [8], summed per group of the RowGroups g
+    (runs of the sorted order) -> [8, 8, Umax]."""
+    S = grad.shape[1]
+    umax = g.ends.shape[1]
+    if g.gsorted is not None:   # the device grouping: one run-sum pass (fjsp_a2c_run_sums)
         row_agent = _index_tensor(tuple(a for a in range(NA) for _ in range(N_ACTIONS[a])), grad.device)
-        srt.mul_(gl.to(grad.dtype)[row_agent, None])
-        ce = _prefix_at(srt, (g.ends - 1)[row_agent])
-        rs = torch.cat([ce[:, :1], ce[:, 1:] - ce[:, :-1]], dim=1).to(grad.dtype)    # [29, Umax]
+        rs = run_sums(grad, row_agent, gl.to(grad.dtype)[row_agent], g)              # [29, Umax]
         out = torch.zeros(NA * 8, umax, dtype=grad.dtype, device=grad.device)
         out[_valid_rows(grad.device)] = rs
-        return out.view(NA, 8, umax), None, None, None, None, None, None, None, None
+        return out.view(NA, 8, umax)
+    # each agent's rows in its sorted sample order, scaled by the agent's loss gradient
+    srt = torch.empty_like(grad)
+    for a in range(NA):
+        o, k = MASK_OFFS[a], N_ACTIONS[a]
+        torch.gather(grad[o:o + k], 1, g.perm[a].expand(k, S), out=srt[o:o + k])
+    row_agent = _index_tensor(tuple(a for a in range(NA) for _ in range(N_ACTIONS[a])), grad.device)
+    srt.mul_(gl.to(grad.dtype)[row_agent, None])
+    ce = _prefix_at(srt, (g.ends - 1)[row_agent])
+    rs = torch.cat([ce[:, :1], ce[:, 1:] - ce[:, :-1]], dim=1).to(grad.dtype)    # [29, Umax]
+    out = torch.zeros(NA * 8, umax, dtype=grad.dtype, device=grad.device)
+    out[_valid_rows(grad.device)] = rs
+    return out.view(NA, 8, umax)
 
 
 _VALID_ROWS = {}
@@ -877,6 +895,25 @@ def _prefix_sum(w, block=1024, dtype=None, add=0):
     return c.view(*lead, P)[..., :S]
 
 
+def cols_of_rows(rows, gidx):
+    """ActorStack.forward_rows' cols from the sample-major rows f32 [S, 40] of the keys pass."""
+    def cols(agents, idx):                                   # [k, 13, u]
+        k, u = idx.shape
+        r = rows.index_select(0, idx.reshape(-1)).view(k, u, GROUP_ROW)
+        return torch.gather(r, 2, gidx[agents][:, None, :].expand(k, u, gidx.shape[1])).transpose(1, 2)
+    return cols
+
+
+def cols_of_states(gt, gidx):
+    """ActorStack.forward_rows' cols from the global states as feature rows gt f32 [38, S]."""
+    def cols(agents, idx):                                   # [k, 13, u] from gt
+        k, u = idx.shape
+        c = gt[:, idx.reshape(-1)].view(GLOBAL_DIM, k, u)
+        c = torch.cat([c, c.new_zeros(1, k, u)])
+        return c[gidx[agents], torch.arange(k, device=idx.device)[:, None], :]
+    return cols
+
+
 class A2CLosses:
     """Loss sums for one (possibly sharded) batch; `count` = the GLOBAL sample count.
 
@@ -928,21 +965,12 @@ class A2CLosses:
             # keys pass's rows: no [38, S] copy of the slab, no 38 scattered words per column
             if rows is None:
                 rows = feature_rows(f3)
-
-            def cols(agents, idx):                                   # [k, 13, u]
-                k, u = idx.shape
-                r = rows.index_select(0, idx.reshape(-1)).view(k, u, GROUP_ROW)
-                return torch.gather(r, 2, gidx[agents][:, None, :].expand(k, u, gidx.shape[1])).transpose(1, 2)
+            cols = cols_of_rows(rows, gidx)
         else:
             # the global states as feature rows [38, S]: one copy of the slab, then row-wise
             # gathers of the groups' representatives
             gt = f3.permute(1, 0, 2).reshape(GLOBAL_DIM, S)
-
-            def cols(agents, idx):                                   # [k, 13, u] from gt
-                k, u = idx.shape
-                c = gt[:, idx.reshape(-1)].view(GLOBAL_DIM, k, u)
-                c = torch.cat([c, c.new_zeros(1, k, u)])
-                return c[gidx[agents], torch.arange(k, device=idx.device)[:, None], :]
+            cols = cols_of_states(gt, gidx)
         # the critic first: its GEMMs keep the GPU busy while the host issues the actors' many
         # small launches (after the grouping's host synchronisations the queue is empty)
         critic_loss = None

@@ -1682,6 +1682,117 @@ __global__ void __launch_bounds__(256) k_actor_head(const float* __restrict__ pu
     }
 }
 
+// The PPO loss head (ppo_vec.ppo_update; an extension, the reference has A2C only): k_actor_head's
+// pass with one more per-sample operand, the behaviour policy's log-probability, and the clipped
+// surrogate in place of adv_n logp.  p, m, entropy, pm, s2, qa, qc and logp are k_actor_head's,
+// the same operations in the same order.  r = exp(logp - logp_old) (1 in record mode: logp_old
+// NULL), rc = clamp(r, 1 - eps_c, 1 + eps_c), surr = min(r adv, rc adv), L = sum over agents of
+// -(sum surr) / count - c (sum entropy) / count.  d surr / d logp = r adv unless the clip holds
+// the sample (adv > 0 and r > 1 + eps_c, or adv < 0 and r < 1 - eps_c), which is autograd's
+// gradient of min(r adv, clamp(r) adv) (a tie halves, clamp passes at its inclusive bounds).
+//   logp_out[a][s] = logp when given (record mode's output, the later epochs' logp_old);
+//   grad as k_actor_head; sums[a][block] = the workgroup's (surr, entropy, (r - 1) - (logp -
+//   logp_old) = the approximate KL term, clipped count) sums.
+__global__ void __launch_bounds__(256) k_actor_head_ppo(const float* __restrict__ pu, int umax,
+                                                        const int64_t* __restrict__ inv, int T, int n,
+                                                        const int8_t* __restrict__ masks,
+                                                        const uint8_t* __restrict__ actions,
+                                                        const double* __restrict__ advs,
+                                                        const float* __restrict__ adv_mean,
+                                                        const float* __restrict__ adv_std,
+                                                        const float* __restrict__ logp_old,
+                                                        float* __restrict__ logp_out, float clip_eps, float inv_count,
+                                                        float ent_coef, float* __restrict__ grad,
+                                                        double* __restrict__ sums) {
+    const int a = blockIdx.y;
+    const size_t S = (size_t)T * n;
+    const size_t s = (size_t)blockIdx.x * 256 + threadIdx.x;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    if (s < S) {
+        const size_t t = s / (size_t)n, e = s - t * (size_t)n;
+        const size_t u = (size_t)inv[(size_t)a * S + s];
+        const int na = c_nact[a], mo = c_mask_off[a];
+        const size_t ta = (t * NAG + (size_t)a) * (size_t)n + e;
+        const int act = (int)actions[ta];
+        const float adv = adv_std ? ((float)advs[ta] - adv_mean[a]) / (adv_std[a] + 1e-8f) : (float)advs[ta];
+        float p[8], m[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            p[j] = pu[((size_t)a * 8 + j) * umax + u];
+            m[j] = j < na ? (float)masks[(t * 29 + mo + j) * n + e] : 0.0f;
+        }
+        // entropy and its gradient
+        float ent = 0.0f, g[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const float pe = p[j] + 1e-10f;
+            ent += p[j] * logf(pe);
+            g[j] = -ent_coef * inv_count * -(logf(pe) + p[j] / pe);
+        }
+        ent = -ent;
+        // masked probabilities: p m / sum(p m), or m / sum(m) when nothing valid is left
+        float sr = 0.0f, sm = 0.0f, pm[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) { sr += p[j] * m[j]; sm += m[j]; }
+#pragma unroll
+        for (int j = 0; j < 8; j++) pm[j] = sr > 0.0f ? (p[j] * m[j]) / sr : m[j] / sm;
+        float s2 = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 8; j++) s2 += pm[j];
+        float qa = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 8; j++) qa = j == act ? pm[j] / s2 : qa;
+        const float eps = 1.1920928955078125e-07f;
+        const float qc = fminf(fmaxf(qa, eps), 1.0f - eps);
+        const float logp = logf(qc);
+        // the ratio to the behaviour policy and the clipped surrogate
+        const size_t as = (size_t)a * S + s;
+        const float dlp = logp_old ? logp - logp_old[as] : 0.0f;
+        const float r = logp_old ? expf(dlp) : 1.0f;
+        if (logp_out) logp_out[as] = logp;
+        const float lo = 1.0f - clip_eps, hi = 1.0f + clip_eps;
+        const float rc = fminf(fmaxf(r, lo), hi);
+        const float surr = fminf(r * adv, rc * adv);
+        const bool clipped = (adv > 0.0f && r > hi) || (adv < 0.0f && r < lo);
+        // d L / d logp = -adv r / count unless clipped; through clamp (inclusive), q = pm / s2, pm = p m / sr
+        const float gl = clipped ? 0.0f : (-adv * inv_count) * r;
+        const float gq = (qa >= eps && qa <= 1.0f - eps) ? gl / qc : 0.0f;
+        if (sr > 0.0f) {
+            float gpm[8], dot = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                gpm[j] = (j == act ? gq / s2 : 0.0f) - gq * qa / s2;   // d q_act / d pm_j
+                dot += gpm[j] * (p[j] * m[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < 8; j++) g[j] += m[j] * (gpm[j] / sr - dot / (sr * sr));
+        }
+#pragma unroll
+        for (int j = 0; j < 8; j++)
+            if (j < na) grad[(size_t)(mo + j) * S + s] = g[j];   // valid actions only (rows mo..mo+na)
+        acc[0] = (double)surr;
+        acc[1] = (double)ent;
+        acc[2] = (double)((r - 1.0f) - dlp);
+        acc[3] = clipped ? 1.0 : 0.0;
+    }
+    // the workgroup's sums, one partial quadruple per workgroup (no atomics, as k_actor_head)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) acc[k] += __shfl_xor(acc[k], off);
+    }
+    __shared__ double s_part[4][4];
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) s_part[threadIdx.x >> 6][k] = acc[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const double v = s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x];
+        sums[((size_t)a * gridDim.x + blockIdx.x) * 4 + threadIdx.x] = v;
+    }
+}
+
 // The shard learner's actor loss head over an owner's records (shard_learner.owner_losses): a
 // record stands for n samples of one agent with equal (input, mask, action) and carries w = the
 // f64 sum of their normalised advantages; the samples' loss terms and gradients are linear in the
@@ -1979,6 +2090,28 @@ extern "C" int fjsp_a2c_actor_head(const float* pu, int32_t umax, const int64_t*
     const size_t S = (size_t)T * (size_t)n;
     hipLaunchKernelGGL(k_actor_head, dim3((unsigned)((S + 255) / 256), NAG), dim3(256), 0, (hipStream_t)stream, pu, umax,
                        inv, T, n, masks, actions, adv, adv_mean, adv_std, inv_count, ent_coef, grad, sums);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) {
+        fjsp_internal_fail(hipGetErrorString(err));
+        return -2;
+    }
+    return 0;
+}
+
+extern "C" int fjsp_a2c_actor_head_ppo(const float* pu, int32_t umax, const int64_t* inv, int32_t T, int32_t n,
+                                       const int8_t* masks, const uint8_t* actions, const double* adv,
+                                       const float* adv_mean, const float* adv_std, const float* logp_old,
+                                       float* logp_out, float clip_eps, float inv_count, float ent_coef, float* grad,
+                                       double* sums, void* stream) {
+    if (T <= 0 || n <= 0 || umax <= 0) return fjsp_internal_fail("fjsp_a2c_actor_head_ppo: T, n and umax must be > 0");
+    if (!(clip_eps > 0.0f && clip_eps < 1.0f))
+        return fjsp_internal_fail("fjsp_a2c_actor_head_ppo: clip_eps must be in (0, 1)");
+    if (!pu || !inv || !masks || !actions || !adv || !grad || !sums || (!adv_mean != !adv_std))
+        return fjsp_internal_fail("fjsp_a2c_actor_head_ppo: null buffer");
+    const size_t S = (size_t)T * (size_t)n;
+    hipLaunchKernelGGL(k_actor_head_ppo, dim3((unsigned)((S + 255) / 256), NAG), dim3(256), 0, (hipStream_t)stream, pu,
+                       umax, inv, T, n, masks, actions, adv, adv_mean, adv_std, logp_old, logp_out, clip_eps, inv_count,
+                       ent_coef, grad, sums);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) {
         fjsp_internal_fail(hipGetErrorString(err));
