@@ -26,6 +26,8 @@
  *   fjsp_read_env    <- FJSPSimulation.get_order_progress   FJSPSimulation.py:260-284
  *                       + agv.position / agv.carrying_tray / current_step (a2c.py:298-376)
  *   fjsp_episode_scan <- MultiAgentA2C.learn episode tracking a2c.py:311-313,346-376
+ *   fjsp_kpi_scan    <- MultiAgentA2C.test's infos tracking a2c.py:612-615, the agents' result
+ *                       dicts and FJSPSimulation.get_order_progress, per finished episode
  *
  * Python binding (ctypes) lives in multi-agent-rl-for-fjsp_amd/_native.py; see INTEGRATION.md.
  */
@@ -321,6 +323,75 @@ int fjsp_episode_scan(const double* rewards,            /* f64 [T][8][N] */
                       fjsp_episode_rec* recs, int64_t cap,
                       int64_t* count,  /* device i64 [1]: episodes finished so far; read and advanced on the device */
                       void* temp, uint64_t temp_bytes, void* stream);
+
+/* ---- shop-floor KPIs over a rollout slab (ABI 14 addition) ----
+ * One record per finished episode, reduced from what every full fjsp_out already carries: the
+ * action-result words (each agent's result dict, e.g. AGVAgent's 'moved' / 'distance' /
+ * 'invalid_action', MachineAgent.py:106-112, PackagingAgent's 'products_completed_this_step'),
+ * the stations' is_busy / queue_length observations, infos['orders_completed'] /
+ * ['total_products_packaged'] (a2c.py:612-615; FJSPSimulation.get_order_progress's
+ * 'completed_orders' / 'products_packaged') and infos['sim_time'].  No per-kind interpretation:
+ * spec.RESULT_KEYS names the agent columns in Python. */
+#define FJSP_KPI_REC_BYTES 432   /* sizeof(fjsp_kpi_rec) = 27 x 16 */
+/* When a monotone infos counter rose.  l = the step's 1-based index within its episode, d = the
+ * counter at this step minus its value at the episode's previous step (0 before the first step;
+ * every order is in the queue at reset).  Where d > 0: first_step = l if still 0, last_step = l,
+ * step_sum += d * l.  Mean flow time = step_sum / counter * step_size. */
+typedef struct fjsp_kpi_times {
+    int32_t first_step;
+    int32_t last_step;
+    int64_t step_sum;
+} fjsp_kpi_times;
+typedef struct fjsp_kpi_rec {
+    /* the first 40 bytes of fjsp_episode_rec: same fields, meaning and values */
+    uint32_t env_gid;
+    int32_t  length;
+    int64_t  end_step;
+    uint64_t seq;
+    int32_t  flags;
+    int32_t  orders_completed; /* a2c.py:614 at the last step; -1 if the slab was not given */
+    int32_t  packaged;         /* a2c.py:615 likewise */
+    int32_t  reserved;         /* 0 */
+    double   makespan;         /* infos['sim_time'] at the episode's last step; NaN if not given */
+    fjsp_kpi_times orders;     /* from orders_completed; all 0 if not given */
+    fjsp_kpi_times products;   /* from packaged; all 0 if not given */
+    /* per agent a: [0..5] steps with bit 0..5 of results[t][a][e] set, [6] steps with bit 7
+     * (executed) set, [7] sum of bits 16..31 (the AGV's 'distance', a packaging station's
+     * 'products_completed_this_step'); all 0 if results was not given */
+    int32_t  agents[8][8];
+    /* per station s (agent s + 2), from the post-step obs_i8 rows 2s (is_busy) and 2s + 1
+     * (queue_length): steps with is_busy != 0, sum and maximum (from 0) of queue_length, 0 */
+    int32_t  stations[6][4];
+} fjsp_kpi_rec;
+
+/* int32 words per env of fjsp_kpi_scan's carry (host-only). */
+int fjsp_kpi_carry_words(void);
+/* The scan.  Per env, t = 0..T-1 in order, the counters above advance (int32, two's-complement
+ * adds); where term | trunc is set at (t, e) the record is written and the env's carry returns to
+ * all zero.  carry: i32 [fjsp_kpi_carry_words()][N] in/out, the open episode's counters, all zero =
+ * a fresh episode; written back at the end of the slab, so the next slab continues it.  results,
+ * obs_i8, orders_completed, packaged and sim_time may each be NULL, independently.  A slab that is
+ * NULL counts as all zeros for this call's rows (and gives -1 / NaN in the head of the records the
+ * call writes): an episode that is open across calls of which only some give a slab accumulates
+ * the given rows, and an infos counter's previous value is 0 after a call without its slab.
+ * Ordering and
+ * capacity are exactly fjsp_episode_scan's (the same count and offsets kernels over the same
+ * flags): episode k of the slab in row-major (t, then e) order gets seq = count_in + k, is written
+ * only if seq < cap, and *count advances by every episode of the slab.  Consequence: scanning the
+ * same slabs into an episode log and a KPI log from the same starting state makes record k of
+ * each describe the same episode, their first 40 bytes equal.  temp is sized by
+ * fjsp_episode_temp_bytes(T, N); recs and temp 16-byte aligned; recs may be NULL when cap == 0.
+ * Three launches ordered by the stream alone.  Stream-ordered. */
+int fjsp_kpi_scan(const uint32_t* results,              /* u32 [T][8][N] or NULL */
+                  const uint8_t* term, const uint8_t* trunc,              /* u8 [T][N] */
+                  const int8_t* obs_i8,                 /* int8 [T][12][N] or NULL */
+                  const int32_t* orders_completed, const int32_t* packaged, /* i32 [T][N] or NULL */
+                  const double* sim_time,               /* f64 [T][N] or NULL */
+                  int32_t T, int32_t N, uint32_t env_gid0, int64_t step0,
+                  int32_t* carry,  /* i32 [words][N] in/out */
+                  fjsp_kpi_rec* recs, int64_t cap,
+                  int64_t* count,  /* device i64 [1], read and advanced on the device */
+                  void* temp, uint64_t temp_bytes, void* stream);
 
 /* Synchronous host copy of one env's state summary (debug / facade use). */
 int fjsp_read_env(fjsp_handle* h, int32_t env, fjsp_env_view* out);

@@ -1701,6 +1701,85 @@ class VecMultiAgentA2C:
             res["actions"] = np.stack(acts) if acts else np.zeros((0, NA, N), np.uint8)
         return res
 
+    @torch.no_grad()
+    def evaluate_kpis(self, num_orders=5, steps=500, seeds=None, deterministic=True, env=None, chunk=64,
+                      trace=False):
+        """The learned policy over `steps` vector steps from a reset with auto-reset (an env starts
+        its next episode at once), every finished episode accounted twice on the device: returns
+        and lengths (episodes.EpisodeLog) and the shop-floor KPIs (kpis.KpiLog: makespan, flow
+        times, station utilisation, queues, AGV distance, invalid actions; kpis.kpi_summary).
+        Per vector step: the policy kernel (policy_fused, or policy), then fjsp_step with
+        auto-reset writing row t of a [chunk]-row slab (rewards, flags, result words, the stations'
+        int8 observations, infos, sim_time) and the post-reset observation's features / masks the
+        next step acts on; every full chunk is scanned into both logs.  Returns {"episodes":
+        EpisodeLog.pop(), "kpis": KpiLog.pop()} (+ "trace": host copies of the scanned slabs and
+        the actions, with trace).  Runs on `env` or, by default, on the training env, which is
+        reset afterwards with the training num_orders as test() does.  The sampling key, the
+        rollout slab, the networks and the optimisers are not touched.
+
+        KPIs of the training rollouts are not available: the fused collect (fjsp_a2c_policy_step)
+        has no result-word output, and track_episodes is unchanged."""
+        from .episodes import EpisodeLog
+        from .kpis import KpiLog
+        on_train = env is None or env is self.env
+        env = self.env if env is None else env
+        N, dev = env.num_envs, self.device
+        steps, C = int(steps), max(1, min(int(chunk), int(steps)))
+        z = lambda *s, dt: torch.zeros(*s, dtype=dt, device=dev)  # noqa: E731
+        s = {"feats": z(C + 1, GLOBAL_DIM, N, dt=torch.float32), "masks": z(C + 1, 29, N, dt=torch.int8),
+             "actions": z(C, NA, N, dt=torch.uint8), "rewards": z(C, NA, N, dt=torch.float64),
+             "term": z(C, N, dt=torch.uint8), "trunc": z(C, N, dt=torch.uint8), "status": z(C, N, dt=torch.int32),
+             "results": z(C, NA, N, dt=torch.int32), "obs_i8": z(C, 12, N, dt=torch.int8),
+             "orders_completed": z(C, N, dt=torch.int32), "packaged": z(C, N, dt=torch.int32),
+             "sim_time": z(C, N, dt=torch.float64)}
+        outs = []
+        for t in range(C):   # per-row output structs, as _alloc builds them
+            o = nat.fjsp_out()
+            for k in ("rewards", "term", "trunc", "status", "results", "obs_i8", "orders_completed", "packaged",
+                      "sim_time"):
+                setattr(o, k, s[k][t].data_ptr())
+            o.next_masks = s["masks"][t + 1].data_ptr()
+            o.feats = s["feats"][t + 1].data_ptr()
+            outs.append(o)
+        val = z(N, dt=torch.float32)
+        cap = max(65536, N * (steps // 16 + 1))
+        log = EpisodeLog(N, dev, env_id_base=env.env_id_base, capacity=cap)
+        kpi = KpiLog(N, dev, env_id_base=env.env_id_base, capacity=cap)
+        env.reset(seeds=seeds, num_orders=num_orders)
+        env.pack_a2c(s["feats"][0], s["masks"][0])
+        keep = {k: [] for k in s if k not in ("feats", "masks", "status")} if trace else None
+        L, h = nat.lib(), env.handle
+        done = 0
+        while done < steps:
+            k = min(C, steps - done)
+            # fjsp_step is called directly (the per-row output structs), so what env.step does first is
+            # done here: the handle follows the current torch stream, which the policy and the scans use
+            env._sync_stream()
+            for t in range(k):
+                if self.fused_policy:
+                    self.policy_fused(s["feats"][t], s["masks"][t], done + t, deterministic, s["actions"][t], val,
+                                      gid0=env.env_id_base)
+                else:
+                    s["actions"][t].copy_(self.policy(s["feats"][t], s["masks"][t], deterministic, t=done + t,
+                                                      gid0=env.env_id_base)[0])
+                nat.check(L.fjsp_step(h, ctypes.c_void_p(s["actions"][t].data_ptr()), None, 1, ctypes.byref(outs[t])))
+            log.scan(s["rewards"][:k], s["term"][:k], s["trunc"][:k], s["orders_completed"][:k], s["packaged"][:k])
+            kpi.scan(s["results"][:k], s["term"][:k], s["trunc"][:k], s["obs_i8"][:k], s["orders_completed"][:k],
+                     s["packaged"][:k], s["sim_time"][:k])
+            if trace:
+                for name in keep:
+                    keep[name].append(s[name][:k].cpu().numpy().copy())
+            s["feats"][0].copy_(s["feats"][k])
+            s["masks"][0].copy_(s["masks"][k])
+            done += k
+        res = {"episodes": log.pop(), "kpis": kpi.pop()}
+        if trace:
+            import numpy as np
+            res["trace"] = {name: np.concatenate(v) for name, v in keep.items()}
+        if on_train and self._bufs is not None:
+            self.reset(num_orders=getattr(self, "num_orders", 25))
+        return res
+
     # ------------------------------------------------------------ checkpoints (a2c.py:733-775)
     def state_dicts(self):
         return {

@@ -1,4 +1,5 @@
-// fjsp_episode.hip — episode accounting over a rollout slab (include/fjsp.h: fjsp_episode_scan).
+// fjsp_episode.hip — episode accounting over a rollout slab (include/fjsp.h: fjsp_episode_scan) and,
+// further down, the shop-floor KPIs of the same episodes (fjsp_kpi_scan).
 //
 // MultiAgentA2C.learn's per-episode bookkeeping (a2c.py:311-313 episode_rewards[agent] += reward,
 // :346-350 total = sum(episode_rewards.values()), episode_end_timesteps, :373 the printed steps)
@@ -22,6 +23,7 @@
 // The arithmetic is one fp64 add per (step, agent) and the left-to-right sum of the eight, in the
 // reference's order; the library is built with -ffp-contract=off.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/fjsp.h"
@@ -240,6 +242,263 @@ __global__ void __launch_bounds__(64 * EP_A) k_episode_scan(const double* __rest
     else ep_body<true>(r, flags, offs, p, W, accp, lenp, sh);
 }
 
+// ---- shop-floor KPIs (include/fjsp.h: fjsp_kpi_scan) -------------------------------------------
+// The same three launches with k_kpi_scan in k_episode_scan's place: one workgroup of 8 waves per
+// 64 envs, wave a = agent a's eight result counters of the 64 envs (one lane per env), forward
+// over t, EP_U rows per load batch with the next batch issued before the scan.  Waves 0 and 1 also
+// follow one infos counter each (orders_completed / packaged -> the completion-time blocks); wave 0
+// writes the record's first 32 bytes (up to orders_completed), wave 1, which holds packaged, the
+// next 16 (packaged, reserved, makespan: it also batches sim_time); waves 2..7 read their station's
+// two obs_i8 rows.  Every wave reads the same flag words and offsets, so every wave derives the
+// same rank by itself and stores only its own 16-byte segments of the record: no LDS, no barrier,
+// no atomic.  Nothing is loaded at an episode's end (vmcnt retires in order, so such a load would
+// wait for the whole next batch already in flight), and no load sits behind a branch.
+// What makes the missing barrier safe: no word of global memory that one wave writes is read or
+// written by another wave of the launch.  Every carry word and every 16-byte record segment has
+// exactly one owner wave (the inputs, flags and offsets are read-only here).  That is why the open
+// episode's length is carried twice: waves 0 and 1 both need it (the head's length, the step index
+// l of both completion-time blocks), and each reads and writes a word of its own, so wave 1's read
+// at its start cannot meet wave 0's write at its end.  The station waves need no length.
+constexpr int KPI_C_LEN = 0;         // carry words [KPI_WORDS][N]: steps of the open episode, wave 0's copy
+constexpr int KPI_C_TIMES = 1;       // + 5 i: first, last, step_sum lo / hi, previous value (i = 0 orders, 1 products)
+constexpr int KPI_C_AGENTS = 11;     // + 8 a + k
+constexpr int KPI_C_STATIONS = 75;   // + 3 s + {busy_steps, queue_sum, queue_max}
+constexpr int KPI_C_LEN1 = 93;       // steps of the open episode, wave 1's copy (equal to word 0)
+constexpr int KPI_WORDS = 94;
+constexpr int KPI_Q_TIMES = 3, KPI_Q_AGENTS = 5, KPI_Q_STATIONS = 21;   // record segments, in 16 bytes
+
+static_assert(sizeof(fjsp_kpi_rec) == FJSP_KPI_REC_BYTES && FJSP_KPI_REC_BYTES % 16 == 0, "fjsp_kpi_rec is 27 x 16 bytes");
+static_assert(offsetof(fjsp_kpi_rec, makespan) == 40 && offsetof(fjsp_episode_rec, total) == 40, "shared 40-byte head");
+static_assert(offsetof(fjsp_kpi_rec, orders) == 16 * KPI_Q_TIMES && offsetof(fjsp_kpi_rec, agents) == 16 * KPI_Q_AGENTS &&
+                  offsetof(fjsp_kpi_rec, stations) == 16 * KPI_Q_STATIONS, "record segments");
+
+struct KpiArgs {
+    const uint32_t* res;
+    const int8_t* obs;
+    const int32_t* oc;
+    const int32_t* pk;
+    const double* st;
+    fjsp_kpi_rec* recs;
+    int32_t* carry;
+    long long cap, base, step0;
+    uint32_t gid0;
+    int T, N;
+};
+
+struct KpiChunk {
+    uint32_t word[EP_U];
+    int32_t x[EP_U], y[EP_U];   // station waves: is_busy, queue_length; waves 0 / 1: the infos counter, -
+    double st[EP_U];            // wave 1: sim_time
+    uint32_t off[EP_U];
+    uint32_t f;
+};
+
+struct KpiState {
+    uint32_t c[8];
+    uint32_t busy, qsum;
+    int32_t qmax;
+    int32_t len, first, last, prev;
+    unsigned long long sum;
+};
+
+// What one wave loads per row, wave-uniform: a base, a row stride and the lane's byte offset.  A slab
+// that was not given reads the first words of the flag table instead (stride and lane offset 0) and
+// is masked to 0: no branch around a load, so no load's first use can move up to the load.
+struct KpiRows {
+    const char* res;   // the agent's result words, u32
+    const char* aux;   // station waves: is_busy bytes (queue_length `queue` bytes on); waves 0 / 1: the infos counter, i32
+    const char* st;    // wave 1: sim_time, f64
+    size_t res_stride, aux_stride, st_stride, queue;
+    uint32_t res_lane, aux_lane, st_lane;
+    uint32_t res_mask;
+    int32_t aux_mask;
+};
+
+// Rows t0 .. t0 + EP_U - 1 (rows past the slab clamped to its last row: never used).  ROLE 0 / 1 /
+// 2 = wave 0 / wave 1 / a station wave.
+template <int ROLE>
+__device__ __forceinline__ void kpi_load(KpiChunk& c, const KpiRows& r, const uint32_t* __restrict__ flags,
+                                         const uint32_t* __restrict__ offs, int t0, int T, int W, uint32_t e, int w) {
+    const int ch = (t0 < T ? t0 : T - 1) / EP_U;
+    c.f = flags[(size_t)ch * ((size_t)W * 64) + e];
+#pragma unroll
+    for (int j = 0; j < EP_U; j++) {
+        const size_t t = (size_t)(t0 + j < T ? t0 + j : T - 1);
+        c.off[j] = offs[t * W + w];
+        // scalar row base + the lane's 32-bit byte offset
+        c.word[j] = *reinterpret_cast<const uint32_t*>(r.res + t * r.res_stride + r.res_lane) & r.res_mask;
+        const char* __restrict__ ax = r.aux + t * r.aux_stride;
+        if (ROLE == 2) {
+            c.x[j] = (int32_t)(*reinterpret_cast<const int8_t*>(ax + r.aux_lane)) & r.aux_mask;
+            c.y[j] = (int32_t)(*reinterpret_cast<const int8_t*>(ax + r.queue + r.aux_lane)) & r.aux_mask;
+        } else {
+            c.x[j] = *reinterpret_cast<const int32_t*>(ax + r.aux_lane) & r.aux_mask;
+            c.y[j] = 0;
+        }
+        c.st[j] = 0.0;
+        if (ROLE == 1) c.st[j] = *reinterpret_cast<const double*>(r.st + t * r.st_stride + r.st_lane);
+    }
+}
+
+template <int ROLE>
+__device__ __forceinline__ void kpi_scan(const KpiChunk& c, int t0, const KpiArgs& p, int a, int e, int lane,
+                                         KpiState& s) {
+    const int rows = min(EP_U, p.T - t0);
+#pragma unroll
+    for (int j = 0; j < EP_U; j++) {
+        if (j < rows) {   // wave-uniform
+            const uint32_t wd = c.word[j];
+            s.len += 1;
+#pragma unroll
+            for (int k = 0; k < 6; k++) s.c[k] += (wd >> k) & 1u;
+            s.c[6] += (wd >> 7) & 1u;
+            s.c[7] += wd >> 16;
+            if (ROLE == 2) {
+                s.busy += c.x[j] != 0 ? 1u : 0u;
+                s.qsum += (uint32_t)c.y[j];
+                s.qmax = max(s.qmax, c.y[j]);
+            } else {
+                const long long d = (long long)c.x[j] - (long long)s.prev;
+                if (d > 0) {
+                    if (s.first == 0) s.first = s.len;
+                    s.last = s.len;
+                    s.sum += (unsigned long long)d * (unsigned long long)s.len;
+                }
+                s.prev = c.x[j];
+            }
+        }
+        const uint32_t fj = (c.f >> (2 * j)) & 3u;   // never set past the slab
+        const uint64_t b = __ballot(fj != 0);
+        if (fj != 0) {
+            const long long seq = p.base + (long long)c.off[j] + lanes_below(b, lane);
+            if ((unsigned long long)seq < (unsigned long long)p.cap) {
+                uint4* q = reinterpret_cast<uint4*>(p.recs + seq);
+                if (ROLE != 2) {
+                    // the 48 bytes in front: wave 0 the 32 that end with orders_completed, wave 1 the 16
+                    // of packaged and makespan; each from its own batch (a load issued here would
+                    // have to wait for the whole batch in flight behind it)
+                    if (ROLE == 0) {
+                        const int oc = p.oc ? c.x[j] : -1;
+                        const long long end = p.step0 + (long long)(t0 + j) + 1;
+                        q[0] = make_uint4(p.gid0 + (uint32_t)e, (uint32_t)s.len, (uint32_t)end,
+                                          (uint32_t)((unsigned long long)end >> 32));
+                        q[1] = make_uint4((uint32_t)seq, (uint32_t)((unsigned long long)seq >> 32), fj, (uint32_t)oc);
+                    } else {
+                        const int pk = p.pk ? c.x[j] : -1;
+                        const unsigned long long mk =
+                            p.st ? (unsigned long long)__double_as_longlong(c.st[j]) : 0x7FF8000000000000ull;
+                        q[2] = make_uint4((uint32_t)pk, 0u, (uint32_t)mk, (uint32_t)(mk >> 32));
+                    }
+                    q[KPI_Q_TIMES + a] = make_uint4((uint32_t)s.first, (uint32_t)s.last, (uint32_t)s.sum,
+                                                    (uint32_t)(s.sum >> 32));
+                } else {
+                    q[KPI_Q_STATIONS + a - 2] = make_uint4(s.busy, s.qsum, (uint32_t)s.qmax, 0u);
+                }
+                q[KPI_Q_AGENTS + 2 * a] = make_uint4(s.c[0], s.c[1], s.c[2], s.c[3]);
+                q[KPI_Q_AGENTS + 2 * a + 1] = make_uint4(s.c[4], s.c[5], s.c[6], s.c[7]);
+            }
+            s = KpiState{};
+        }
+    }
+}
+
+template <int ROLE>
+__device__ __forceinline__ void kpi_body(const uint32_t* __restrict__ flags, const uint32_t* __restrict__ offs,
+                                         const KpiArgs& p, int W, int w, int a) {
+    const int lane = threadIdx.x & 63;
+    const int e = w * 64 + lane;
+    const int T = p.T;
+    const size_t N = (size_t)p.N, col = (size_t)w * 64;
+    const bool live = e < p.N;
+    // lanes e >= N load their workgroup's last env's column; their flag words are 0 (temp's padded
+    // rows), so they end no episode, and their carry is neither read nor written
+    const uint32_t ll = (uint32_t)min(lane, p.N - w * 64 - 1);
+    const char* none = reinterpret_cast<const char*>(flags);
+    const int32_t* info = ROLE == 0 ? p.oc : p.pk;
+    KpiRows r;
+    r.res = p.res ? reinterpret_cast<const char*>(p.res + (size_t)a * N + col) : none;
+    r.res_stride = p.res ? (size_t)EP_A * N * 4 : 0;
+    r.res_lane = p.res ? ll * 4u : 0u;
+    r.res_mask = p.res ? ~0u : 0u;
+    if (ROLE == 2) {
+        r.aux = p.obs ? reinterpret_cast<const char*>(p.obs + (size_t)(2 * (a - 2)) * N + col) : none;
+        r.aux_stride = p.obs ? (size_t)FJSP_OBS_I8 * N : 0;
+        r.queue = p.obs ? N : 0;
+        r.aux_lane = p.obs ? ll : 0u;
+        r.aux_mask = p.obs ? -1 : 0;
+    } else {
+        r.aux = info ? reinterpret_cast<const char*>(info + col) : none;
+        r.aux_stride = info ? N * 4 : 0;
+        r.queue = 0;
+        r.aux_lane = info ? ll * 4u : 0u;
+        r.aux_mask = info ? -1 : 0;
+    }
+    const bool has_st = ROLE == 1 && p.st;
+    r.st = has_st ? reinterpret_cast<const char*>(p.st + col) : none;
+    r.st_stride = has_st ? N * 8 : 0;
+    r.st_lane = has_st ? ll * 8u : 0u;
+    int32_t* __restrict__ cy = p.carry + e;   // word k of this env: cy[k * N]
+    const int ca = KPI_C_AGENTS + 8 * a, cs = KPI_C_STATIONS + 3 * (a - 2), ct = KPI_C_TIMES + 5 * a;
+    const int cl = ROLE == 0 ? KPI_C_LEN : KPI_C_LEN1;   // each of the two waves its own word (see above)
+    KpiState s{};
+    if (live) {
+        if (ROLE != 2) s.len = cy[(size_t)cl * N];
+#pragma unroll
+        for (int k = 0; k < 8; k++) s.c[k] = (uint32_t)cy[(size_t)(ca + k) * N];
+        if (ROLE == 2) {
+            s.busy = (uint32_t)cy[(size_t)cs * N];
+            s.qsum = (uint32_t)cy[(size_t)(cs + 1) * N];
+            s.qmax = cy[(size_t)(cs + 2) * N];
+        } else {
+            s.first = cy[(size_t)ct * N];
+            s.last = cy[(size_t)(ct + 1) * N];
+            s.sum = (unsigned long long)(uint32_t)cy[(size_t)(ct + 2) * N] |
+                    ((unsigned long long)(uint32_t)cy[(size_t)(ct + 3) * N] << 32);
+            s.prev = cy[(size_t)(ct + 4) * N];
+        }
+    }
+    KpiChunk A, B;
+    int t0 = 0;
+    kpi_load<ROLE>(A, r, flags, offs, 0, T, W, (uint32_t)e, w);
+    for (;;) {   // A holds t0.., B is loaded before A's scan, and the other way round
+        kpi_load<ROLE>(B, r, flags, offs, t0 + EP_U, T, W, (uint32_t)e, w);
+        kpi_scan<ROLE>(A, t0, p, a, e, lane, s);
+        t0 += EP_U;
+        if (t0 >= T) break;
+        kpi_load<ROLE>(A, r, flags, offs, t0 + EP_U, T, W, (uint32_t)e, w);
+        kpi_scan<ROLE>(B, t0, p, a, e, lane, s);
+        t0 += EP_U;
+        if (t0 >= T) break;
+    }
+    if (live) {
+        if (ROLE != 2) cy[(size_t)cl * N] = s.len;
+#pragma unroll
+        for (int k = 0; k < 8; k++) cy[(size_t)(ca + k) * N] = (int32_t)s.c[k];
+        if (ROLE == 2) {
+            cy[(size_t)cs * N] = (int32_t)s.busy;
+            cy[(size_t)(cs + 1) * N] = (int32_t)s.qsum;
+            cy[(size_t)(cs + 2) * N] = s.qmax;
+        } else {
+            cy[(size_t)ct * N] = s.first;
+            cy[(size_t)(ct + 1) * N] = s.last;
+            cy[(size_t)(ct + 2) * N] = (int32_t)(uint32_t)s.sum;
+            cy[(size_t)(ct + 3) * N] = (int32_t)(uint32_t)(s.sum >> 32);
+            cy[(size_t)(ct + 4) * N] = s.prev;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(64 * EP_A) k_kpi_scan(const uint32_t* __restrict__ flags,
+                                                        const uint32_t* __restrict__ offs,
+                                                        const long long* __restrict__ base, KpiArgs p, int W) {
+    p.base = base[0];
+    const int w = (int)blockIdx.x;
+    const int a = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (a == 0) kpi_body<0>(flags, offs, p, W, w, a);
+    else if (a == 1) kpi_body<1>(flags, offs, p, W, w, a);
+    else kpi_body<2>(flags, offs, p, W, w, a);
+}
+
 // temp: the offsets table u32 [T][W] (padded to 16 bytes), 16 bytes for the count at entry, the
 // flag words u32 [ceil(T / EP_U)][64 W]
 bool ep_temp_layout(int32_t T, int32_t N, uint64_t* table, uint64_t* total) {
@@ -298,6 +557,54 @@ int fjsp_episode_scan(const double* rewards, const uint8_t* term, const uint8_t*
     p.N = N;
     hipLaunchKernelGGL(k_episode_scan, dim3((unsigned)W), dim3(64 * EP_A), 0, st, rewards, flags, offs, base, p, W,
                        acc, len);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        fjsp_internal_fail(hipGetErrorString(e));
+        return -2;
+    }
+    return 0;
+}
+
+int fjsp_kpi_carry_words(void) { return KPI_WORDS; }
+
+int fjsp_kpi_scan(const uint32_t* results, const uint8_t* term, const uint8_t* trunc, const int8_t* obs_i8,
+                  const int32_t* orders_completed, const int32_t* packaged, const double* sim_time, int32_t T,
+                  int32_t N, uint32_t env_gid0, int64_t step0, int32_t* carry, fjsp_kpi_rec* recs, int64_t cap,
+                  int64_t* count, void* temp, uint64_t temp_bytes, void* stream) {
+    if (T <= 0 || N <= 0) return fjsp_internal_fail("fjsp_kpi_scan: T and N must be > 0");
+    if (cap < 0) return fjsp_internal_fail("fjsp_kpi_scan: cap must be >= 0");
+    if (!term || !trunc || !carry || !count || !temp || (cap > 0 && !recs))
+        return fjsp_internal_fail("fjsp_kpi_scan: null buffer");
+    uint64_t table, total;
+    if (!ep_temp_layout(T, N, &table, &total)) return fjsp_internal_fail("fjsp_kpi_scan: T * N must be < 2^31");
+    if (temp_bytes < total) return fjsp_internal_fail("fjsp_kpi_scan: temp buffer too small");
+    if ((((uintptr_t)recs | (uintptr_t)temp) & 15u) != 0)
+        return fjsp_internal_fail("fjsp_kpi_scan: recs and temp must be 16-byte aligned");
+    const int W = (int)(((int64_t)N + 63) / 64);   // T W 64 < 2^31 (checked above)
+    const int L = T * W;
+    uint32_t* offs = (uint32_t*)temp;
+    long long* base = (long long*)((char*)temp + table);
+    uint32_t* flags = (uint32_t*)((char*)temp + table + 16);
+    const hipStream_t st = (hipStream_t)stream;
+    const long long waves = (long long)W * ((T + EP_U - 1) / EP_U);
+    hipLaunchKernelGGL(k_episode_count, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, term, trunc, T, N, W, offs,
+                       flags);
+    hipLaunchKernelGGL(k_episode_offsets, dim3(1), dim3(EPO_THREADS), 0, st, offs, L, base, (long long*)count);
+    KpiArgs p;
+    p.res = results;
+    p.obs = obs_i8;
+    p.oc = orders_completed;
+    p.pk = packaged;
+    p.st = sim_time;
+    p.recs = recs;
+    p.carry = carry;
+    p.cap = cap;
+    p.base = 0;
+    p.step0 = step0;
+    p.gid0 = env_gid0;
+    p.T = T;
+    p.N = N;
+    hipLaunchKernelGGL(k_kpi_scan, dim3((unsigned)W), dim3(64 * EP_A), 0, st, flags, offs, base, p, W);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fjsp_internal_fail(hipGetErrorString(e));

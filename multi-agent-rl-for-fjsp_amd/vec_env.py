@@ -259,6 +259,31 @@ class FJSPVecEnv:
             done += k
         return log.pop()
 
+    def evaluate_kpis(self, policy="heuristic", num_orders=5, steps=500, seeds=None, action_seed=0, chunk=256):
+        """evaluate_episodes with the shop-floor KPIs beside the returns: the same loop, each chunk
+        scanned into an EpisodeLog and a kpis.KpiLog (fjsp_kpi_scan over the chunk's result words,
+        the stations' int8 observations, the infos and sim_time).  Returns {"episodes":
+        EpisodeLog.pop(), "kpis": KpiLog.pop()}; record k of each describes the same episode
+        (kpis.kpi_summary derives makespan, flow times, utilisation, ... from "kpis").  Only the
+        records reach the host."""
+        from .episodes import EpisodeLog
+        from .kpis import KpiLog
+        steps, chunk = int(steps), max(1, min(int(chunk), int(steps)))
+        self.reset(seeds=seeds, num_orders=num_orders)
+        cap = max(65536, self.num_envs * (steps // 16 + 1))   # as evaluate_episodes
+        log = EpisodeLog(self.num_envs, self.device, env_id_base=self.env_id_base, capacity=cap)
+        kpi = KpiLog(self.num_envs, self.device, env_id_base=self.env_id_base, capacity=cap)
+        b = Buffers(chunk, self.num_envs, self.device, infos=True)
+        done = 0
+        while done < steps:
+            k = min(chunk, steps - done)
+            self.rollout(k, action_seed=action_seed, step0=done, policy=policy, autoreset=True, buffers=b)
+            log.scan(b.rewards[:k], b.term[:k], b.trunc[:k], b.orders_completed[:k], b.packaged[:k])
+            kpi.scan(b.results[:k], b.term[:k], b.trunc[:k], b.obs_i8[:k], b.orders_completed[:k], b.packaged[:k],
+                     b.sim_time[:k])
+            done += k
+        return {"episodes": log.pop(), "kpis": kpi.pop()}
+
     def pack_a2c(self, feats=None, masks=None):
         """a2c features f32 [38, N] and masks int8 [29, N] of the current observations
         (MultiAgentA2C._get_global_state, a2c.py:153-166)."""
