@@ -519,99 +519,140 @@ FJSP_DEV uint32_t agv_execute(Env& E, const Tables& T, const Cfg& C, int action,
 // while it is non-empty (the pickup station and the machines only append; only the AGV pops).
 // agv_fin completes the step on the final list words (after the pickup station's action and the
 // machines' actions of the previous step).  Together they equal agv_execute<true>.
+//
+// The split puts everything that is a function of the AGV's own words, the action and the
+// prefetched front into agv_pre: the wave that runs it waits for the other agents' posts between
+// the two halves, and what agv_fin executes after that wait is step latency.  agv_pre leaves
+//   * the one list operation of the lane as data: an all-ones mask on the list word (W7..W12)
+//     it pops or pushes, and the new word as ((lw + delta) & keep) | orb with one edge value;
+//   * both candidates of the AGV word and of the finished result word (result | action << 8):
+//     [1] the PICKUP succeeded on the prefetched front, [0] it did not; on every other action the
+//     outcome is already known and both hold it.  The move's target is folded into the AGV word
+//     (the move always lands inside the run), so the pair equals agv_execute<true> followed by
+//     `if (move_to) set_loc(move_to)`;
+//   * the drop's packaging half (pend), the tray pool's increment and the status bits.
+// agv_fin selects the lane's list word, resolves its length and picks.  Lane predicates are
+// data in VGPRs (masks, thresholds compared with the length), not lane masks in SGPR pairs
+// that would stay live across the wait.
+// The DROP's `snext[carry] = NIL` is stored by agv_pre: the carried slot left its list when
+// the AGV picked it up and joins one only through this drop, so between the two halves no list
+// of any agent holds it — the pickup station links new slots and its own tail, the machines
+// their queue fronts and current trays, the packaging stations their runs — and nobody reads
+// or writes that byte until the list it joins is walked after agv_fin.
 struct AgvPre {
-    int loc, carry, code, src, dst, ml, d, action;
-    bool want6, is_move, moved, ok7, at_pick, at_store, at_pack, store_full;
-    uint32_t pre_len, pnext, pcode, pow;
+    uint32_t m[6];               // all-ones on the list word (W7 + i) this lane pops or pushes
+    uint32_t lw_own;             // W8 & m[1]: the storage list is the AGV's own
+    uint32_t delta, keep, orb;   // the list word after the operation, unless
+    uint32_t edge_len, edge_val; //   len <= edge_len: edge_val (pop of the last tray, push on an empty list)
+    uint32_t force;              // 0 on a PICKUP lane (it succeeds iff len != 0), 1 elsewhere
+    uint32_t thr;                // len above it needs a table access: PICKUP with 0 / 1 trays prefetched: that
+                                 // count (the front or its successor is new); DROP that pushes: 0 (link the
+                                 // old tail); ~0 elsewhere
+    uint32_t w6[2], r[2];        // AGV word / result | action << 8: [0] pickup failed, [1] succeeded
+    uint32_t pend, pool_add, st; // deferred packaging drop, pool increment (<< 8, W5), status bits
+    uint32_t carry;
+    int ml;
+    bool moved;
 };
+// the AGV word after a PICKUP of slot ps (tray code scode of order word ow) at location bits loc3
+FJSP_DEV uint32_t agv_carried(uint32_t loc3, uint32_t ps, uint32_t scode, uint32_t ow) {
+    const uint32_t rg = tc_range((int)scode);
+    const bool full6 = tc_count((int)scode) > 0;
+    return loc3 | (ps << 3) | (scode << 11) |
+           (full6 ? (((uint32_t)ow_type(ow) << 24) | ((uint32_t)ow_color(ow) << 26) |
+                     ((uint32_t)((ow & rg) != rg) << 28) | ((uint32_t)(((ow >> 9) & rg) != rg) << 29))
+                  : 0u);
+}
 FJSP_DEV AgvPre agv_pre(const Env& E, const Tables& T, const Cfg& C, int action) {
     AgvPre a;
-    a.action = action;
-    a.loc = E.loc();
-    a.carry = E.carry();
-    const bool has = a.carry != NIL;
-    a.is_move = (unsigned)(action - 1) < 5u;
+    const int loc = E.loc();
+    const int carry = E.carry();
+    const bool has = carry != NIL;
+    const bool is_move = (unsigned)(action - 1) < 5u;
     a.ml = move_loc(action);
-    a.d = manhattan(a.loc, a.ml);
-    a.moved = a.is_move && a.d != 0;
-    a.src = nib(nibs(0, L_PREADY, L_M1R, L_M0R, L_STORAGE, L_STORAGE), a.loc);
-    a.want6 = action == 6 && !has && a.loc != LOC_PACK;
-    a.code = E.carry_code();
+    const int d = manhattan(loc, a.ml);
+    a.moved = is_move && d != 0;
+    const int src = nib(nibs(0, L_PREADY, L_M1R, L_M0R, L_STORAGE, L_STORAGE), loc);
+    const bool want6 = action == 6 && !has && loc != LOC_PACK;
+    const int code = E.carry_code();
     const int ty = E.carry_type(), np = E.carry_np(), nk = E.carry_nk();
-    const uint32_t cond = ((uint32_t)(tc_count(a.code) == 0) << LOC_PICKUP) |
+    const uint32_t cond = ((uint32_t)(tc_count(code) == 0) << LOC_PICKUP) |
                           ((uint32_t)(np && (ty == 1 || ty == 2)) << LOC_SMALL) |
                           ((uint32_t)(np && (ty == 3 || ty == 2)) << LOC_BIG) | (1u << LOC_STORAGE) |
                           ((uint32_t)(nk && !np) << LOC_PACK);
-    a.ok7 = action == 7 && has && ((cond >> a.loc) & 1u);
-    a.at_pick = a.loc == LOC_PICKUP;
-    a.at_store = a.loc == LOC_STORAGE;
-    a.at_pack = a.loc == LOC_PACK;
-    a.store_full = E.ll(L_STORAGE) >= C.storage_cap;
-    const int base = nib(nibs(0xF, 0xF, L_M1Q, L_M0Q, L_STORAGE, L_PKG), a.loc);
-    const bool no_dst = base == 0xF || (a.at_store && a.store_full) || a.at_pack;
-    a.dst = no_dst ? -1 : base;
+    const bool ok7 = action == 7 && has && ((cond >> loc) & 1u);
+    const bool at_pick = loc == LOC_PICKUP, at_store = loc == LOC_STORAGE, at_pack = loc == LOC_PACK;
+    const bool store_full = E.ll(L_STORAGE) >= C.storage_cap;
+    const int base = nib(nibs(0xF, 0xF, L_M1Q, L_M0Q, L_STORAGE, L_PKG), loc);
+    const bool push = ok7 && !(base == 0xF || (at_store && store_full) || at_pack);
     // prefetch the front of the pickup source
-    const uint32_t lws = lword<PICK_LISTS>(E, a.src);
-    a.pre_len = a.want6 ? (lws >> 16) : 0u;
-    a.pnext = 0; a.pcode = 0; a.pow = 0;
-    if (a.pre_len != 0) {
-        const int ps = (int)(lws & 0xFFu);
-        a.pnext = T.snext[ps * T.stride];
-        a.pcode = T.scode[ps * T.stride];
-        a.pow = T.orders[tc_order((int)a.pcode) * T.stride];
+    const uint32_t lws = lword<PICK_LISTS>(E, src);
+    const uint32_t pre_len = want6 ? (lws >> 16) : 0u;
+    const uint32_t ps = lws & 0xFFu;
+    uint32_t pnext = 0, pcode = 0, pow = 0;
+    if (pre_len != 0) {
+        pnext = T.snext[ps * T.stride];
+        pcode = T.scode[ps * T.stride];
+        pow = T.orders[tc_order((int)pcode) * T.stride];
     }
+    if (push) T.snext[carry * T.stride] = (uint8_t)NIL;   // see above: no other agent touches the slot
+    // the list operation
+    const int li = want6 ? src : push ? base : -1;
+#pragma unroll
+    for (int i = 0; i < 6; i++) a.m[i] = li == i ? ~0u : 0u;
+    a.lw_own = E.w[7 + L_STORAGE] & a.m[L_STORAGE];
+    a.delta = want6 ? 0xFFFF0000u : 0x10000u;                     // len - 1 / len + 1
+    a.keep = want6 ? 0xFFFFFF00u : 0xFFFF00FFu;                   // new head / new tail
+    a.orb = want6 ? pnext : (uint32_t)carry << 8;
+    a.edge_len = want6 ? 1u : 0u;
+    a.edge_val = want6 ? ((uint32_t)NIL | ((uint32_t)NIL << 8)) : ((uint32_t)carry | ((uint32_t)carry << 8) | 0x10000u);
+    a.force = want6 ? 0u : 1u;
+    a.thr = (want6 && pre_len <= 1u) ? pre_len : push ? 0u : ~0u;
+    a.carry = (uint32_t)carry;
+    // AGV word: unchanged (a move lands) / empty hands / the prefetched tray
+    const uint32_t w6 = E.w[6];
+    a.w6[0] = ok7 ? ((w6 & ~(0xFFu << 3)) | ((uint32_t)NIL << 3)) : a.moved ? ((w6 & ~7u) | (uint32_t)a.ml) : w6;
+    a.w6[1] = want6 ? agv_carried(w6 & 7u, ps, pcode, pow) : a.w6[0];
+    // result: 1 success, 2 invalid, 4 moved, 8 pickup, 16 drop, 32 to packaging; 16.. distance
+    const uint32_t rc = R_EXEC | ((uint32_t)action << 8) | (a.moved ? (4u | ((uint32_t)d << 16)) : 0u) |
+                        (ok7 ? (16u | (at_pack ? 32u : 0u)) : 0u);
+    a.r[0] = rc | ((action == 0 || is_move || ok7) ? 1u : 2u);
+    a.r[1] = want6 ? (rc | 1u | 8u) : a.r[0];
+    a.pend = (ok7 && at_pack) ? (1u | ((uint32_t)carry << 1) | ((uint32_t)code << 9) | ((uint32_t)E.carry_color() << 22)) : 0u;
+    a.pool_add = (ok7 && at_pick) ? (1u << 8) : 0u;   // add_empty_tray (the pool never exceeds its 16 bits: <= pool0)
+    a.st = (ok7 && at_store && store_full) ? ST_TRAY_LOST : 0u;
     return a;
 }
 FJSP_DEV uint32_t agv_fin(Env& E, const Tables& T, const AgvPre& a, int* move_to, uint32_t* pend) {
-    const uint32_t lws = lword<PICK_LISTS>(E, a.src);
-    const uint32_t len = lws >> 16;
-    const bool ok6 = a.want6 && len != 0;
-    const int ps = (int)(lws & 0xFFu);
-    uint32_t next = a.pnext, scode = a.pcode, ow = a.pow;
-    if (ok6 && a.pre_len == 0) {   // the list was empty before: its front is new
-        next = T.snext[ps * T.stride];
-        scode = T.scode[ps * T.stride];
-        ow = T.orders[tc_order((int)scode) * T.stride];
-    } else if (ok6 && a.pre_len == 1 && len >= 2) {   // the single front got a successor: the
-        next = (lws >> 8) & 0xFFu;                      // tray pushed since (one push per list per
-    }                                                   // step: pickup, a machine's SIGNAL), the tail
-    const int carry = a.carry;
-    const bool push = a.ok7 && a.dst >= 0;
-    const uint32_t lwd = lword<DROP_LISTS>(E, a.dst);
-    if (push) {
-        T.snext[carry * T.stride] = (uint8_t)NIL;
-        if ((lwd >> 16) != 0) T.snext[((lwd >> 8) & 0xFFu) * T.stride] = (uint8_t)carry;
+    // the lane's one list word, from the final W7, W9..W12
+    const uint32_t lw = a.lw_own | (E.w[7] & a.m[0]) | (E.w[9] & a.m[2]) | (E.w[10] & a.m[3]) | (E.w[11] & a.m[4]) |
+                        (E.w[12] & a.m[5]);
+    const uint32_t len = lw >> 16;
+    const bool ok = (len | a.force) != 0;   // PICKUP: the list is not empty; every other outcome is known
+    uint32_t orb = a.orb, w6y = a.w6[1];
+    if (len > a.thr) {
+        if (a.force) {           // DROP onto a list that is not empty: link its tail
+            T.snext[((lw >> 8) & 0xFFu) * T.stride] = (uint8_t)a.carry;
+        } else if (a.thr == 0) {   // the list was empty before: its front is new
+            const uint32_t ps = lw & 0xFFu;
+            orb = T.snext[ps * T.stride];
+            const uint32_t scode = T.scode[ps * T.stride];
+            w6y = agv_carried(a.w6[0] & 7u, ps, scode, T.orders[tc_order((int)scode) * T.stride]);
+        } else {                 // the single front got a successor: the tray pushed since (one push
+            orb = (lw >> 8) & 0xFFu;   // per list per step: pickup, a machine's SIGNAL), the tail
+        }
     }
-    const uint32_t n6 = len - 1u;
-    const uint32_t popped = n6 == 0 ? ((uint32_t)NIL | ((uint32_t)NIL << 8)) : (next | (lws & 0xFF00u) | (n6 << 16));
-    const uint32_t nd = lwd >> 16;
-    const uint32_t pushed = (nd == 0 ? (uint32_t)carry : (lwd & 0xFFu)) | ((uint32_t)carry << 8) | ((nd + 1) << 16);
+    uint32_t nw = ((lw + a.delta) & a.keep) | orb;
+    nw = len <= a.edge_len ? a.edge_val : nw;
+    nw = ok ? nw : lw;
 #pragma unroll
-    for (int i = 0; i < NLIST; i++) {
-        if (!(((PICK_LISTS | DROP_LISTS) >> i) & 1u)) continue;
-        uint32_t v = E.w[7 + i];
-        if ((PICK_LISTS >> i) & 1u) v = (ok6 && a.src == i) ? popped : v;
-        if ((DROP_LISTS >> i) & 1u) v = (push && a.dst == i) ? pushed : v;
-        E.w[7 + i] = v;
-    }
-    *pend = (a.ok7 && a.at_pack) ? (1u | ((uint32_t)carry << 1) | ((uint32_t)a.code << 9) | ((uint32_t)E.carry_color() << 22)) : 0u;
-    const uint32_t rg = tc_range((int)scode);
-    const bool full6 = tc_count((int)scode) > 0;
-    const uint32_t carried = (E.w[6] & 7u) | ((uint32_t)ps << 3) | (scode << 11) |
-                             (full6 ? (((uint32_t)ow_type(ow) << 24) | ((uint32_t)ow_color(ow) << 26) |
-                                       ((uint32_t)((ow & rg) != rg) << 28) | ((uint32_t)(((ow >> 9) & rg) != rg) << 29))
-                                    : 0u);
-    const uint32_t dropped = (E.w[6] & ~(0xFFu << 3)) | ((uint32_t)NIL << 3);
-    E.w[6] = ok6 ? carried : a.ok7 ? dropped : E.w[6];
-    E.set_pool(E.pool() + ((a.ok7 && a.at_pick) ? 1 : 0));
-    E.w[2] |= (a.ok7 && a.at_store && a.store_full) ? ST_TRAY_LOST : 0u;
+    for (int i = 0; i < 6; i++) E.w[7 + i] ^= (E.w[7 + i] ^ nw) & a.m[i];   // bit-field insert under the mask
+    E.w[6] = ok ? w6y : a.w6[0];
+    E.w[5] += a.pool_add;
+    E.w[2] |= a.st;
+    *pend = a.pend;
     if (a.moved) *move_to = a.ml;
-    const bool success = a.action == 0 || a.is_move || ok6 || a.ok7;
-    uint32_t r = R_EXEC | (success ? 1u : 2u);
-    r |= a.moved ? (4u | ((uint32_t)a.d << 16)) : 0u;
-    r |= ok6 ? 8u : 0u;
-    r |= a.ok7 ? (16u | (a.at_pack ? 32u : 0u)) : 0u;
-    return r;
+    return ok ? a.r[1] : a.r[0];
 }
 
 // The packaging half of a deferred AGV drop (agv_execute<true>): route the tray to its station

@@ -1126,10 +1126,14 @@ constexpr uint32_t K_WORDS = (1u << 1) | (0xFu << 13) | (0x3FFu << 20);
 // station masks (3 per station, from field 11) emitted by E0 instead of E3: E3 arrived last at
 // the barrier in 92 % of the steps; 0 / 2 / 4 / 6 stations: 1.212 / 1.183 / 1.186 / 1.210 us per
 // step at 16 envs per workgroup (profiles/r02/experiments/e3_masks_to_e0_*.json)
-constexpr int AG_E0ST = 2;
+// Since P resolves the AGV's step ahead of its hand-offs (agv_pre / agv_fin) it is no longer the
+// last wave: E3 and E0 were (87 % / 82 % of the steps), so the AGV's move masks went from E3 to E2
+// and one of E0's two stations back to E3: 1.236 -> 1.215 ms per 1 024-step launch; none of
+// E0's stations, or one / two stations on E1: 1.234 / 1.219 / 1.225-1.255 (profiles/agv_resolve/)
+constexpr int AG_E0ST = 1;
 constexpr uint32_t AG_E0ST_BITS = ((1u << (3 * AG_E0ST)) - 1u) << 11;
-constexpr uint32_t AG_MASKS_E0 = 0x7u | AG_E0ST_BITS, AG_MASKS_E2 = 0x3u << 9,
-                   AG_MASKS_E3 = ((0x3Fu << 3) | (0x3FFFFu << 11)) & ~AG_E0ST_BITS;
+constexpr uint32_t AG_MASKS_E0 = 0x7u | AG_E0ST_BITS, AG_MASKS_E2 = (0x3u << 9) | (0x3Fu << 3),
+                   AG_MASKS_E3 = (0x3FFFFu << 11) & ~AG_E0ST_BITS;
 static_assert((AG_MASKS_E0 | AG_MASKS_E2 | AG_MASKS_E3) == (1u << NMASK) - 1u && !(AG_MASKS_E0 & AG_MASKS_E2) &&
               !(AG_MASKS_E0 & AG_MASKS_E3) && !(AG_MASKS_E2 & AG_MASKS_E3), "mask split");
 // snapshot slot words (PipeSnap, 32 per lane): AM writes q[0..3], K q[4..7]
@@ -1170,9 +1174,21 @@ __device__ __forceinline__ bool ag_fresh(int k, bool valid, const uint4 (*s_p1)[
     return autoreset && (all_done || (int)(w0a & 0xFFFFu) >= C.max_steps);
 }
 
+// Holds agv_pre's results in VGPRs at this point of P's step: without it the compiler is free to
+// sink their computation below the hand-off waits, where every instruction is step latency.
+__device__ __forceinline__ void ag_pin(AgvPre& a) {
+#define AG_PIN(x) asm volatile("" : "+v"(x))
+#pragma unroll
+    for (int i = 0; i < 6; i++) AG_PIN(a.m[i]);
+    AG_PIN(a.lw_own); AG_PIN(a.delta); AG_PIN(a.keep); AG_PIN(a.orb); AG_PIN(a.edge_len); AG_PIN(a.edge_val);
+    AG_PIN(a.force); AG_PIN(a.thr); AG_PIN(a.w6[0]); AG_PIN(a.w6[1]); AG_PIN(a.r[0]);
+    AG_PIN(a.r[1]); AG_PIN(a.pend); AG_PIN(a.pool_add); AG_PIN(a.st); AG_PIN(a.carry);
+#undef AG_PIN
+}
+
 // One emit role's outputs of step t from the step's snapshot (AM's and K's words, SA_* / SK_*):
 // E0 rewards and the pickup's masks, E1 int32 and float32 fields, E2 int8 fields, term, trunc,
-// status and the AGV's pickup / drop masks, E3 the other masks.
+// status and the AGV's masks, E3 the other masks.
 __device__ __forceinline__ void ag_emit(int part, const uint32_t* v, uint32_t t, uint32_t n, uint32_t ue, const Cfg& C,
                                         const fjsp_out& out) {
     Env E;
@@ -1592,6 +1608,7 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
                     for (int i = 0; i < 7; i++) Ea.w[6 + i] = sa[i];
                     pre = agv_pre(Ea, TL, C, act1);
                 }
+                ag_pin(pre);   // computed here, in the idle window before the waits
                 AG_MARK(2);
                 if (!wait_first) ag_spin(&s_flag1, (uint32_t)(k + 1));
                 ag_spin(&s_uflag, (uint32_t)(k + 1));
@@ -1605,8 +1622,9 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
                     Ea.w[9] = p2.x; Ea.w[10] = p2.y; Ea.w[11] = p2.z; Ea.w[12] = p2.w;
                     int mv = 0;
                     uint32_t pend = 0;
-                    const uint32_t r1 = (agv_fin(Ea, TL, pre, &mv, &pend) & 0xFFu) | ((uint32_t)act1 << 8);
-                    if (mv) Ea.set_loc(mv);
+                    // result | action << 8 with the move folded into W6; the distance bits (16..)
+                    // fall off in AM's r0 | r1 << 16
+                    const uint32_t r1 = agv_fin(Ea, TL, pre, &mv, &pend);
                     AG_MARK(4);
 #pragma unroll
                     for (int i = 0; i < 7; i++) sa[i] = Ea.w[6 + i];
@@ -1623,7 +1641,7 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
         predraw_wave<CR, PB, true, true>(S, K, lane, e, valid, (size_t)blk * EPW, s_mb, s_cp, s_nxt);
     } else {
         // E0: step k+2's actions, rewards, the pickup's masks; E1: int32 and float32 fields; E2:
-        // int8 fields, term, trunc, status, the AGV's pickup / drop masks; E3: step k+1's pickup
+        // int8 fields, term, trunc, status, the AGV's masks; E3: step k+1's pickup
         // station (for P), the other masks (balanced by measured cycles: scripts/diag_ag_stamps.py;
         // E0 shares P's SIMD)
         const Cfg C = cfg_at(ag_args(), s_lut);
