@@ -447,8 +447,13 @@ int fjsp_a2c_policy(const float* feats, const int8_t* masks, int32_t n, const fl
  * tile with those actions, run inside the same launch by the tile's last actor workgroup.
  * feats / masks = the current observation ([38][n] / [29][n]); actions u8 [8][n] and values f32
  * [n] as fjsp_a2c_policy writes them (probabilities are not available here).  out: the step's
- * outputs of this one step, limited to rewards, term, trunc, status, next_masks and feats (each
- * [F][n], any may be NULL; the other fields must be NULL).  Results equal fjsp_a2c_policy
+ * outputs of this one step, limited to rewards, term, trunc, status, next_masks and feats and,
+ * since the KPI extension (no ABI change: a call that was valid before does what it did), results,
+ * obs_i8, orders_completed, packaged and sim_time as fjsp_step writes them (the post-step state
+ * before the auto-reset), each [F][n], any may be NULL; obs_i32, obs_f32, masks and next_i32 /
+ * next_i8 / next_f32 must be NULL.  With one of the five KPI outputs the launch runs the kernel's
+ * KPI instance, with none the kernel it ran before.  The tiles' outputs leave in 16-byte pieces
+ * when n is a multiple of 64 and every given base is 16-byte aligned.  Results equal fjsp_a2c_policy
  * followed by fjsp_step with the same arguments, byte for byte.  Replaces fjsp_a2c_policy +
  * fjsp_step per vector step (one launch instead of two).  Only the envs [env_begin, env_begin +
  * env_count) are processed (whole 64-env tiles: env_begin a multiple of 64, env_count a multiple

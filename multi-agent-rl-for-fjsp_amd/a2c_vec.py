@@ -1173,7 +1173,8 @@ class VecMultiAgentA2C:
 
     def __init__(self, env, batch_size=256, gamma=0.99, lamb=0.95, lr_actor=3e-4, lr_critic=1e-3,
                  use_gae=True, entropy_coef=0.01, max_grad_norm=0.5, hidden=256, seed=None, group=None,
-                 use_graph=None, fused_policy=True, exchange="allreduce", dedup=True, track_episodes=False):
+                 use_graph=None, fused_policy=True, exchange="allreduce", dedup=True, track_episodes=False,
+                 track_kpis=False):
         self.env = env
         self.device = env.device
         self.N = env.num_envs
@@ -1206,6 +1207,12 @@ class VecMultiAgentA2C:
         # off by default, the collect / update path is then unchanged
         self.track_episodes = bool(track_episodes)
         self.episode_log = None
+        # shop-floor KPIs of the training rollouts (kpis.KpiLog over five more slabs the collect
+        # fills: result words, the stations' int8 observations, infos, sim time); off by default,
+        # the collect then launches the kernels and writes the bytes it always did
+        self.track_kpis = bool(track_kpis)
+        self.kpi_log = None
+        self.training_kpis = None
         self._bufs = None
         # None: decided per collect (_graph_on); True / False: always / never replay a captured graph
         self.use_graph = None if use_graph is None else bool(use_graph) and self.device.type == "cuda"
@@ -1255,9 +1262,20 @@ class VecMultiAgentA2C:
             # room for learn()'s drain interval: 4 batches at one episode per 16 steps and env
             self.episode_log = EpisodeLog(N, dev, env_id_base=self.env.env_id_base,
                                           capacity=max(65536, 4 * N * (T // 16 + 1)))
-            if not self.fused_step:   # fjsp_step writes the infos; the fused launch's outputs have no room
+            # fjsp_step writes the infos; the fused launch only with track_kpis (its KPI instance),
+            # so that this switch alone leaves the fused collect as it is
+            if not self.fused_step or self.track_kpis:
                 b["orders_completed"] = z(T, N, dt=torch.int32)
                 b["packaged"] = z(T, N, dt=torch.int32)
+        if self.track_kpis:
+            from .kpis import KpiLog
+            # the collect's five further outputs (fused and unfused alike) and their log
+            self.kpi_log = KpiLog(N, dev, env_id_base=self.env.env_id_base, capacity=max(65536, 4 * N * (T // 16 + 1)))
+            b["results"] = z(T, NA, N, dt=torch.int32)
+            b["obs_i8"] = z(T, 12, N, dt=torch.int8)
+            b.setdefault("orders_completed", z(T, N, dt=torch.int32))
+            b.setdefault("packaged", z(T, N, dt=torch.int32))
+            b["sim_time"] = z(T, N, dt=torch.float64)
         outs = []
         for t in range(T):
             o = nat.fjsp_out()
@@ -1267,9 +1285,9 @@ class VecMultiAgentA2C:
             o.status = b["status"][t].data_ptr()
             o.next_masks = b["masks"][t + 1].data_ptr()
             o.feats = b["feats"][t + 1].data_ptr()
-            if "orders_completed" in b:
-                o.orders_completed = b["orders_completed"][t].data_ptr()
-                o.packaged = b["packaged"][t].data_ptr()
+            for k in ("results", "obs_i8", "orders_completed", "packaged", "sim_time"):
+                if k in b:
+                    setattr(o, k, b[k][t].data_ptr())
             outs.append(o)
         b["outs"] = outs
         self._bufs = b
@@ -1295,6 +1313,9 @@ class VecMultiAgentA2C:
         if self.episode_log is not None:
             self.episode_log.reset()   # every env starts a new episode,
             self.episode_log.step0 = 0  # and end_step counts from this reset (a2c.py:278 global_timestep = 0)
+        if self.kpi_log is not None:
+            self.kpi_log.reset()
+            self.kpi_log.step0 = 0
 
     # ------------------------------------------------------------ predict
     @torch.no_grad()
@@ -1601,11 +1622,38 @@ class VecMultiAgentA2C:
     def account_episodes(self):
         """Scan the batch just collected into the episode log (track_episodes=True): one
         fjsp_episode_scan over the slab's rewards / term / trunc (and the infos slabs of the
-        unfused collect), on the current stream, outside the collect and its graph."""
+        unfused collect or of track_kpis), on the current stream, outside the collect and its graph."""
         if self.episode_log is None:
             raise RuntimeError("account_episodes needs track_episodes=True and an allocated rollout (reset())")
         b = self._bufs
         self.episode_log.scan(b["rewards"], b["term"], b["trunc"], b.get("orders_completed"), b.get("packaged"))
+
+    def account_kpis(self):
+        """Scan the batch just collected into the KPI log (track_kpis=True): one fjsp_kpi_scan over
+        the slab's result words / term / trunc / int8 observations / infos / sim time, on the
+        current stream, outside the collect and its graph; once per collected batch (an update's
+        epochs read the slab, they never scan it)."""
+        if self.kpi_log is None:
+            raise RuntimeError("account_kpis needs track_kpis=True and an allocated rollout (reset())")
+        b = self._bufs
+        self.kpi_log.scan(b["results"], b["term"], b["trunc"], b["obs_i8"], b["orders_completed"], b["packaged"],
+                          b["sim_time"])
+
+    def pop_kpis(self):
+        """Drain the KPI log (KpiLog.pop(): the records of the episodes that ended in the scanned
+        batches, global env ids, numbered as the episode log's) and append them to
+        training_kpis, whose "records" kpis.kpi_summary turns into the curve."""
+        if self.kpi_log is None:
+            raise RuntimeError("pop_kpis needs track_kpis=True and an allocated rollout (reset())")
+        import numpy as np
+        rec = self.kpi_log.pop()
+        if self.training_kpis is None:
+            self.training_kpis = rec
+        else:
+            old, axis = self.training_kpis, {"agents": 2, "stations": 2}
+            self.training_kpis = {k: old[k] + v if k == "dropped" else np.concatenate([old[k], v], axis=axis.get(k, 0))
+                                  for k, v in rec.items()}
+        return rec
 
     def episode_summary(self):
         """Drain the episode log: extends overall_rewards with the episodes' totals (a2c.py:348-349)
@@ -1622,24 +1670,35 @@ class VecMultiAgentA2C:
     def learn(self, total_timesteps, num_orders=25, seeds=None, deterministic=False, action_fn=None):
         """learn (a2c.py:254-388) on N envs: total_timesteps counts env-steps of this shard
         (N per vector step); an update every batch_size vector steps.  With track_episodes the
-        finished episodes of every batch are logged on the device; episode_summary() drains them."""
+        finished episodes of every batch are logged on the device; episode_summary() drains them.
+        With track_kpis their shop-floor KPIs are logged the same way, drained on the same rhythm
+        and kept in training_kpis (kpis.kpi_summary(self.training_kpis["records"]) is the curve)."""
         self.reset(seeds=seeds, num_orders=num_orders)
+        if self.track_kpis:   # starts empty in every learn(), as the episode lists do
+            self.kpi_log.pop()
+            self.training_kpis = None
         if self.track_episodes:   # a2c.py:274,279: both lists start empty in every learn()
             self.episode_summary()
             self.overall_rewards, self.episode_end_timesteps = [], []
         steps = batches = 0
         while steps < total_timesteps:
             self.collect(deterministic, action_fn)
+            batches += 1
             if self.track_episodes:
                 self.account_episodes()
-                batches += 1
                 if batches % 4 == 0:   # drain before the log can fill (the only synchronisation)
                     self.episode_summary()
+            if self.track_kpis:
+                self.account_kpis()
+                if batches % 4 == 0:
+                    self.pop_kpis()
             self.update()
             self.roll_over()
             steps += self.batch_size * self.N
         if self.track_episodes:
             self.episode_summary()
+        if self.track_kpis:
+            self.pop_kpis()
         return self
 
     @torch.no_grad()
@@ -1717,8 +1776,9 @@ class VecMultiAgentA2C:
         reset afterwards with the training num_orders as test() does.  The sampling key, the
         rollout slab, the networks and the optimisers are not touched.
 
-        KPIs of the training rollouts are not available: the fused collect (fjsp_a2c_policy_step)
-        has no result-word output, and track_episodes is unchanged."""
+        KPIs of the training rollouts themselves come from track_kpis=True (account_kpis /
+        pop_kpis, learn()'s training_kpis): the collect then fills the same slabs for the batches
+        the update trains on, and no separate rollout is needed."""
         from .episodes import EpisodeLog
         from .kpis import KpiLog
         on_train = env is None or env is self.env

@@ -1006,6 +1006,20 @@ FJSP_DEV void observe(Env& E, const Cfg& C, Sink& o) {
     compute_masks(E, C, o);
 }
 
+// The twelve values observe() hands its sink's i8() (fields 0..11: the two machines' and the four
+// packaging stations' is_busy / queue_length), with obs_i8_checked's int8 truncation but without
+// its status flag: for a caller that wants them of a state it does not otherwise observe
+// (k_policy_step's KPI outputs, the post-step state before the auto-reset).
+FJSP_DEV void station_i8(const Env& E, int8_t* v) {
+    v[0] = (int8_t)E.m_busy(0); v[1] = (int8_t)E.ll(L_M0Q);
+    v[2] = (int8_t)E.m_busy(1); v[3] = (int8_t)E.ll(L_M1Q);
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        v[4 + 2 * s] = (int8_t)E.p_busy(s);
+        v[5 + 2 * s] = (int8_t)E.p_queued(s);
+    }
+}
+
 // ---------------------------------------------------------------- heuristic policy
 // MultiAgentA2C._get_heuristic_actions (a2c.py:390-537) on the packed state.  The reference
 // compares the AGV position with (2,3) small, (0,3) big, (0,0) pickup, (3,5) packaging and

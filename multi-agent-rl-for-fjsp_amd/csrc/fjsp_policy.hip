@@ -745,6 +745,21 @@ struct StepArgs {
     int flags;             // STEP_AUTORESET
 };
 constexpr int STEP_AUTORESET = 1;   // reset(seed=None) an env whose episode ended
+// The KPI instances' further outputs (row t of the learner's KPI slabs, track_kpis; any may be
+// NULL), as step_and_emit writes them: the result words, the stations' int8 observations of the
+// post-step state before the auto-reset, the infos and the sim time.  An argument of its own that
+// only k_policy_step<*, true> has, so that StepArgs and the code of the other instances stay as
+// they are.
+template <bool KPI>
+struct KpiArgs {};
+template <>
+struct KpiArgs<true> {
+    uint32_t* results;           // [8][n]
+    int8_t* obs_i8;              // [12][n]
+    int32_t* orders_completed;   // [n]
+    int32_t* packaged;           // [n]
+    double* sim_time;            // [n]
+};
 
 // The tile's state words, [NSTATE][64] u32 after the policy's LDS (STATE_BYTES more per
 // workgroup: 2 x 77.5 KB still fit a CU): every actor workgroup of the tile copies them in with
@@ -776,7 +791,14 @@ __device__ __forceinline__ void state_prefetch(const StepArgs& St, int tile, uin
 constexpr int STG_F32 = 0, STG_NF32 = fjsp::NFEAT + fjsp::NSTATE + 1;
 constexpr int STG_F64 = STG_F32 + STG_NF32 * 64 * 4;
 constexpr int STG_U8 = STG_F64 + NAG * 64 * 8, STG_NU8 = fjsp::NMASK + 2;
-static_assert(STG_U8 + STG_NU8 * 64 <= LDS_BYTES - 16 && STG_F64 % 16 == 0 && STG_U8 % 16 == 0, "staging rows");
+// The KPI instances' rows after them (3.75 KB more): u32 [10][64] = result words 0..7,
+// orders_completed, packaged; f64 [1][64] sim_time; i8 [12][64] the stations' observations.
+constexpr int STG_K32 = STG_U8 + STG_NU8 * 64, STG_NK32 = NAG + 2;
+constexpr int STG_K64 = STG_K32 + STG_NK32 * 64 * 4;
+constexpr int STG_K8 = STG_K64 + 64 * 8, STG_NK8 = 12;
+static_assert(STG_K8 + STG_NK8 * 64 <= LDS_BYTES - 16 && STG_F64 % 16 == 0 && STG_U8 % 16 == 0 && STG_K32 % 16 == 0 &&
+              STG_K64 % 16 == 0 && STG_K8 % 16 == 0, "staging rows");
+static_assert(STG_NK8 == fjsp::NI8 && STG_NK32 * 16 + 32 + STG_NK8 * 4 <= NTHR, "the KPI rows: one 16-byte piece per thread");
 // observe() into the staging rows (StoreSink's values for the collect's two outputs); one wave
 // builds the a2c features, another the masks, from the staged state (the work of the other half
 // is dead code in each)
@@ -835,12 +857,30 @@ __device__ __forceinline__ void tile_copy_out(const StepArgs& St, int tile, cons
         if (dst) *reinterpret_cast<uint4*>(dst + e0 + 16 * piece) = sb[c];
     }
 }
+// ... and the KPI rows: 240 pieces, at most one per thread
+__device__ __forceinline__ void tile_copy_out_kpi(const KpiArgs<true>& K, size_t n, int tile, const unsigned char* s_mem,
+                                                  int tid) {
+    const size_t e0 = (size_t)tile * TA;
+    if (tid < STG_NK32 * 16) {
+        const int row = tid >> 4, piece = tid & 15;
+        uint32_t* dst = row < NAG ? (K.results ? K.results + row * n : nullptr)
+                        : reinterpret_cast<uint32_t*>(row == NAG ? K.orders_completed : K.packaged);
+        if (dst) *reinterpret_cast<uint4*>(dst + e0 + 4 * piece) = reinterpret_cast<const uint4*>(s_mem + STG_K32)[tid];
+    } else if (tid < STG_NK32 * 16 + 32) {
+        const int piece = tid - STG_NK32 * 16;
+        if (K.sim_time) *reinterpret_cast<uint4*>(K.sim_time + e0 + 2 * piece) = reinterpret_cast<const uint4*>(s_mem + STG_K64)[piece];
+    } else if (tid < STG_NK32 * 16 + 32 + STG_NK8 * 4) {
+        const int c = tid - (STG_NK32 * 16 + 32), row = c >> 2, piece = c & 3;
+        if (K.obs_i8) *reinterpret_cast<uint4*>(K.obs_i8 + row * n + e0 + 16 * piece) = reinterpret_cast<const uint4*>(s_mem + STG_K8)[c];
+    }
+}
 
 // STAGED: a full tile whose outputs go through the staging rows (tile_copy_out); else every lane
 // stores its own outputs (partial tiles, unaligned outputs).
-template <bool STAGED>
-__device__ __forceinline__ void tile_step(const PolicyArgs& A, const StepArgs& St, int tile, unsigned char* s_mem,
-                                          const uint32_t* s_state, int lane) {
+// KPI: the step's result words, the stations' int8 observations, the infos and the sim time as well.
+template <bool STAGED, bool KPI>
+__device__ __forceinline__ void tile_step(const PolicyArgs& A, const StepArgs& St, const KpiArgs<KPI>& K, int tile,
+                                          unsigned char* s_mem, const uint32_t* s_state, int lane) {
     const double* s_lut = reinterpret_cast<const double*>(s_state + fjsp::NSTATE * 64);
     const int e = tile * TA + lane;
     const bool valid = e < A.n;
@@ -888,6 +928,32 @@ __device__ __forceinline__ void tile_step(const PolicyArgs& A, const StepArgs& S
         if (St.trunc) fjsp::st32(St.trunc, ue, (uint8_t)truncated);
         if (St.status) fjsp::st32(St.status, ue, E.status());
     }
+    if constexpr (KPI) {   // step_and_emit's results / obs_i8 / infos / sim_time of the state before the reset
+        int8_t q[fjsp::NI8];
+        fjsp::station_i8(E, q);
+        const double sim = (double)(E.step() + 1) * (double)C.step_size;
+        if (STAGED) {
+            uint32_t* rk = reinterpret_cast<uint32_t*>(s_mem + STG_K32);
+            int8_t* rq = reinterpret_cast<int8_t*>(s_mem + STG_K8);
+#pragma unroll
+            for (int a = 0; a < NAG; a++) rk[a * 64 + lane] = res[a];
+            rk[NAG * 64 + lane] = (uint32_t)E.ncompleted();
+            rk[(NAG + 1) * 64 + lane] = (uint32_t)E.total_packaged();
+            reinterpret_cast<double*>(s_mem + STG_K64)[lane] = sim;
+#pragma unroll
+            for (int f = 0; f < fjsp::NI8; f++) rq[f * 64 + lane] = q[f];
+        } else {
+#pragma unroll
+            for (int a = 0; a < NAG; a++)
+                if (K.results) fjsp::st32(K.results, (uint32_t)a * n + ue, res[a]);
+#pragma unroll
+            for (int f = 0; f < fjsp::NI8; f++)
+                if (K.obs_i8) fjsp::st32(K.obs_i8, (uint32_t)f * n + ue, q[f]);
+            if (K.orders_completed) fjsp::st32(K.orders_completed, ue, (int32_t)E.ncompleted());
+            if (K.packaged) fjsp::st32(K.packaged, ue, (int32_t)E.total_packaged());
+            if (K.sim_time) fjsp::st32(K.sim_time, ue, sim);
+        }
+    }
     E.set_step(E.step() + 1);
     PST(4, __builtin_amdgcn_s_memtime());
     if ((St.flags & STEP_AUTORESET) && (all_done || truncated)) E = fjsp::env_reset_cold(E, T, C, St.S, e, nord);
@@ -907,8 +973,16 @@ __device__ __forceinline__ void tile_step(const PolicyArgs& A, const StepArgs& S
 
 // STAGED (every tile full, every output and state row 16-byte aligned): the tail's outputs go
 // through the staging rows (tile_copy_out)
-template <bool STAGED>
-__global__ void __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(4, 4))) k_policy_step(PolicyArgs A, StepArgs St) {
+// KPI: the instances of a launch with one of KpiArgs' outputs.  KP is KpiArgs<true> for them and
+// nothing otherwise: k_policy_step<*, false> keeps its two arguments (even an empty third one moves
+// the hidden arguments behind it), so its code has no trace of the KPI outputs.
+__device__ __forceinline__ KpiArgs<false> kpi_args() { return {}; }
+__device__ __forceinline__ const KpiArgs<true>& kpi_args(const KpiArgs<true>& k) { return k; }
+template <bool STAGED, bool KPI, class... KP>
+__global__ void __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(4, 4))) k_policy_step(PolicyArgs A, StepArgs St,
+                                                                                                 KP... kp) {
+    static_assert(sizeof...(KP) == (KPI ? 1 : 0), "KpiArgs<true> with KPI, else no further argument");
+    const KpiArgs<KPI>& K = kpi_args(kp...);
     __shared__ __attribute__((aligned(16))) unsigned char s_mem[LDS_BYTES + STATE_BYTES + LUT_BYTES];
     uint32_t* s_state = reinterpret_cast<uint32_t*>(s_mem + LDS_BYTES);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -961,13 +1035,14 @@ __global__ void __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(4, 4)
     if (!*s_last) return;
     PST(14, __builtin_amdgcn_s_memtime());   // diagnostic builds: the tile's step tail
     if (STAGED) {
-        if (wave == 0) tile_step<true>(A, St, tile, s_mem, s_state, lane);
+        if (wave == 0) tile_step<true, KPI>(A, St, K, tile, s_mem, s_state, lane);
         __syncthreads();                      // the step's staging rows are in
         if (wave == 1 || wave == 2) tile_observe(St, s_mem, s_state, lane, wave);
         __syncthreads();                      // the observation's
         tile_copy_out(St, tile, s_mem, tid);
+        if constexpr (KPI) tile_copy_out_kpi(K, (size_t)St.S.n, tile, s_mem, tid);
     } else if (wave == 0) {
-        tile_step<false>(A, St, tile, s_mem, s_state, lane);
+        tile_step<false, KPI>(A, St, K, tile, s_mem, s_state, lane);
     }
     PST(15, __builtin_amdgcn_s_memtime());
 }
@@ -2054,9 +2129,9 @@ int fjsp_internal_policy_step(const float* feats, const int8_t* masks, int32_t n
                               int32_t deterministic, uint8_t* actions, float* values, const fjsp::DevState& S,
                               const fjsp::Cfg& C, const fjsp_out& out, uint32_t* tile_cnt, uint32_t* tile_act,
                               int32_t autoreset, int32_t env_begin, int32_t env_count, hipStream_t stream) {
-    if (out.obs_i32 || out.obs_i8 || out.obs_f32 || out.masks || out.results || out.orders_completed || out.packaged ||
-        out.sim_time || out.next_i32 || out.next_i8 || out.next_f32)
-        return fjsp_internal_fail("fjsp_a2c_policy_step: outputs limited to rewards, term, trunc, status, next_masks, feats");
+    if (out.obs_i32 || out.obs_f32 || out.masks || out.next_i32 || out.next_i8 || out.next_f32)
+        return fjsp_internal_fail("fjsp_a2c_policy_step: outputs limited to rewards, term, trunc, status, next_masks, feats, "
+                                  "results, obs_i8, orders_completed, packaged, sim_time");
     // envs [env_begin, env_begin + env_count): whole 64-env tiles (the caller checks the range)
     PolicyArgs A{feats, masks, n, actor_w, critic_w, seed, env_gid0, step, deterministic, actions, values, nullptr,
                  values ? (env_count + TC - 1) / TC : 0, (env_count + TA - 1) / TA, env_begin / TA, policy_xmap(), policy_dedup()};
@@ -2065,13 +2140,22 @@ int fjsp_internal_policy_step(const float* feats, const int8_t* masks, int32_t n
     // the tiles copy their outputs out in 16-byte pieces when every tile is full and every output
     // row and state row of a tile starts 16-byte aligned (n % 64 == 0, 16-byte aligned bases)
     const uintptr_t bases = (uintptr_t)out.rewards | (uintptr_t)out.term | (uintptr_t)out.trunc | (uintptr_t)out.status |
-                            (uintptr_t)out.next_masks | (uintptr_t)out.feats | (uintptr_t)S.words;
+                            (uintptr_t)out.next_masks | (uintptr_t)out.feats | (uintptr_t)S.words |
+                            (uintptr_t)out.results | (uintptr_t)out.obs_i8 | (uintptr_t)out.orders_completed |
+                            (uintptr_t)out.packaged | (uintptr_t)out.sim_time;
     StepArgs St{S, C, out.rewards, out.term, out.trunc, out.status, out.next_masks, out.feats, tile_cnt, tile_act,
                 autoreset ? STEP_AUTORESET : 0};
-    if (n % TA == 0 && (bases & 15u) == 0)
-        hipLaunchKernelGGL(k_policy_step<true>, dim3((unsigned)(A.nc + actor_blocks)), dim3(NTHR), 0, stream, A, St);
-    else
-        hipLaunchKernelGGL(k_policy_step<false>, dim3((unsigned)(A.nc + actor_blocks)), dim3(NTHR), 0, stream, A, St);
+    const bool staged = n % TA == 0 && (bases & 15u) == 0;
+    const dim3 grid((unsigned)(A.nc + actor_blocks));
+    // the KPI instances only with one of their outputs: every other launch runs the kernels it ran before
+    if (out.results || out.obs_i8 || out.orders_completed || out.packaged || out.sim_time) {
+        const KpiArgs<true> K{out.results, out.obs_i8, out.orders_completed, out.packaged, out.sim_time};
+        if (staged) hipLaunchKernelGGL((k_policy_step<true, true, KpiArgs<true>>), grid, dim3(NTHR), 0, stream, A, St, K);
+        else hipLaunchKernelGGL((k_policy_step<false, true, KpiArgs<true>>), grid, dim3(NTHR), 0, stream, A, St, K);
+    } else {
+        if (staged) hipLaunchKernelGGL((k_policy_step<true, false>), grid, dim3(NTHR), 0, stream, A, St);
+        else hipLaunchKernelGGL((k_policy_step<false, false>), grid, dim3(NTHR), 0, stream, A, St);
+    }
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) {
         fjsp_internal_fail(hipGetErrorString(err));

@@ -6,7 +6,7 @@ per-block stamp slots are not shared), for every tile's last actor workgroup the
 entry to the tail (slot 1 -> 14) and of the tail (14 -> 15), and the launch's HIP-event time.
 Prints JSON.
 
-usage: FJSP_LIB=.../libfjsp_stamps.so python scripts/diag_collect_tail.py [N] [steps] [warm_batches]"""
+usage: FJSP_LIB=.../libfjsp_stamps.so python scripts/diag_collect_tail.py [N] [steps] [warm_batches] [track_kpis]"""
 import ctypes
 import importlib
 import json
@@ -22,8 +22,8 @@ A = importlib.import_module("multi-agent-rl-for-fjsp_amd.a2c_vec")
 V = importlib.import_module("multi-agent-rl-for-fjsp_amd.vec_env")
 
 
-def main(N=4096, steps=64, warm=1):
-    L = A.VecMultiAgentA2C(V.FJSPVecEnv(N), batch_size=256, seed=0)
+def main(N=4096, steps=64, warm=1, kpis=0):
+    L = A.VecMultiAgentA2C(V.FJSPVecEnv(N), batch_size=256, seed=0, track_kpis=bool(kpis))   # kpis: the KPI instance
     L.reset(seeds=torch.arange(N), num_orders=25)
     for _ in range(warm):
         L.collect()
@@ -58,7 +58,7 @@ def main(N=4096, steps=64, warm=1):
     Tl = np.array([x for l in tail for x in l])
     per_launch_max_tail = [max(x) for x in tail if x]
     per_launch_max_end = [max(p + q for p, q in zip(x, y)) for x, y in zip(pre, tail) if x]
-    res = {"envs": N, "groups": groups, "launches": len(ev_ms),
+    res = {"envs": N, "track_kpis": bool(kpis), "groups": groups, "launches": len(ev_ms),
            "launch_ms_median": float(np.median(ev_ms)),
            "tail_cycles": {"mean": float(Tl.mean()), "p50": float(np.median(Tl)), "p90": float(np.percentile(Tl, 90)),
                            "max": float(Tl.max())},
