@@ -694,7 +694,7 @@ __device__ __forceinline__ void predraw_wave(const DevState& S, int K, int lane,
 
 __device__ constexpr fjsp_out kNoOutDev = {};
 // The multi-wave kernels' arguments (k_step_pipe, k_step_ag), read per role from the kernarg
-// segment through a pointer the compiler cannot see through (`opaque`): a value read once at the
+// segment through a pointer the compiler cannot see through (`kargs`): a value read once at the
 // kernel's entry stays in an SGPR through every role's step loop (the state pointers, the config,
 // the output pointers and the action stream: 44 SGPR spills, ~400 v_readlane reloads in r03's
 // k_step_ag); read inside the role's branch it lives only there.  (volatile reads of the by-value
@@ -724,27 +724,60 @@ static_assert(sizeof(DevState) == 64 && sizeof(Cfg) == 48 && offsetof(AgArgs, C)
 static_assert(offsetof(PipeArgs, K) == 112 && offsetof(PipeArgs, seed) == 120 && offsetof(PipeArgs, step0) == 132 &&
                   offsetof(PipeArgs, mode) == 136 && offsetof(PipeArgs, autoreset) == 140 && offsetof(PipeArgs, out) == 144,
               "PipeArgs mirrors k_step_pipe's kernel arguments");
-template <class T>
-__device__ __forceinline__ const T* opaque(const T* p) {
+// k_step_pipe's form: the kernarg pointer as a generic pointer (per-lane flat loads, the values in
+// VGPRs).  The scalar form below measured 1.5-2 % slower per step for its masked-random actions
+// at 4 096 envs (profiles/emit_stores/), so the kernel keeps this one.
+template <class A>
+__device__ __forceinline__ const A* kargs_flat() {
+    const A* p = (const A*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(p));
     return p;
 }
-template <class A>
-__device__ __forceinline__ const A* kargs() {
-    return opaque((const A*)__builtin_amdgcn_kernarg_segment_ptr());
-}
-__device__ __forceinline__ const AgArgs* ag_args() { return kargs<AgArgs>(); }
 template <class A>
 __device__ __forceinline__ Cfg cfg_at(const A* a, const double* lut) {
     Cfg c = a->C;
     c.lut = lut;
     return c;
 }
-// the outputs a role writes, read in its branch
 __device__ __forceinline__ fjsp_out out_at(const fjsp_out& o) {
     fjsp_out r = kNoOutDev;
     r.obs_i32 = o.obs_i32; r.obs_i8 = o.obs_i8; r.obs_f32 = o.obs_f32; r.masks = o.masks;
     r.rewards = o.rewards; r.term = o.term; r.trunc = o.trunc; r.status = o.status;
+    return r;
+}
+// k_step_ag's form: the kernarg segment stays in the constant address space through the asm, so
+// the reads are scalar loads into SGPRs and a pointer loaded from constant memory is known to be
+// global: the stores through it are global stores, scalar base + the lane's 32-bit offset.
+#define FJSP_KARG __attribute__((address_space(4)))
+template <class A>
+__device__ __forceinline__ const FJSP_KARG A* kargs() {
+    const FJSP_KARG A* p = (const FJSP_KARG A*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+__device__ __forceinline__ const FJSP_KARG AgArgs* ag_args() { return kargs<AgArgs>(); }
+template <class A>
+__device__ __forceinline__ Cfg cfg_at(const FJSP_KARG A* a, const double* lut) {
+    Cfg c;
+    c.step_size = a->C.step_size; c.max_steps = a->C.max_steps; c.tray_cap = a->C.tray_cap;
+    c.mask_tray_cap = a->C.mask_tray_cap; c.storage_cap = a->C.storage_cap; c.pool0 = a->C.pool0;
+    c.pkg_cap = a->C.pkg_cap; c.ptk_small = a->C.ptk_small; c.ptk_big = a->C.ptk_big; c.ptk_pack = a->C.ptk_pack;
+    c.lut = lut;
+    return c;
+}
+template <class A>
+__device__ __forceinline__ DevState state_at(const FJSP_KARG A* a) {
+    DevState s;
+    s.words = a->S.words; s.orders = a->S.orders; s.scode = a->S.scode; s.snext = a->S.snext;
+    s.scstep = a->S.scstep; s.mt = a->S.mt; s.nxt = a->S.nxt; s.n = a->S.n;
+    return s;
+}
+// the outputs a role writes, read in its branch
+template <class A>
+__device__ __forceinline__ fjsp_out out_at(const FJSP_KARG A* a) {
+    fjsp_out r = kNoOutDev;
+    r.obs_i32 = a->out.obs_i32; r.obs_i8 = a->out.obs_i8; r.obs_f32 = a->out.obs_f32; r.masks = a->out.masks;
+    r.rewards = a->out.rewards; r.term = a->out.term; r.trunc = a->out.trunc; r.status = a->out.status;
     return r;
 }
 
@@ -818,8 +851,8 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
         if (wave == 0 && blockIdx.x == 0) stall_for_test(S);
     }
     if (wave == 0) {
-        // the config and the action stream read in this branch (kargs)
-        const PipeArgs* pa = kargs<PipeArgs>();
+        // the config and the action stream read in this branch (kargs_flat)
+        const PipeArgs* pa = kargs_flat<PipeArgs>();
         const DevState S = pa->S;
         const Cfg C = cfg_at(pa, s_lut);
         const uint64_t seed = pa->seed;
@@ -952,8 +985,8 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
         // observation fields (+ the next step's uniform actions), wave 2 int8 fields, masks,
         // term, trunc, status.  NEMIT == 1 (many envs: the CUs are already full): one wave.
         const int part = wave - 1;
-        // the config, the outputs and the action stream read in this branch (kargs)
-        const PipeArgs* pa = kargs<PipeArgs>();
+        // the config, the outputs and the action stream read in this branch (kargs_flat)
+        const PipeArgs* pa = kargs_flat<PipeArgs>();
         const Cfg C = cfg_at(pa, s_lut);
         const fjsp_out out = out_at(pa->out);
         const uint64_t seed = pa->seed;
@@ -1189,7 +1222,8 @@ __device__ __forceinline__ void ag_pin(AgvPre& a) {
 // One emit role's outputs of step t from the step's snapshot (AM's and K's words, SA_* / SK_*):
 // E0 rewards and the pickup's masks, E1 int32 and float32 fields, E2 int8 fields, term, trunc,
 // status and the AGV's masks, E3 the other masks.
-__device__ __forceinline__ void ag_emit(int part, const uint32_t* v, uint32_t t, uint32_t n, uint32_t ue, const Cfg& C,
+template <int part>
+__device__ __forceinline__ void ag_emit(const uint32_t* v, uint32_t t, uint32_t n, uint32_t ue, const Cfg& C,
                                         const fjsp_out& out) {
     Env E;
 #pragma unroll
@@ -1370,7 +1404,13 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
         if (wave == AG_AM && blockIdx.x == 0) stall_for_test(S);
     }
     if (wave == AG_AM) {
-        const Cfg C = cfg_at(ag_args(), s_lut);
+        Cfg C = cfg_at(ag_args(), s_lut);
+        // AM's loop has no SGPRs to spare: with its six config scalars there, four of them and a
+        // loop-invariant condition were spilled to VGPR lanes and read back by v_readlane at each
+        // use.  Held in VGPRs (where the per-lane reads through a generic pointer had them before)
+        // they cost nothing per use.
+        asm volatile("" : "+v"(C.max_steps), "+v"(C.tray_cap), "+v"(C.storage_cap), "+v"(C.pool0), "+v"(C.ptk_small),
+                          "+v"(C.ptk_big));
         __builtin_amdgcn_s_setprio(3);   // the machines -> AGV chain is the critical path
         Env E;
         if (valid) env_load(E, S.words, S.n, e);
@@ -1644,70 +1684,77 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
         // int8 fields, term, trunc, status, the AGV's masks; E3: step k+1's pickup
         // station (for P), the other masks (balanced by measured cycles: scripts/diag_ag_stamps.py;
         // E0 shares P's SIMD)
-        const Cfg C = cfg_at(ag_args(), s_lut);
-        const int part = wave == AG_E0 ? 0 : wave == AG_E1 ? 1 : wave == AG_E2 ? 2 : 3;
-        if (part == 3) __builtin_amdgcn_s_setprio(2);   // E3 runs the pickup station for P first
-        const AgArgs* ea = ag_args();   // the outputs and E0's action stream, read in this branch
-        fjsp_out eo = kNoOutDev;
-        eo.obs_i32 = ea->out.obs_i32; eo.obs_i8 = ea->out.obs_i8; eo.obs_f32 = ea->out.obs_f32; eo.masks = ea->out.masks;
-        eo.rewards = ea->out.rewards; eo.term = ea->out.term; eo.trunc = ea->out.trunc; eo.status = ea->out.status;
-        const uint64_t eseed = ea->seed;
-        const uint32_t egid = ea->gid0 + (uint32_t)e, estep = ea->step0;
-        for (int k = 0; k <= K; k++) {
-            AG_T0();
-            if (part == 3 && k + 1 < K) {   // step k+1's pickup station, from P's AGV result of step k
-                const bool fresh = ag_fresh(k, valid, s_p1, s_kpost, lane, C, autoreset);
-                if (__ballot(valid && fresh) != 0) ag_spin(&s_flag1, (uint32_t)(k + 1));
-                AG_MARK(3);
-                if (valid) {
-                    Env Ep;
+        // The role is a compile-time value: four instances of the loop, selected once per wave, so
+        // each role reads only the snapshot words and the output pointers it uses.
+        auto emit_loop = [&](auto role) __attribute__((always_inline)) {
+            constexpr int part = decltype(role)::value;
+            const FJSP_KARG AgArgs* ea = ag_args();   // the config, the outputs and E0's action stream, read here
+            const Cfg C = cfg_at(ea, s_lut);
+            if (part == 3) __builtin_amdgcn_s_setprio(2);   // E3 runs the pickup station for P first
+            const fjsp_out eo = out_at(ea);
+            const uint32_t n = (uint32_t)ea->S.n;
+            const uint64_t eseed = ea->seed;
+            const uint32_t egid = ea->gid0 + (uint32_t)e, estep = ea->step0;
+            for (int k = 0; k <= K; k++) {
+                AG_T0();
+                if (part == 3 && k + 1 < K) {   // step k+1's pickup station, from P's AGV result of step k
+                    const bool fresh = ag_fresh(k, valid, s_p1, s_kpost, lane, C, autoreset);
+                    if (__ballot(valid && fresh) != 0) ag_spin(&s_flag1, (uint32_t)(k + 1));
+                    AG_MARK(3);
+                    if (valid) {
+                        Env Ep;
 #pragma unroll
-                    for (int i = 0; i < NSTATE; i++) Ep.w[i] = 0u;
-                    if (fresh) {
-                        uint32_t p1[8];
-                        q_get(&s_p1[k & 1][0][lane], 2, p1);
-                        Ep.w[0] = p1[P1_W0]; Ep.w[4] = p1[P1_W4]; Ep.w[5] = p1[P1_W5]; Ep.w[7] = p1[P1_W7];
-                    } else {
-                        uint32_t rs[16];
-                        q_get(&s_res[k & 1][0][lane], 2, rs);   // RS_NO, RS_W4, RS_W5..: W5, W6, W7
-                        Ep.w[0] = (s_p1[(k - 1) & 1][0][lane].x & 0x00FFFFFFu) | (rs[RS_NO] << 24);
-                        Ep.w[4] = rs[RS_W4]; Ep.w[5] = rs[RS_W5]; Ep.w[7] = rs[RS_W5 + 2];
+                        for (int i = 0; i < NSTATE; i++) Ep.w[i] = 0u;
+                        if (fresh) {
+                            uint32_t p1[8];
+                            q_get(&s_p1[k & 1][0][lane], 2, p1);
+                            Ep.w[0] = p1[P1_W0]; Ep.w[4] = p1[P1_W4]; Ep.w[5] = p1[P1_W5]; Ep.w[7] = p1[P1_W7];
+                        } else {
+                            uint32_t rs[16];
+                            q_get(&s_res[k & 1][0][lane], 2, rs);   // RS_NO, RS_W4, RS_W5..: W5, W6, W7
+                            Ep.w[0] = (s_p1[(k - 1) & 1][0][lane].x & 0x00FFFFFFu) | (rs[RS_NO] << 24);
+                            Ep.w[4] = rs[RS_W4]; Ep.w[5] = rs[RS_W5]; Ep.w[7] = rs[RS_W5 + 2];
+                        }
+                        const int act0 = (int)(s_act[(k + 1) % 3][0][lane] & 0xFFu);
+                        const uint32_t r0 = (pickup_execute(Ep, TL, C, act0) & 0xFFu) | ((uint32_t)act0 << 8);
+                        AG_MARK(4);
+                        s_pk[lane] = make_uint4(Ep.w[0], Ep.w[4], Ep.w[5], Ep.w[7]);
+                        s_pkr[lane] = make_uint2(r0, Ep.w[2]);
+                        __hip_atomic_store(&s_uflag, (uint32_t)(k + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                     }
-                    const int act0 = (int)(s_act[(k + 1) % 3][0][lane] & 0xFFu);
-                    const uint32_t r0 = (pickup_execute(Ep, TL, C, act0) & 0xFFu) | ((uint32_t)act0 << 8);
-                    AG_MARK(4);
-                    s_pk[lane] = make_uint4(Ep.w[0], Ep.w[4], Ep.w[5], Ep.w[7]);
-                    s_pkr[lane] = make_uint2(r0, Ep.w[2]);
-                    __hip_atomic_store(&s_uflag, (uint32_t)(k + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
+                AG_MARK(0);
+                if (part == 0 && k + 2 < K) {   // E0 draws step k + 2's actions (uniform random)
+                    int act[NA];
+                    synth_uniform(eseed, egid, estep + (uint32_t)(k + 2), act);
+                    s_act[(k + 2) % 3][0][lane] = pack_actions(act, 0);
+                    s_act[(k + 2) % 3][1][lane] = pack_actions(act, 4);
+                }
+                if (k > 0 && valid) {
+                    const uint32_t t = (uint32_t)(k - 1);
+                    uint32_t v[SNAP_N];
+                    snap_get(snap[(k - 1) & 1], lane, v);
+                    if (part == 2 && s_abort) v[SA_ST] |= ST_SPIN_TIMEOUT | ST_DIVERGED;
+                    FJSP_DIAG(
+                    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the snapshot arrived
+                    )
+                    AG_MARK(1);
+                    ag_emit<part>(v, t, n, ue, C, eo);
+                }
+                AG_MARK(2);
+                AG_ACC(ag_busy);
+                AG_BARRIER();
             }
-            AG_MARK(0);
-            if (part == 0 && k + 2 < K) {   // E0 draws step k + 2's actions (uniform random)
-                int act[NA];
-                synth_uniform(eseed, egid, estep + (uint32_t)(k + 2), act);
-                s_act[(k + 2) % 3][0][lane] = pack_actions(act, 0);
-                s_act[(k + 2) % 3][1][lane] = pack_actions(act, 4);
-            }
-            if (k > 0 && valid) {
-                const uint32_t t = (uint32_t)(k - 1);
-                uint32_t v[SNAP_N];
-                snap_get(snap[(k - 1) & 1], lane, v);
-                if (part == 2 && s_abort) v[SA_ST] |= ST_SPIN_TIMEOUT | ST_DIVERGED;
-                FJSP_DIAG(
-                __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the snapshot arrived
-                )
-                AG_MARK(1);
-                ag_emit(part, v, t, n, ue, C, eo);
-            }
-            AG_MARK(2);
-            AG_ACC(ag_busy);
-            AG_BARRIER();
-        }
+        };
+        if (wave == AG_E0) emit_loop(std::integral_constant<int, 0>{});
+        else if (wave == AG_E1) emit_loop(std::integral_constant<int, 1>{});
+        else if (wave == AG_E2) emit_loop(std::integral_constant<int, 2>{});
+        else emit_loop(std::integral_constant<int, 3>{});
     }
     __syncthreads();
     // the state pointers read again for the copy-out (otherwise live in SGPRs through every
     // role's step loop)
-    const DevState So = ag_args()->S;
+    const DevState So = state_at(ag_args());
     if (threadIdx.x == 0) report_abort(So, s_abort);
     FJSP_DIAG(
     const uint64_t t_out = __builtin_amdgcn_s_memtime();
