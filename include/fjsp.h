@@ -172,7 +172,13 @@ int fjsp_abi_version(void);
 const char* fjsp_last_error(void);
 int fjsp_default_config(fjsp_config* cfg);
 int fjsp_default_reward_weights(fjsp_reward_weights* w);
-/* Replace the handle's reward weights (takes effect at the next launch). */
+/* Replace the handle's reward weights.  The weights belong to the handle (a fresh handle has the
+ * defaults) and are not part of a snapshot: fjsp_restore leaves the handle's own weights, whatever
+ * the handle the snapshot was taken from used.  A change applies from the next launch (fjsp_step,
+ * fjsp_step_many, fjsp_a2c_policy_step, a replayed graph of one) or the next server step (the step
+ * server is stopped first and relaunched by that step); launches queued on the handle's stream before
+ * the call keep the old weights (the call waits for that stream; work a caller queued on streams
+ * of its own is the caller's to finish first).  Every step kernel reads the one device table the call rewrites. */
 int fjsp_set_reward_weights(fjsp_handle* h, const fjsp_reward_weights* w);
 /* Validate a config (0 = usable by the closed-form kernels). */
 int fjsp_check_config(const fjsp_config* cfg);

@@ -313,6 +313,40 @@ class FJSPVecEnv:
             raise ValueError(f"snapshot of {snap.numel() * snap.element_size()} bytes, handle needs {nb}")
         nat.check(nat.lib().fjsp_restore(self._h, _ptr(snap.contiguous())))
 
+    def reward_weights(self):
+        """The handle's reward weights as {fjsp_reward_weights field: value} (the defaults until
+        set_reward_weights; they belong to the handle and are not part of a snapshot)."""
+        w = getattr(self, "_weights", None)
+        if w is None:
+            w = nat.fjsp_reward_weights()
+            nat.check(nat.lib().fjsp_default_reward_weights(ctypes.byref(w)))
+            self._weights = w
+        return {k: float(getattr(w, k)) for k in nat.REWARD_FIELDS}
+
+    def set_reward_weights(self, weights=None, **names):
+        """fjsp_set_reward_weights: `weights` = a fjsp_reward_weights, sixteen values in its field
+        order or a {field: value} mapping (None: keep the current ones), then single fields by
+        name (case-insensitive, so RewardModel's ORDER_COMPLETE_REWARD works too).  Applies from
+        the next launch or server step.  Returns the new weights as reward_weights() does."""
+        cur = self.reward_weights()
+        if isinstance(weights, nat.fjsp_reward_weights):
+            weights = {k: getattr(weights, k) for k in nat.REWARD_FIELDS}
+        elif weights is not None and not hasattr(weights, "keys"):
+            vals = [float(x) for x in weights]
+            if len(vals) != len(nat.REWARD_FIELDS):
+                raise ValueError(f"{len(nat.REWARD_FIELDS)} reward weights expected, got {len(vals)}")
+            weights = dict(zip(nat.REWARD_FIELDS, vals))
+        for src in (weights or {}, names):
+            for k, v in src.items():
+                if k.lower() not in cur:
+                    raise ValueError(f"unknown reward weight {k!r}")
+                cur[k.lower()] = float(v)
+        w = nat.fjsp_reward_weights(*[cur[k] for k in nat.REWARD_FIELDS])
+        self._sync_stream()
+        nat.check(nat.lib().fjsp_set_reward_weights(self._h, ctypes.byref(w)))
+        self._weights = w
+        return self.reward_weights()
+
     def last_kernel(self):
         """Name of the kernel variant of the last step launch (e.g. "k_step_pipe<lds>")."""
         return nat.lib().fjsp_last_kernel(self._h).decode()

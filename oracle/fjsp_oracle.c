@@ -181,7 +181,14 @@ typedef struct {
     uint32_t status;
     /* scratch for step results */
     uint32_t results[8];
+    /* RewardModel's sixteen weights (RewardModel.py:12-32), in fjsp_reward_weights field order */
+    double w[16];
 } sim_t;
+
+enum { W_ORDER = 0, W_THROUGHPUT, W_TIME, W_PICK_LOAD, W_PICK_TRAY, W_PICK_IDLE, W_AGV_DELIVERY, W_AGV_MOVE,
+       W_AGV_PACKAGING, W_AGV_INVALID, W_M_COMPLETE, W_M_START, W_M_IDLE, W_P_COMPLETE, W_P_START, W_P_IDLE, NW };
+static const double DEFAULT_W[NW] = {100.0, 10.0, -0.1, 1.0, 5.0, -1.0, 2.0, -0.1, 10.0, -5.0, 5.0, 1.0, -2.0, 20.0,
+                                     2.0, -1.0};
 
 /* LocationType values / coordinates (constants.py:5-11; enums/LocationType.py) */
 enum { LOC_NONE = 0, LOC_PICKUP = 1, LOC_BIG = 2, LOC_SMALL = 3, LOC_STORAGE = 4, LOC_PACK = 5 };
@@ -791,10 +798,13 @@ void* oracle_create(const int32_t* cfg) {
     sim_t* s = (sim_t*)calloc(1, sizeof(sim_t));
     memcpy(s->cfg, cfg, sizeof(s->cfg));
     mt_seed(&s->rng, 5489u);
+    memcpy(s->w, DEFAULT_W, sizeof(s->w));
     sim_init(s);
     return s;
 }
 void oracle_destroy(void* h) { free(h); }
+/* sim.reward_calculator's fields; they belong to the sim object, a reset keeps them.  NULL = defaults. */
+void oracle_set_weights(void* h, const double* w) { memcpy(((sim_t*)h)->w, w ? w : DEFAULT_W, sizeof(DEFAULT_W)); }
 void oracle_seed(void* h, uint32_t seed) { mt_seed(&((sim_t*)h)->rng, seed); }
 
 int oracle_reset(void* h, int num_orders, oracle_rec* o) {
@@ -856,32 +866,33 @@ int oracle_step(void* h, const uint8_t* actions, const uint8_t* order, oracle_re
     int products_packaged = s->total_packaged - products_before;
     int time_elapsed = s->cfg[C_STEP];
     /* RewardModel.calculate_global_reward :34-44 */
-    double g = 100.0 * (double)orders_completed;
-    g += 10.0 * (double)products_packaged;
-    g += -0.1 * (double)time_elapsed;
+    const double* w = s->w;
+    double g = w[W_ORDER] * (double)orders_completed;
+    g += w[W_THROUGHPUT] * (double)products_packaged;
+    g += w[W_TIME] * (double)time_elapsed;
     if (o) memset(o, 0, sizeof(*o));
     for (int a = 0; a < 8; a++) {
         int act = actions[a] == 255 ? 0 : actions[a];   /* actions.get(agent_id, 0) */
         uint32_t r = res[a];
         double loc = 0.0;                                 /* calculate_local_reward :46-97 */
         if (a == 0) {
-            if (r & 2) loc += 1.0;
-            if (r & 4) loc += 5.0;
-            if (act == 0 && (r & 8)) loc += -1.0;
+            if (r & 2) loc += w[W_PICK_LOAD];
+            if (r & 4) loc += w[W_PICK_TRAY];
+            if (act == 0 && (r & 8)) loc += w[W_PICK_IDLE];
         } else if (a == 1) {
-            if (r & 8) loc += 2.0;
-            if (r & 16) loc += 2.0;
-            if (r & 32) loc += 10.0;
-            if (r & 4) loc += -0.1;
-            if (r & 2) loc += -5.0;
+            if (r & 8) loc += w[W_AGV_DELIVERY];
+            if (r & 16) loc += w[W_AGV_DELIVERY];
+            if (r & 32) loc += w[W_AGV_PACKAGING];
+            if (r & 4) loc += w[W_AGV_MOVE];
+            if (r & 2) loc += w[W_AGV_INVALID];
         } else if (a <= 3) {
-            if (r & 2) loc += 1.0;
-            if (r & 4) loc += 5.0;
-            if (act == 0 && (r & 8)) loc += -2.0;
+            if (r & 2) loc += w[W_M_START];
+            if (r & 4) loc += w[W_M_COMPLETE];
+            if (act == 0 && (r & 8)) loc += w[W_M_IDLE];
         } else {
-            if (r & 2) loc += 2.0;
-            if (r & 4) loc += 20.0;
-            if (act == 0 && (r & 8)) loc += -1.0;
+            if (r & 2) loc += w[W_P_START];
+            if (r & 4) loc += w[W_P_COMPLETE];
+            if (act == 0 && (r & 8)) loc += w[W_P_IDLE];
         }
         if (o) o->rewards[a] = g / 8.0 + loc;           /* combine_rewards :99-110 */
         s->results[a] = r;
@@ -1006,12 +1017,26 @@ void oracle_heuristic(void* h, uint8_t* out) {
  * oracle_heuristic (policy 3);
  * auto-reset with seed=None on term|trunc.  If `rec_out` is non-NULL it receives
  * [steps][n_envs] records (post-step obs); reset obs go to `reset_out` if non-NULL. */
+int oracle_rollout_w(const int32_t* cfg, int n_envs, uint32_t gid0, const uint32_t* seeds,
+                     int num_orders, int steps, uint64_t action_seed, int policy,
+                     const uint8_t* actions_in, oracle_rec* rec_out, oracle_rec* reset_out,
+                     uint64_t* checksum, const double* weights);
 int oracle_rollout(const int32_t* cfg, int n_envs, uint32_t gid0, const uint32_t* seeds,
                    int num_orders, int steps, uint64_t action_seed, int policy,
                    const uint8_t* actions_in, oracle_rec* rec_out, oracle_rec* reset_out,
                    uint64_t* checksum) {
+    return oracle_rollout_w(cfg, n_envs, gid0, seeds, num_orders, steps, action_seed, policy, actions_in, rec_out,
+                            reset_out, checksum, NULL);
+}
+
+/* oracle_rollout under the reward weights w[16] (fjsp_reward_weights order; NULL = the defaults). */
+int oracle_rollout_w(const int32_t* cfg, int n_envs, uint32_t gid0, const uint32_t* seeds,
+                     int num_orders, int steps, uint64_t action_seed, int policy,
+                     const uint8_t* actions_in, oracle_rec* rec_out, oracle_rec* reset_out,
+                     uint64_t* checksum, const double* weights) {
     uint64_t ck = 0;
     sim_t* s = (sim_t*)oracle_create(cfg);
+    oracle_set_weights(s, weights);
     oracle_rec cur, rec;
     for (int e = 0; e < n_envs; e++) {
         mt_seed(&s->rng, seeds[e]);

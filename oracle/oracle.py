@@ -86,6 +86,8 @@ def lib():
                                      ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
                                      ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.POINTER(ctypes.c_uint64)]
+        L.oracle_rollout_w.argtypes = L.oracle_rollout.argtypes + [ctypes.c_void_p]
+        L.oracle_set_weights.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.oracle_gae.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                  ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                  ctypes.c_void_p, ctypes.c_void_p]
@@ -97,6 +99,15 @@ def cfg_array(**over):
     c = dict(DEFAULT_CFG)
     c.update(over)
     return (ctypes.c_int32 * len(CFG_ORDER))(*[int(c[k]) for k in CFG_ORDER])
+
+
+def weights_array(weights):
+    """The sixteen reward weights (fjsp_reward_weights field order) as contiguous f64, or None."""
+    if weights is None:
+        return None
+    w = np.ascontiguousarray(weights, np.float64)
+    assert w.shape == (16,), w.shape
+    return w
 
 
 def rec_to_np(r):
@@ -117,6 +128,12 @@ class OracleEnv:
 
     def seed(self, s):
         lib().oracle_seed(self._h, s & 0xFFFFFFFF)
+
+    def set_weights(self, weights=None):
+        """sim.reward_calculator's sixteen fields in fjsp_reward_weights order (None: the defaults);
+        they stay with the env over resets."""
+        w = weights_array(weights)
+        lib().oracle_set_weights(self._h, None if w is None else w.ctypes.data)
 
     def reset(self, seed=None, num_orders=30):
         if seed is not None:
@@ -154,9 +171,10 @@ def actions(seed, env_gid, step, masks=None):
 
 
 def rollout(n_envs, steps, seeds=None, gid0=0, num_orders=30, action_seed=0, policy=0,
-            actions_in=None, record=True, record_resets=False, **cfg):
+            actions_in=None, record=True, record_resets=False, weights=None, **cfg):
     """Run n_envs envs x steps with auto-reset; returns (records [steps, n_envs], resets, checksum).
-    policy: 0 unmasked random, 1 masked random, 3 heuristic (a2c.py:390-537); actions_in -> 2."""
+    policy: 0 unmasked random, 1 masked random, 3 heuristic (a2c.py:390-537); actions_in -> 2.
+    weights: the sixteen reward weights in fjsp_reward_weights order (None: the defaults)."""
     seeds = np.arange(gid0, gid0 + n_envs, dtype=np.uint32) if seeds is None else np.asarray(seeds, np.uint32)
     rec = np.zeros((steps, n_envs), REC_DTYPE) if record else None
     rst = np.zeros((steps, n_envs), REC_DTYPE) if record_resets else None
@@ -165,10 +183,12 @@ def rollout(n_envs, steps, seeds=None, gid0=0, num_orders=30, action_seed=0, pol
         ain = np.ascontiguousarray(actions_in, np.uint8)
         policy = 2
     ck = ctypes.c_uint64(0)
-    lib().oracle_rollout(cfg_array(**cfg), n_envs, gid0, seeds.ctypes.data, num_orders, steps,
-                         action_seed, policy, None if ain is None else ain.ctypes.data,
-                         None if rec is None else rec.ctypes.data,
-                         None if rst is None else rst.ctypes.data, ctypes.byref(ck))
+    w = weights_array(weights)
+    lib().oracle_rollout_w(cfg_array(**cfg), n_envs, gid0, seeds.ctypes.data, num_orders, steps,
+                           action_seed, policy, None if ain is None else ain.ctypes.data,
+                           None if rec is None else rec.ctypes.data,
+                           None if rst is None else rst.ctypes.data, ctypes.byref(ck),
+                           None if w is None else w.ctypes.data)
     return rec, rst, ck.value
 
 

@@ -11,7 +11,12 @@
       queue 128 products of one colour (7 AGV actions per wanted tray, 3 per other tray, one
       product loaded per step); tests/overflow_scripts.py's controller then runs on the KEEP
       (default 2 500) most favourable tables, every colour.  Prints the fullest packaging queues
-      (128 = the flag; overflow_scripts.OBS_SEED = 2 528 654 is the one table that reaches it)."""
+      (128 = the flag; overflow_scripts.OBS_SEED = 2 528 654 is the one table that reaches it).
+  python scripts/search_status_cases.py blue2 [SEEDS]
+      a configuration in which packaging_blue_2 earns its three reward terms (tests/test_gpu_rewards.py):
+      432 configurations at action seed 13 under masked actions (200 envs x 280 steps), then action
+      seeds 0..SEEDS-1 (default 400) on the best six; ranked by the smallest of the three counts on
+      unflagged env-steps (parity_util.STATUS_CFGS["F"]: 31 / 161 / 68, nothing flagged)."""
 import os
 import sys
 
@@ -65,11 +70,41 @@ def obs(tables=3000000, keep=2500):
     print("fullest queues (products, seed, colour, last step):", top[:12])
 
 
+def blue2(nseeds=400):
+    import itertools
+    flags = O.ST_EXCEPTION | O.ST_OBS_OVERFLOW | O.ST_PKG_WAIT
+
+    def score(cfg, aseed):
+        rec, _, _ = O.rollout(200, 280, seeds=P.status_seeds(200), num_orders=20, action_seed=aseed, policy=1, **cfg)
+        fl = (rec["status"] & flags) != 0
+        c = P.reward_term_counts(rec, ~fl)
+        b = (c["pkg_blue_2.start"], c["pkg_blue_2.complete"], c["pkg_blue_2.idle"])
+        return min(b), b, float(fl.mean())
+    res = []
+    for cap, tc, ptp, pts, mx in itertools.product((1, 2, 3), (1, 2, 3), (250, 500, 1000, 2000), (10, 60), (200, 253)):
+        cfg = dict(packaging_capacity=cap, tray_capacity=tc, mask_tray_capacity=tc, pt_packaging=ptp, pt_small=pts,
+                   pt_big=pts if pts == 10 else 120, max_episode_steps=mx)
+        res.append(score(cfg, 13) + (cfg,))
+    res.sort(key=lambda r: (-r[0], r[2]))
+    print("configurations at action seed 13 (min, (start, complete, idle), flagged share, cfg):")
+    for r in res[:10]:
+        print(" ", r, flush=True)
+    out = []
+    for r in res[:6]:
+        out += [score(r[3], a) + (r[3], a) for a in range(nseeds)]
+    out.sort(key=lambda r: (-r[0], r[2]))
+    print("action seeds on the best six:")
+    for r in out[:10]:
+        print(" ", r, flush=True)
+
+
 if __name__ == "__main__":
     cmd, args = (sys.argv[1] if len(sys.argv) > 1 else ""), [int(x) for x in sys.argv[2:]]
     if cmd == "c-seed":
         c_seed(*args)
     elif cmd == "obs":
         obs(*args)
+    elif cmd == "blue2":
+        blue2(*args)
     else:
         sys.exit(__doc__)

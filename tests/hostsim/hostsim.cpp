@@ -52,6 +52,14 @@ void* hs_create(const int32_t* c, int n) {
     h->mti = (int*)calloc(n, sizeof(int));
     return h;
 }
+// w[16] in fjsp_reward_weights order: rebuilds the reward table as fjsp_set_reward_weights does
+void hs_set_weights(void* p, const double* w) {
+    HS* h = (HS*)p;
+    build_reward_lut(w, h->C.step_size, const_cast<double*>(h->C.lut));
+}
+// the step's two reward functions on their own (the exhaustive table test)
+double hs_local_reward(void* p, int a, uint32_t r, int act) { return local_reward(((HS*)p)->C, a, r, act); }
+double hs_global_reward8(void* p, int orders_done, int packaged) { return global_reward8(((HS*)p)->C, orders_done, packaged); }
 void hs_destroy(void* p) {
     HS* h = (HS*)p; free((void*)h->C.lut); free(h->E); free(h->orders); free(h->scode); free(h->snext); free(h->scstep); free(h->mt); free(h->mti); free(h);
 }

@@ -110,6 +110,12 @@ STATUS_CFGS = {
     "D": dict(cfg={"packaging_capacity": 2, "pt_packaging": 200}, num_orders=20, action_seed=13, target="flagged"),
     "E": dict(cfg={"packaging_capacity": 2, "pt_packaging": 200, "storage_capacity": 1, "max_episode_steps": 90},
               num_orders=20, action_seed=13, target="TRAY_LOST"),
+    # Not a status configuration (no target; the status tests do not run it): the one configuration
+    # found in which packaging_blue_2 earns rewards (tests/test_gpu_rewards.py).  One Resource slot
+    # per station, trays of one product and packaging runs of 100 steps keep packaging_blue_1's
+    # slot in use when the next blue tray arrives; nothing is flagged under masked actions.
+    "F": dict(cfg={"packaging_capacity": 1, "tray_capacity": 1, "mask_tray_capacity": 1, "pt_packaging": 1000,
+                   "pt_small": 10, "pt_big": 10, "max_episode_steps": 253}, num_orders=20, action_seed=301, target=None),
 }
 
 
@@ -241,3 +247,81 @@ def assert_grads_close(got, ref, rel=1e-5):
     bad = [(s, e) for s, e in errs if e > rel]
     assert not bad, bad
     return errs
+
+
+# ---------------------------------------------------------------- reward weights
+# The sixteen RewardModel weights in fjsp_reward_weights field order, and the non-default sets
+# the reward tests run under (tests/test_gpu_rewards.py, test_hostsim_logic.py, the fixture
+# tests/golden/reward_weights.npz).  With the defaults several weights coincide (PICKUP_LOAD =
+# MACHINE_START, PICKUP_IDLE = PACKAGING_IDLE, AGV_MOVE = TIME_PENALTY, ...) and all but +-0.1 are
+# small dyadic numbers, so a lookup into another agent kind's table region or a sum in another
+# order changes no bit.  DISTINCT: pairwise different non-dyadic values with the defaults' signs and
+# rough magnitudes (test_reward_sets checks that no two flag combinations of an agent share a sum).
+REWARD_NAMES = ("ORDER_COMPLETE_REWARD", "THROUGHPUT_BONUS", "TIME_PENALTY", "PICKUP_LOAD_REWARD",
+                "PICKUP_TRAY_COMPLETE", "PICKUP_IDLE_PENALTY", "AGV_DELIVERY_REWARD", "AGV_MOVE_PENALTY",
+                "AGV_PACKAGING_DELIVERY", "AGV_INVALID_ACTION", "MACHINE_COMPLETE_REWARD", "MACHINE_START_REWARD",
+                "MACHINE_IDLE_PENALTY", "PACKAGING_COMPLETE_REWARD", "PACKAGING_START_REWARD",
+                "PACKAGING_IDLE_PENALTY")
+DEFAULT_WEIGHTS = (100.0, 10.0, -0.1, 1.0, 5.0, -1.0, 2.0, -0.1, 10.0, -5.0, 5.0, 1.0, -2.0, 20.0, 2.0, -1.0)
+DISTINCT = (37.3, 3.7, -0.13, 1.1, 4.9, -0.7, 2.3, -0.17, 9.1, -5.3, 6.1, 1.3, -1.9, 19.7, 2.9, -1.1)
+SCALED = tuple(w * 1.37 + 0.011 for w in DEFAULT_WEIGHTS)
+GLOBAL_ONLY = DISTINCT[:3] + (0.0,) * 13
+LOCAL_ONLY = (0.0,) * 3 + DISTINCT[3:]
+REWARD_SETS = {"DISTINCT": DISTINCT, "SCALED": SCALED, "GLOBAL_ONLY": GLOBAL_ONLY, "LOCAL_ONLY": LOCAL_ONLY}
+
+AGENT_NAMES = ("pickup", "agv", "small_machine", "big_machine", "pkg_blue_1", "pkg_blue_2", "pkg_red", "pkg_green")
+# result-word bit of each reward term (tests/golden/gen_golden.py RESULT_KEYS: bit 0 is `success`).
+# The idle flags are set at action 0 only, by the reference's agents as by the oracle.
+_STATION_TERMS = (("start", 2), ("complete", 4), ("idle", 8))
+_TERM_BITS = {"pickup": (("loaded", 2), ("tray_complete", 4), ("idle", 8)),
+              "agv": (("pickup", 8), ("drop", 16), ("to_packaging", 32), ("moved", 4), ("invalid", 2))}
+REWARD_TERMS = tuple(f"{a}.{k}" for a in AGENT_NAMES for k, _ in _TERM_BITS.get(a, _STATION_TERMS)) + (
+    "orders_completed", "packaged")
+REWARD_FLOOR = 10
+# Terms a policy cannot reach in configuration A (the oracle alone, 200 envs x 280 steps); every
+# other term must be exercised on at least REWARD_FLOOR comparable env-steps, these on none.
+_BLUE2 = ("pkg_blue_2.start", "pkg_blue_2.complete", "pkg_blue_2.idle")
+REWARD_UNREACHABLE = {
+    "random": _BLUE2,
+    "masked": _BLUE2 + ("agv.invalid",),
+    # the heuristic never idles the pickup, never sends the AGV an invalid action and never
+    # signals a packaging station (a2c.py:390-537 proposes START or IDLE there)
+    "heuristic": _BLUE2 + ("pickup.idle", "agv.invalid", "pkg_blue_1.complete", "pkg_red.complete",
+                           "pkg_green.complete"),
+}
+
+
+# Configuration F (STATUS_CFGS) under masked actions: packaging_blue_2 is reached (31 / 161 / 68
+# env-steps); an order is completed on 1 env-step only, which is neither a floor nor unreachable:
+# that term is configuration A's to cover.
+REWARD_UNREACHABLE_F = {"masked": ("agv.invalid",)}
+REWARD_EXEMPT_F = ("orders_completed",)
+
+
+def reward_term_counts(rec, ok=None):
+    """From the oracle's records [steps, n] alone: on how many comparable env-steps (ok, default
+    all) each reward term of REWARD_TERMS is earned."""
+    res = np.asarray(rec["results"]).astype(np.uint32)
+    ok = np.ones(res.shape[:2], bool) if ok is None else np.asarray(ok, bool)
+    out = {}
+    for i, a in enumerate(AGENT_NAMES):
+        for k, bit in _TERM_BITS.get(a, _STATION_TERMS):
+            out[f"{a}.{k}"] = int((ok & ((res[:, :, i] & bit) != 0)).sum())
+    ended = (np.asarray(rec["term"]) | np.asarray(rec["trunc"])).astype(bool)
+    for name, key in (("orders_completed", "orders_completed"), ("packaged", "packaged")):
+        cum = np.asarray(rec[key]).astype(np.int64)
+        prev = np.zeros_like(cum)
+        prev[1:] = np.where(ended[:-1], 0, cum[:-1])      # the counters restart with the episode
+        out[name] = int((ok & (cum - prev > 0)).sum())
+    return out
+
+
+def reward_conditions(counts, unreachable, what="", exempt=()):
+    """The floor that keeps a reward comparison from passing on nothing: every term outside
+    `unreachable` on at least REWARD_FLOOR comparable env-steps, the unreachable ones on none
+    (so the list stays true); `exempt` terms are under neither condition."""
+    assert set(counts) == set(REWARD_TERMS) and set(unreachable) | set(exempt) <= set(REWARD_TERMS)
+    low = {k: v for k, v in counts.items() if k not in unreachable and k not in exempt and v < REWARD_FLOOR}
+    assert not low, (what, "terms below the floor", low)
+    stray = {k: counts[k] for k in unreachable if counts[k]}
+    assert not stray, (what, "terms listed as unreachable were reached", stray)

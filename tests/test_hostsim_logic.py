@@ -31,6 +31,11 @@ def L():
     lib.hs_reset.argtypes = [Pt, Pt, ctypes.c_int, Pt, Pt, Pt, Pt]
     lib.hs_step.argtypes = [Pt, Pt, ctypes.c_int] + [Pt] * 13
     lib.hs_heuristic.argtypes = [Pt, Pt]
+    lib.hs_set_weights.argtypes = [Pt, Pt]
+    lib.hs_local_reward.restype = ctypes.c_double
+    lib.hs_local_reward.argtypes = [Pt, ctypes.c_int, ctypes.c_uint32, ctypes.c_int]
+    lib.hs_global_reward8.restype = ctypes.c_double
+    lib.hs_global_reward8.argtypes = [Pt, ctypes.c_int, ctypes.c_int]
     return lib
 
 
@@ -47,6 +52,11 @@ class HS:
 
     def __del__(self):
         self.L.hs_destroy(self.h)
+
+    def set_weights(self, w):
+        w = np.ascontiguousarray(w, np.float64)
+        assert w.shape == (16,)
+        self.L.hs_set_weights(self.h, w.ctypes.data)
 
     def heuristic(self):
         out = np.zeros((self.n, 8), np.uint8)
@@ -65,7 +75,7 @@ class HS:
             self.ri32, self.ri8, self.rf32, self.rmk)])
 
 
-@pytest.mark.parametrize("policy,cfg,norders,n,steps", [
+CLOSED_FORM_CASES = [
     (0, {}, 30, 64, 1000),
     (1, {}, 30, 64, 1000),
     (0, {"storage_capacity": 2}, 5, 32, 500),
@@ -77,16 +87,33 @@ class HS:
     (1, "C", None, 200, 260),
     (0, "E", None, 200, 260),
     (1, "E", None, 200, 260),
-])
+]
+
+
+@pytest.mark.parametrize("policy,cfg,norders,n,steps", CLOSED_FORM_CASES)
 def test_closed_form_vs_oracle(L, policy, cfg, norders, n, steps):
+    _closed_form_vs_oracle(L, policy, cfg, norders, n, steps)
+
+
+@pytest.mark.parametrize("policy,cfg,norders,n,steps", CLOSED_FORM_CASES + [(1, "F", None, 200, 280)])
+def test_closed_form_vs_oracle_weighted(L, policy, cfg, norders, n, steps):
+    """test_closed_form_vs_oracle's configurations under the DISTINCT reward weights against the
+    oracle under the same weights: rewards (and everything else) byte-equal on comparable env-steps.
+    Configuration F in addition: the one in which packaging_blue_2 earns its three terms."""
+    _closed_form_vs_oracle(L, policy, cfg, norders, n, steps, weights=P.DISTINCT)
+
+
+def _closed_form_vs_oracle(L, policy, cfg, norders, n, steps, weights=None):
     seeds, aseed, scfg = np.arange(n, dtype=np.uint32) + 100, 0, None
     if isinstance(cfg, str):   # a status configuration (parity_util.STATUS_CFGS), with its seeds
         scfg, c = cfg, P.STATUS_CFGS[cfg]
         cfg, norders, aseed, seeds = c["cfg"], c["num_orders"], c["action_seed"], P.status_seeds(n)
     hs = HS(L, n, cfg)
+    if weights is not None:
+        hs.set_weights(weights)
     hs.reset(seeds, norders)
     rec, rst, _ = O.rollout(n, steps, seeds=seeds, gid0=0, num_orders=norders, policy=policy, action_seed=aseed,
-                            record_resets=True, **cfg)
+                            record_resets=True, weights=weights, **cfg)
     masks = hs.mk.copy()
     status, ended = np.zeros((steps, n), np.uint32), np.zeros((steps, n), bool)
     for t in range(steps):
@@ -110,8 +137,14 @@ def test_closed_form_vs_oracle(L, policy, cfg, norders, n, steps):
         masks = hs.rmk.copy()
     # the whole rollout at once: also the reason bits at each episode's first flagged step
     r = P.status_parity(status, rec, (cfg, policy), got_ended=ended)
-    print(f"test_closed_form_vs_oracle {cfg} policy={policy}: {r}")
-    if scfg:
+    print(f"test_closed_form_vs_oracle {cfg} policy={policy} weights={'default' if weights is None else 'DISTINCT'}: {r}")
+    if weights is not None:   # the weighted run compares something: the rewards are not the defaults'
+        rec0, _, _ = O.rollout(n, steps, seeds=seeds, gid0=0, num_orders=norders, policy=policy, action_seed=aseed, **cfg)
+        assert P.bits_equal(rec0["results"], rec["results"]) and (rec0["rewards"] != rec["rewards"]).mean() > 0.9
+    if scfg == "F":
+        ok = (rec["status"] & (O.ST_EXCEPTION | O.ST_PKG_WAIT | O.ST_OBS_OVERFLOW)) == 0
+        P.reward_conditions(P.reward_term_counts(rec, ok), P.REWARD_UNREACHABLE_F["masked"], "F", exempt=P.REWARD_EXEMPT_F)
+    elif scfg:
         P.status_conditions(scfg, r)
         if scfg == "E":
             assert ended.sum() >= 2 * n, "E is there for the bits cleared at auto-resets"
@@ -238,3 +271,56 @@ def test_property_random_configs_and_actions(L):
             if r["term"] or r["trunc"]:
                 o.reset(num_orders=norders)
     run()
+
+
+def _result_dict(a, r):
+    """The reference's action_result booleans of agent a for result word r (gen_golden.RESULT_KEYS)."""
+    if a == 0:
+        keys = ("success", "product_loaded", "tray_completed", "idle_with_orders")
+    elif a == 1:
+        keys = ("success", "invalid_action", "moved", "pickup_success", "drop_success", "delivered_to_packaging")
+    elif a <= 3:
+        keys = ("success", "started_processing", "completed_processing", "idle_with_queue")
+    else:
+        keys = ("success", "started_packaging", "completed_packaging", "idle_with_queue")
+    return {k: bool(r >> i & 1) for i, k in enumerate(keys)}
+
+
+@pytest.mark.parametrize("sname", ["DISTINCT", "SCALED"])
+def test_reward_table_exhaustive(L, sname):
+    """The reward table (build_reward_lut) and its two readers (reward_index / local_reward,
+    global_reward8) of the host build, exhaustively against utils/RewardModel.py's formulas fed the
+    same booleans: every agent, every combination of its result flags (with and without the word's
+    other bits: bit 7 `acted`, the AGV's distance / the packaging count above bit 16), the action
+    0, non-zero, and absent (255, result word 0: actions.get(agent_id, 0) and an empty result);
+    orders 0..3, packaged 0..7 at step sizes 10 and 20.  Bit for bit.  The only place the
+    terms of packaging_blue_2 are certain to be covered."""
+    import importlib
+    R = importlib.import_module("multi-agent-rl-for-fjsp_amd.utils.RewardModel")
+    spec = importlib.import_module("multi-agent-rl-for-fjsp_amd.spec")
+    w = P.REWARD_SETS[sname]
+    rm = R.RewardModel(**dict(zip(P.REWARD_NAMES, w)))
+    assert rm.weights() == tuple(w) and R._WEIGHT_NAMES == P.REWARD_NAMES
+    seen = set()
+    for step in (10, 20):
+        hs = HS(L, 1, {"step_size": step, "pt_small": 6 * step, "pt_big": 12 * step, "pt_packaging": 3 * step})
+        hs.set_weights(w)
+        for a, agent in enumerate(spec.AGENTS):
+            nflag = 6 if a == 1 else 4
+            for flags in range(1 << nflag):
+                for extra in (0, 0x80, 0x00070080):
+                    for act in (0, 1, 2, 7 if a == 1 else 2, 255):
+                        if act == 255 and (flags or extra):
+                            continue        # an absent agent has no result
+                        r = flags | extra
+                        got = L.hs_local_reward(hs.h, a, r, act)
+                        want = rm.calculate_local_reward(agent, 0 if act == 255 else act,
+                                                         {} if act == 255 else _result_dict(a, r))
+                        assert np.float64(got).tobytes() == np.float64(want).tobytes(), (agent, hex(r), act, got, want)
+                        seen.add((a, flags, act == 0))
+        for n in range(4):
+            for p in range(8):
+                got = L.hs_global_reward8(hs.h, n, p)
+                want = rm.calculate_global_reward(n, p, step) / 8
+                assert np.float64(got).tobytes() == np.float64(want).tobytes(), (step, n, p, got, want)
+    assert len(seen) == 2 * (7 * 16 + 64)

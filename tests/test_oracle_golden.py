@@ -128,3 +128,92 @@ def test_oracle_heuristic_drives_golden_traces(tr):
         r = env.step(tr.actions[t])
         if r["term"] or r["trunc"]:
             env.reset(num_orders=tr.num_orders)
+
+
+def _local_sums(w):
+    """Every flag combination's local reward per agent kind under weights w (fjsp_reward_weights
+    order), summed in calculate_local_reward's order: {kind: {flags: sum}}."""
+    W = dict(zip(P.REWARD_NAMES, w))
+    kinds = {"pickup": ("PICKUP_LOAD_REWARD", "PICKUP_TRAY_COMPLETE", "PICKUP_IDLE_PENALTY"),
+             "machine": ("MACHINE_START_REWARD", "MACHINE_COMPLETE_REWARD", "MACHINE_IDLE_PENALTY"),
+             "packaging": ("PACKAGING_START_REWARD", "PACKAGING_COMPLETE_REWARD", "PACKAGING_IDLE_PENALTY"),
+             "agv": ("AGV_DELIVERY_REWARD", "AGV_DELIVERY_REWARD", "AGV_PACKAGING_DELIVERY", "AGV_MOVE_PENALTY",
+                     "AGV_INVALID_ACTION")}
+    out = {}
+    for kind, names in kinds.items():
+        out[kind] = {}
+        for flags in range(1 << len(names)):
+            s = 0.0
+            for i, nm in enumerate(names):
+                if flags >> i & 1:
+                    s += W[nm]
+            out[kind][flags] = s
+    return out
+
+
+def test_reward_sets():
+    """The weight sets of parity_util are what the reward tests rely on: DISTINCT has sixteen
+    pairwise different values, none a multiple of 1/1024 (so sums round), with the defaults' signs;
+    no two sums of up to five of the AGV's terms coincide (other than through the weight its pickup
+    and its drop share), nor two sums of up to three terms of any station, of two different agent
+    kinds included (a lookup into another kind's region of the table shows)."""
+    d = P.DISTINCT
+    assert len(set(d)) == 16 and all(float(x * 1024) != int(x * 1024) for x in d)
+    assert all((x > 0) == (y > 0) for x, y in zip(d, P.DEFAULT_WEIGHTS))
+    assert all(0.3 < x / y < 3.0 for x, y in zip(d, P.DEFAULT_WEIGHTS))
+    assert P.SCALED == tuple(w * 1.37 + 0.011 for w in P.DEFAULT_WEIGHTS)
+    assert P.GLOBAL_ONLY == d[:3] + (0.0,) * 13 and P.LOCAL_ONLY == (0.0,) * 3 + d[3:]
+    seen = {}        # (SCALED keeps the defaults' coincidences: it is there for the rounding)
+    for kind, tab in _local_sums(d).items():
+        for flags, s in tab.items():
+            if flags == 0:
+                continue
+            # the AGV's pickup and drop (bits 0, 1) share AGV_DELIVERY_REWARD: one class per count
+            key = (kind, flags) if kind != "agv" else (kind, bin(flags & 3).count("1"), flags >> 2)
+            assert seen.setdefault(s, key) == key, (s, seen[s], key)
+    assert len(seen) == 3 * 7 + (3 * 8 - 1)
+    # the three global terms tell orders from products from time
+    g = {(n, p): d[0] * n + d[1] * p + d[2] * 10 for n in range(4) for p in range(8)}
+    assert len(set(g.values())) == len(g)
+
+
+def _reward_cases():
+    return [(s, p, seed) for s in P.REWARD_SETS for p, _ in (("unmasked", 30), ("masked", 30), ("heuristic", 3))
+            for seed in (1, 5)]
+
+
+@pytest.mark.parametrize("sname,policy,seed", _reward_cases())
+def test_oracle_reward_weights(golden_dir, sname, policy, seed):
+    """The oracle under non-default reward weights against the reference run with
+    sim.reward_calculator's fields set to them (tests/golden/gen_reward_golden.py): the recorded
+    actions replayed, rewards byte-equal, results, term and trunc equal."""
+    d = np.load(f"{golden_dir}/reward_weights.npz")
+    w = d[f"{sname}_weights"]
+    assert P.bits_equal(w, np.array(P.REWARD_SETS[sname], np.float64))
+    g = lambda k: d[f"{sname}_{policy}_s{seed}_{k}"]  # noqa: E731
+    acts, rew, res, term, trunc = g("actions"), g("rewards"), g("results"), g("term"), g("trunc")
+    num_orders = 3 if policy == "heuristic" else 30
+    env = O.OracleEnv()
+    env.set_weights(w)
+    env.reset(seed=seed, num_orders=num_orders)
+    rows = []
+    for t in range(len(acts)):
+        r = env.step(acts[t])
+        assert r["status"] & O.ST_EXCEPTION == 0
+        assert P.bits_equal(r["rewards"], rew[t]), (t, r["rewards"], rew[t])
+        assert P.bits_equal(r["results"], res[t]) and r["term"] == term[t] and r["trunc"] == trunc[t], t
+        rows.append(r)
+        if r["term"] or r["trunc"]:
+            env.reset(num_orders=num_orders)       # the weights stay with the env
+    # the same through rollout(weights=...), and the default-weight rollout differs
+    seeds = np.array([seed], np.uint32)
+    rec, _, _ = O.rollout(1, len(acts), seeds=seeds, num_orders=num_orders, actions_in=acts[:, None, :], weights=w)
+    assert P.bits_equal(rec["rewards"][:, 0], rew)
+    rec0, _, _ = O.rollout(1, len(acts), seeds=seeds, num_orders=num_orders, actions_in=acts[:, None, :])
+    assert P.bits_equal(rec0["results"], rec["results"]) and not P.bits_equal(rec0["rewards"], rec["rewards"])
+    # the recorded run is no empty one: it earns local terms, and the heuristic completes orders
+    cnt = P.reward_term_counts({k: np.stack([x[k] for x in rows])[:, None] for k in
+                                ("results", "term", "trunc", "orders_completed", "packaged")})
+    assert cnt["pickup.loaded"] >= 10 and cnt["agv.moved"] >= 10, cnt
+    if policy == "heuristic":
+        assert cnt["orders_completed"] >= 3 and cnt["packaged"] >= 3, cnt   # both global counts non-zero, repeatedly
