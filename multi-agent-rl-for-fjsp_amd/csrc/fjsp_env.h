@@ -657,24 +657,30 @@ FJSP_DEV uint32_t agv_fin(Env& E, const Tables& T, const AgvPre& a, int* move_to
 
 // The packaging half of a deferred AGV drop (agv_execute<true>): route the tray to its station
 // (FJSPSimulation.add_tray_to_packaging) with the Resource counts as they are now.
-FJSP_DEV void agv_pack_drop(Env& E, const Tables& T, const Cfg& C, uint32_t pend) {
+// NS: the station slots `st` can name (4; k_step_ag's lane groups hold 4 / G of them each).
+template <int NS>
+FJSP_DEV void agv_pack_push(Env& E, const Tables& T, uint32_t pend, int st) {
     const int carry = (int)((pend >> 1) & 0xFFu), code = (int)((pend >> 9) & 0x1FFFu);
-    const int st = pkg_station(E, C, (int)((pend >> 22) & 3u));
-    if (st < 0) { E.flag(ST_PROD_LOST); return; }
-    const uint32_t lwd = lword<(0xFu << L_PKG)>(E, L_PKG + st);
+    constexpr uint32_t CAND = ((1u << NS) - 1u) << L_PKG;
+    const uint32_t lwd = lword<CAND>(E, L_PKG + st);
     T.snext[carry * T.stride] = (uint8_t)NIL;
     T.scstep[carry * T.stride] = PKG_CONT;
     const uint32_t nd = lwd >> 16;
     if (nd != 0) T.snext[((lwd >> 8) & 0xFFu) * T.stride] = (uint8_t)carry;
-    set_lword<(0xFu << L_PKG)>(E, L_PKG + st,
-                                (nd == 0 ? (uint32_t)carry : (lwd & 0xFFu)) | ((uint32_t)carry << 8) | ((nd + 1) << 16));
+    set_lword<CAND>(E, L_PKG + st,
+                    (nd == 0 ? (uint32_t)carry : (lwd & 0xFFu)) | ((uint32_t)carry << 8) | ((nd + 1) << 16));
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
+    for (int k = 0; k < NS; k++) {
         const uint32_t wk = E.w[20 + k];
         const uint32_t qf = ((wk >> 2) & 0xFFu) == (uint32_t)NIL ? (uint32_t)carry : ((wk >> 2) & 0xFFu);
         const uint32_t nw = (wk & ~(0xFFu << 2) & 0x3FFFFu) | (qf << 2) | (((wk >> 18) + (uint32_t)tc_count(code)) << 18);
         E.w[20 + k] = (st == k) ? nw : wk;
     }
+}
+FJSP_DEV void agv_pack_drop(Env& E, const Tables& T, const Cfg& C, uint32_t pend) {
+    const int st = pkg_station(E, C, (int)((pend >> 22) & 3u));
+    if (st < 0) { E.flag(ST_PROD_LOST); return; }
+    agv_pack_push<4>(E, T, pend, st);
 }
 
 // MachineAgent.execute_action (MachineAgent.py:99-139); grant happens in the run.
@@ -874,6 +880,102 @@ FJSP_DEV void pack_finish(Env& E, const Tables& T, const Cfg& C, int started, in
         const int inflight = E.p_inflight(S) + E.p_queued(S);
         E.w[20 + S] = 3u | ((uint32_t)NIL << 2) | ((uint32_t)(inflight & 0xFF) << 10);
     }
+}
+
+// ---- k_step_ag's packaging wave on lane groups.  With EPW envs per workgroup the wave has
+// G = 64 / EPW lanes per env: lane group g holds stations p * G + g (p < 4 / G) in the station
+// slots p of its own Env (W13+p, W20+p, W26+p, completed count p), so the <S> functions above
+// run unchanged on slot p, and the four stations' completion loops run side by side.  W0's step
+// and W1 are the same in every group; W2 is ORed over the groups after each step.  The caller
+// combines over the groups: pack_lane_room's bits (OR) before pack_lane_step, its return value
+// (sum) and W2 (OR) after it, then pack_lane_apply.  G = 4 / 2 / 1.
+template <int P>
+struct PackSlot { static constexpr int value = P; };
+template <int P, int NP, class F>
+FJSP_DEV void pack_slots(F&& f) {
+    if constexpr (P < NP) { f(PackSlot<P>{}); pack_slots<P + 1, NP>(f); }
+}
+// this lane's stations with room for a drop, at the stations' own bit positions
+template <int G>
+FJSP_DEV uint32_t pack_lane_room(const Env& E, const Cfg& C, int g) {
+    uint32_t room = 0;
+#pragma unroll
+    for (int p = 0; p < 4 / G; p++) room |= (uint32_t)(E.p_inflight(p) < C.pkg_cap) << (p * G + g);
+    return room;
+}
+// The lane's share of K's step: completions due, the AGV's drop if it is routed to one of the
+// lane's stations (room: the four stations' room bits), the actions, the grants.  r[p]: result |
+// action << 8 of station p * G + g.  Returns orders completed | products packaged << 8 by the
+// lane's stations; W1 is left as it was (pack_lane_apply adds the groups' sum).
+template <int G>
+FJSP_DEV uint32_t pack_lane_step(Env& E, const Tables& T, const Cfg& C, int g, uint32_t a1, uint32_t pend, uint32_t room,
+                                 uint32_t* r) {
+    constexpr int NP = 4 / G;
+    const int step = E.step();
+    const uint32_t w1 = E.w[1];
+    bool due[NP];
+    int done[NP], st[NP], orders_done = 0;
+    pack_slots<0, NP>([&](auto p) { due[p.value] = pack_due<p.value>(E, T, step); });
+    pack_slots<0, NP>([&](auto p) { done[p.value] = pack_complete<p.value>(E, T, due[p.value], &orders_done); });
+    if (pend) {   // FJSPSimulation.add_tray_to_packaging: pkg_station on the gathered room bits
+        const uint32_t cand = (uint32_t)nib(nibs(0, 0x4, 0x3, 0x8, 0, 0), (int)((pend >> 22) & 3u)) & room;
+        const int s = __builtin_ffs((int)cand) - 1;
+        if (s < 0) E.flag(ST_PROD_LOST);
+        else if ((s & (G - 1)) == g) agv_pack_push<NP>(E, T, pend, s / G);
+    }
+    pack_slots<0, NP>([&](auto p) {
+        const int act = (int)((a1 >> (8 * (p.value * G + g))) & 0xFFu);
+        st[p.value] = 0;
+        r[p.value] = (pack_execute<p.value>(E, act, &st[p.value]) & 0xFFu) | ((uint32_t)act << 8);
+    });
+    pack_slots<0, NP>([&](auto p) { pack_finish<p.value>(E, T, C, st[p.value], done[p.value]); });
+    bool over = false;
+#pragma unroll
+    for (int p = 0; p < NP; p++) over = over || E.p_queued(p) > 127;
+    if (over) E.flag(ST_OBS_OVERFLOW | ST_DIVERGED);
+    const uint32_t part = (uint32_t)orders_done | ((uint32_t)(E.total_packaged() - (int)(w1 >> 8)) << 8);
+    E.w[1] = w1;
+    return part;
+}
+// sums: pack_lane_step's return values added over the env's lane groups
+FJSP_DEV void pack_lane_apply(Env& E, uint32_t sums) { E.w[1] += sums; }
+// The station slots of lane group g from / to the state words (k_step_ag's launch prologue and
+// epilogue, the host test): word(i) reads state word i of the lane's env.
+template <int G, class W>
+FJSP_DEV void pack_lane_load(Env& E, int g, W&& word) {
+    E.w[1] = word(1);
+    E.w[24] = 0u; E.w[25] = 0u;
+#pragma unroll
+    for (int p = 0; p < 4 / G; p++) {
+        const int s = p * G + g;
+        E.w[7 + L_PKG + p] = word(7 + L_PKG + s);
+        E.w[20 + p] = word(20 + s);
+        E.w[26 + p] = word(26 + s);
+        E.set_p_completed(p, (int)((word(24 + (s >> 1)) >> (16 * (s & 1))) & 0xFFFFu));
+    }
+}
+// env_clear of the packaging words (and K's copies of the step and the status) on a lane
+template <int G>
+FJSP_DEV void pack_lane_clear(Env& E) {
+    E.w[0] = 0u; E.w[1] = 0u; E.w[2] = 0u;
+#pragma unroll
+    for (int p = 0; p < 4 / G; p++) {
+        E.w[7 + L_PKG + p] = (uint32_t)NIL | ((uint32_t)NIL << 8);
+        E.w[20 + p] = (uint32_t)NIL << 2;
+        E.w[26 + p] = 0u;
+    }
+    E.w[24] = 0u; E.w[25] = 0u;
+}
+// the lane's completed counts at their places in W24 (half = 0) / W25 (half = 1): OR over the groups
+template <int G>
+FJSP_DEV uint32_t pack_lane_counts(const Env& E, int g, int half) {
+    uint32_t v = 0;
+#pragma unroll
+    for (int p = 0; p < 4 / G; p++) {
+        const int s = p * G + g;
+        v |= (s >> 1) == half ? (uint32_t)E.p_completed(p) << (16 * (s & 1)) : 0u;
+    }
+    return v;
 }
 
 // ---------------------------------------------------------------- observations

@@ -1171,8 +1171,19 @@ static_assert((AG_MASKS_E0 | AG_MASKS_E2 | AG_MASKS_E3) == (1u << NMASK) - 1u &&
               !(AG_MASKS_E0 & AG_MASKS_E3) && !(AG_MASKS_E2 & AG_MASKS_E3), "mask split");
 // snapshot slot words (PipeSnap, 32 per lane): AM writes q[0..3], K q[4..7]
 enum : int { SA_W0 = 0, SA_ST, SA_W4, SA_W5, SA_W6, SA_L0, SA_M0 = SA_L0 + 6, SA_M1, SA_R01, SA_R23,
-             SK_W1 = 16, SK_P0, SK_N0 = SK_P0 + 4, SK_ST = SK_N0 + 4, SK_G, SK_R45, SK_R67 };
-static_assert(SA_R23 < 16 && SK_R67 < 32, "snapshot slot");
+             SK_W1 = 16 };
+// K's words by the wave's number of lane groups G: with one lane per env the order K has always
+// stored them in; with lane groups, whole 16-byte groups per kind of word, so that group 0 writes
+// the words that are one per env and every group its station's words at their places
+template <int G>
+struct SnapK {
+    static constexpr int ST = G == 1 ? 25 : 17, GS = G == 1 ? 26 : 18, P0 = G == 1 ? 17 : 20, N0 = G == 1 ? 21 : 24,
+                         R45 = G == 1 ? 27 : 28, R67 = R45 + 1;
+    static_assert(G == 1 || (SK_W1 % 4 == 0 && GS < SK_W1 + 4 && P0 % 4 == 0 && N0 % 4 == 0 && R45 % 4 == 0),
+                  "K's snapshot words");
+    static_assert(R67 < 32, "snapshot slot");
+};
+static_assert(SA_R23 < 16, "snapshot slot");
 // P's results for a step (s_res): next_order, W4, W5..W12, pickup result, AGV result, status, drop
 enum : int { RS_NO = 0, RS_W4, RS_W5, RS_R0 = RS_W5 + 8, RS_R1, RS_ST, RS_PEND = 15, RS_N };
 static_assert(RS_N <= 16, "s_res slot");
@@ -1188,6 +1199,21 @@ __device__ __forceinline__ void q_get(const uint4* q, int ng, uint32_t* v) {   /
 __device__ __forceinline__ void q_put(uint4* q, int ng, const uint32_t* v) {
 #pragma unroll
     for (int g = 0; g < ng; g++) q[g * BLOCK] = make_uint4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
+}
+
+// k_step_ag's lane groups: lane g * (BLOCK / G) + e is group g's lane of env e.  OR / sum of a
+// value over an env's G lanes, the result in each of them (every lane of the env active).
+template <int G>
+__device__ __forceinline__ uint32_t lanes_or(uint32_t x) {
+    if constexpr (G >= 4) x |= (uint32_t)__shfl_xor((int)x, BLOCK / 4);
+    if constexpr (G >= 2) x |= (uint32_t)__shfl_xor((int)x, BLOCK / 2);
+    return x;
+}
+template <int G>
+__device__ __forceinline__ uint32_t lanes_sum(uint32_t x) {
+    if constexpr (G >= 4) x += (uint32_t)__shfl_xor((int)x, BLOCK / 4);
+    if constexpr (G >= 2) x += (uint32_t)__shfl_xor((int)x, BLOCK / 2);
+    return x;
 }
 
 __device__ __forceinline__ void snap_put4(PipeSnap& sp, int q0, int lane, const uint32_t* v) {
@@ -1222,26 +1248,27 @@ __device__ __forceinline__ void ag_pin(AgvPre& a) {
 // One emit role's outputs of step t from the step's snapshot (AM's and K's words, SA_* / SK_*):
 // E0 rewards and the pickup's masks, E1 int32 and float32 fields, E2 int8 fields, term, trunc,
 // status and the AGV's masks, E3 the other masks.
-template <int part>
+template <int part, int G>   // G: K's lane groups (the order of its snapshot words, SnapK)
 __device__ __forceinline__ void ag_emit(const uint32_t* v, uint32_t t, uint32_t n, uint32_t ue, const Cfg& C,
                                         const fjsp_out& out) {
+    using SK = SnapK<G>;
     Env E;
 #pragma unroll
     for (int i = 0; i < NSTATE; i++) E.w[i] = 0u;
-    E.w[0] = v[SA_W0]; E.w[2] = v[SA_ST] | v[SK_ST]; E.w[4] = v[SA_W4]; E.w[5] = v[SA_W5];
+    E.w[0] = v[SA_W0]; E.w[2] = v[SA_ST] | v[SK::ST]; E.w[4] = v[SA_W4]; E.w[5] = v[SA_W5];
     E.w[6] = v[SA_W6];
 #pragma unroll
     for (int l = 0; l < 6; l++) E.w[7 + l] = v[SA_L0 + l];
     E.w[17] = v[SA_M0]; E.w[18] = v[SA_M1];
     E.w[1] = v[SK_W1];
 #pragma unroll
-    for (int s = 0; s < 4; s++) { E.w[20 + s] = v[SK_P0 + s]; E.w[26 + s] = v[SK_N0 + s]; }
+    for (int s = 0; s < 4; s++) { E.w[20 + s] = v[SK::P0 + s]; E.w[26 + s] = v[SK::N0 + s]; }
     const StoreSink sink{out.obs_i32, out.obs_i8, out.obs_f32, out.masks, t, n, ue};
     if (part == 0) {
         if (out.rewards) {
-            const uint32_t gs = v[SK_G];
+            const uint32_t gs = v[SK::GS];
             const double g8 = global_reward8(C, (int)(gs & 0xFFFFu), (int)(gs >> 16));
-            const uint32_t rw[4] = {v[SA_R01], v[SA_R23], v[SK_R45], v[SK_R67]};
+            const uint32_t rw[4] = {v[SA_R01], v[SA_R23], v[SK::R45], v[SK::R67]};
 #pragma unroll
             for (int a = 0; a < NA; a++) {
                 const uint32_t r = (rw[a >> 1] >> (16 * (a & 1))) & 0xFFFFu;
@@ -1526,35 +1553,36 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
                 if (!((K_WORDS >> i) & 1u)) S.words[i * n + e] = E.w[i];
         }
     } else if (wave == AG_K) {
+        // The packaging stations on the wave's lane groups (fjsp_env.h, pack_lane_*): lane
+        // 16 * g + e at 16 envs per workgroup holds station g of env e, so the four stations'
+        // completion loops, actions and grants are one instruction stream with every lane on.
+        // Hand-off slots and tables are the env's (index el); what is one per env (s_kpost, W1,
+        // the status and the step's counts in the snapshot) is written by group 0.
+        constexpr int G = BLOCK / EPW, NP = 4 / G;
         const Cfg C = cfg_at(ag_args(), s_lut);
         __builtin_amdgcn_s_setprio(2);
+        const int g = lane / EPW, el = lane % EPW;
+        const int ek = blk * EPW + el;
+        const bool kvalid = ek < S.n;
+        const Tables TK{s_orders + el, s_code + el, s_next + el, s_cstep + el, BLOCK};
         Env E;
 #pragma unroll
         for (int i = 0; i < NSTATE; i++) E.w[i] = 0u;
-        if (valid) {
-#pragma unroll
-            for (int i = 0; i < NSTATE; i++)
-                if ((K_WORDS >> i) & 1u) E.w[i] = S.words[i * n + e];
-            E.w[0] = S.words[e] & 0xFFFFu;   // the step counter (AM owns W0)
+        if (kvalid) {
+            pack_lane_load<G>(E, g, [&](int i) { return S.words[(size_t)i * n + ek]; });
+            E.w[0] = S.words[ek] & 0xFFFFu;   // the step counter (AM owns W0)
         }
         bool trunc_prev = false;
         for (int k = 0; k <= K; k++) {
             AG_T0();
             bool fresh = k == 0;
-            if (valid && k > 0) {   // the reset AM makes at the top of this step, on the packaging words
-                const uint32_t w0a = s_p1[(k - 1) & 1][0][lane].x;   // AM's W0 after step k-1's pickup (P1_W0)
+            if (kvalid && k > 0) {   // the reset AM makes at the top of this step, on the packaging words
+                const uint32_t w0a = s_p1[(k - 1) & 1][0][el].x;   // AM's W0 after step k-1's pickup (P1_W0)
                 const int nord = (int)((w0a >> 16) & 0xFFu);
                 const int all_done = E.ncompleted() == nord && nord > 0 && (int)(w0a >> 24) == nord;
                 if (autoreset && (all_done || trunc_prev)) {   // env_clear of the packaging words
                     fresh = true;
-                    E.w[0] = 0u; E.w[1] = 0u; E.w[2] = 0u;
-#pragma unroll
-                    for (int s = 0; s < 4; s++) {
-                        E.w[7 + L_PKG + s] = (uint32_t)NIL | ((uint32_t)NIL << 8);
-                        E.w[20 + s] = (uint32_t)NIL << 2;
-                        E.w[26 + s] = 0u;
-                    }
-                    E.w[24] = 0u; E.w[25] = 0u;
+                    pack_lane_clear<G>(E);
                 }
             }
             if (k < K) {
@@ -1565,56 +1593,93 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
                     AG_SPIN_T0();
                     ag_spin(&s_flag1, 1u);
                     AG_SPIN_ACC();
-                    if (valid) pend = s_p1[0][1][lane].z;   // P1_PEND
-                } else if (valid && !fresh) {
-                    pend = s_res[k & 1][RS_PEND / 4][lane].w;   // RS_PEND = 15
+                    if (kvalid) pend = s_p1[0][1][el].z;   // P1_PEND
+                } else if (kvalid && !fresh) {
+                    pend = s_res[k & 1][RS_PEND / 4][el].w;   // RS_PEND = 15
                 }
-                if (valid) {
-                    const int step = E.step(), tp0 = E.total_packaged();
-                    const uint32_t a1 = s_act[k % 3][1][lane];
-                    // completions due this step (NORMAL events older than the step's actions)
-                    int done[4], orders_done = 0;
-                    const bool due0 = pack_due<0>(E, TL, step), due1 = pack_due<1>(E, TL, step);
-                    const bool due2 = pack_due<2>(E, TL, step), due3 = pack_due<3>(E, TL, step);
-                    done[0] = pack_complete<0>(E, TL, due0, &orders_done);
-                    done[1] = pack_complete<1>(E, TL, due1, &orders_done);
-                    done[2] = pack_complete<2>(E, TL, due2, &orders_done);
-                    done[3] = pack_complete<3>(E, TL, due3, &orders_done);
-                    if (pend) agv_pack_drop(E, TL, C, pend);   // routing reads the in-flight counts before the run
-                    int st[4] = {0, 0, 0, 0};
-                    uint32_t r[4];
-                    r[0] = pack_execute<0>(E, (int)(a1 & 0xFFu), &st[0]);
-                    r[1] = pack_execute<1>(E, (int)((a1 >> 8) & 0xFFu), &st[1]);
-                    r[2] = pack_execute<2>(E, (int)((a1 >> 16) & 0xFFu), &st[2]);
-                    r[3] = pack_execute<3>(E, (int)(a1 >> 24), &st[3]);
-                    pack_finish<0>(E, TL, C, st[0], done[0]);
-                    pack_finish<1>(E, TL, C, st[1], done[1]);
-                    pack_finish<2>(E, TL, C, st[2], done[2]);
-                    pack_finish<3>(E, TL, C, st[3], done[3]);
-                    E.set_ncompleted(E.ncompleted() + orders_done);
-                    if (E.p_queued(0) > 127 || E.p_queued(1) > 127 || E.p_queued(2) > 127 || E.p_queued(3) > 127)
-                        E.flag(ST_OBS_OVERFLOW | ST_DIVERGED);
-                    s_kpost[k & 1][lane] = E.w[1];
+                if (kvalid) {
+                    const int step = E.step();
+                    const uint32_t a1 = s_act[k % 3][1][el];
+                    if constexpr (G == 1) {   // one lane per env: the four stations in turn
+                        const int tp0 = E.total_packaged();
+                        // completions due this step (NORMAL events older than the step's actions)
+                        int done[4], orders_done = 0;
+                        const bool due0 = pack_due<0>(E, TK, step), due1 = pack_due<1>(E, TK, step);
+                        const bool due2 = pack_due<2>(E, TK, step), due3 = pack_due<3>(E, TK, step);
+                        done[0] = pack_complete<0>(E, TK, due0, &orders_done);
+                        done[1] = pack_complete<1>(E, TK, due1, &orders_done);
+                        done[2] = pack_complete<2>(E, TK, due2, &orders_done);
+                        done[3] = pack_complete<3>(E, TK, due3, &orders_done);
+                        if (pend) agv_pack_drop(E, TK, C, pend);   // routing reads the in-flight counts before the run
+                        int st[4] = {0, 0, 0, 0};
+                        uint32_t r[4];
+                        r[0] = pack_execute<0>(E, (int)(a1 & 0xFFu), &st[0]);
+                        r[1] = pack_execute<1>(E, (int)((a1 >> 8) & 0xFFu), &st[1]);
+                        r[2] = pack_execute<2>(E, (int)((a1 >> 16) & 0xFFu), &st[2]);
+                        r[3] = pack_execute<3>(E, (int)(a1 >> 24), &st[3]);
+                        pack_finish<0>(E, TK, C, st[0], done[0]);
+                        pack_finish<1>(E, TK, C, st[1], done[1]);
+                        pack_finish<2>(E, TK, C, st[2], done[2]);
+                        pack_finish<3>(E, TK, C, st[3], done[3]);
+                        E.set_ncompleted(E.ncompleted() + orders_done);
+                        if (E.p_queued(0) > 127 || E.p_queued(1) > 127 || E.p_queued(2) > 127 || E.p_queued(3) > 127)
+                            E.flag(ST_OBS_OVERFLOW | ST_DIVERGED);
+                        s_kpost[k & 1][el] = E.w[1];
 #pragma unroll
-                    for (int q = 0; q < 4; q++) r[q] = (r[q] & 0xFFu) | (((a1 >> (8 * q)) & 0xFFu) << 8);
-                    const uint32_t v[16] = {E.w[1], E.w[20], E.w[21], E.w[22], E.w[23], E.w[26], E.w[27], E.w[28],
-                                            E.w[29], E.w[2],
-                                            (uint32_t)orders_done | ((uint32_t)(E.total_packaged() - tp0) << 16),
-                                            r[0] | (r[1] << 16), r[2] | (r[3] << 16), 0u, 0u, 0u};
-                    snap_put4(snap[k & 1], 4, lane, v);
+                        for (int q = 0; q < 4; q++) r[q] = (r[q] & 0xFFu) | (((a1 >> (8 * q)) & 0xFFu) << 8);
+                        const uint32_t v[16] = {E.w[1], E.w[20], E.w[21], E.w[22], E.w[23], E.w[26], E.w[27], E.w[28],
+                                                E.w[29], E.w[2],
+                                                (uint32_t)orders_done | ((uint32_t)(E.total_packaged() - tp0) << 16),
+                                                r[0] | (r[1] << 16), r[2] | (r[3] << 16), 0u, 0u, 0u};
+                        snap_put4(snap[k & 1], 4, el, v);
+                    } else {
+                        // routing reads the in-flight counts before the run: gathered from the groups
+                        const uint32_t room = lanes_or<G>(pack_lane_room<G>(E, C, g));
+                        uint32_t r[NP];
+                        const uint32_t sums = lanes_sum<G>(pack_lane_step<G>(E, TK, C, g, a1, pend, room, r));
+                        E.w[2] = lanes_or<G>(E.w[2]);
+                        pack_lane_apply(E, sums);
+                        // K's half of the snapshot: group 0 the words that are one per env, every
+                        // group its stations' words and result halves at their places
+                        using SK = SnapK<G>;
+                        uint32_t* sw = reinterpret_cast<uint32_t*>(&snap[k & 1].q[0][el]);
+                        uint16_t* sh = reinterpret_cast<uint16_t*>(sw);
+                        if (g == 0) {
+                            s_kpost[k & 1][el] = E.w[1];
+                            // the step's orders done | packaged << 16
+                            snap[k & 1].q[SK_W1 / 4][el] = make_uint4(E.w[1], E.w[2], (sums & 0xFFu) | ((sums >> 8) << 16), 0u);
+                        }
+#pragma unroll
+                        for (int p = 0; p < NP; p++) {
+                            const int s = p * G + g;
+                            sw[SK::P0 * BLOCK + s] = E.w[20 + p];
+                            sw[SK::N0 * BLOCK + s] = E.w[26 + p];
+                            sh[2 * SK::R45 * BLOCK + s] = (uint16_t)r[p];
+                        }
+                    }
                     trunc_prev = step >= C.max_steps;
                     E.set_step(step + 1);
                 }
-            } else if (valid) {
-                s_kpost[2][lane] = E.w[2];   // status bits for AM's final store of W2
+            } else if (kvalid && g == 0) {
+                s_kpost[2][el] = E.w[2];   // status bits for AM's final store of W2
             }
             AG_ACC(ag_busy);
             AG_BARRIER();
         }
-        if (valid) {
+        if (kvalid) {
+            const uint32_t c01 = lanes_or<G>(pack_lane_counts<G>(E, g, 0)), c23 = lanes_or<G>(pack_lane_counts<G>(E, g, 1));
 #pragma unroll
-            for (int i = 0; i < NSTATE; i++)
-                if ((K_WORDS >> i) & 1u) S.words[i * n + e] = E.w[i];
+            for (int p = 0; p < NP; p++) {
+                const size_t s = (size_t)(p * G + g);
+                S.words[(7 + L_PKG + s) * n + ek] = E.w[7 + L_PKG + p];
+                S.words[(20 + s) * n + ek] = E.w[20 + p];
+                S.words[(26 + s) * n + ek] = E.w[26 + p];
+            }
+            if (g == 0) {
+                S.words[n + ek] = E.w[1];
+                S.words[(size_t)24 * n + ek] = c01;
+                S.words[(size_t)25 * n + ek] = c23;
+            }
         }
     } else if (wave == AG_P) {
         const Cfg C = cfg_at(ag_args(), s_lut);
@@ -1739,7 +1804,7 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
                     __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the snapshot arrived
                     )
                     AG_MARK(1);
-                    ag_emit<part>(v, t, n, ue, C, eo);
+                    ag_emit<part, BLOCK / EPW>(v, t, n, ue, C, eo);
                 }
                 AG_MARK(2);
                 AG_ACC(ag_busy);
