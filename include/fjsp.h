@@ -79,7 +79,7 @@ extern "C" {
 #define FJSP_STATUS_PROD_LOST    0x10u  /* no packaging station with capacity: products lost (reference behaviour) */
 #define FJSP_STATUS_OVERWRITE    0x20u  /* machine START overwrote an unsignalled tray (reference behaviour) */
 #define FJSP_STATUS_SLOT_OVERFLOW 0x40u /* more trays in one episode than the slot arena holds (not emulated) */
-#define FJSP_STATUS_SPIN_TIMEOUT 0x80u  /* a wave of a multi-wave step kernel gave up waiting for another wave's
+#define FJSP_STATUS_SPIN_TIMEOUT 0x80u  /* a wave of k_step_ag gave up waiting for another wave's
                                            hand-off (bounded wait; results of that workgroup are invalid) */
 
 /* action_mode for fjsp_step_many */
@@ -196,18 +196,22 @@ int fjsp_set_stream(fjsp_handle* h, void* hip_stream);
  * table ahead on a fourth wave, so auto-resets need no MT draws on the critical path; the
  * results are identical either way); "agents" (0/1, default 1: uniform-random actions with LDS
  * tables and the pre-draw run k_step_ag, the env's agents split over eight wavefronts of its
- * workgroup; identical results); "ag_envs" (0/16/32/64, default 0 = auto: envs per k_step_ag
+ * workgroup; identical results; 0 sends those launches to k_step_pipe<lds,2emit,predraw>, which
+ * runs every agent on its one sim wave: 2.87 against 1.18 us per step at 4 096 envs, 30 orders,
+ * 200-step launches; the tests' independent reference for k_step_ag); "ag_envs" (0/16/32/64, default 0 = auto: envs per k_step_ag
  * workgroup, lanes >= ag_envs idle; auto = 64 for launches of fewer than 64 steps, else the
  * fewest that give every workgroup a CU of its own; identical results); "step_envs" (0/16/32/64,
  * default 0 = 64; ABI 12: envs per k_step workgroup (fjsp_step), lanes >= step_envs idle;
  * identical results); "env_id_base" (0..2^32-1, default 0: the handle is the shard [value, value + N) of a
  * larger job — every env's MT19937 stream is re-seeded to np.random.seed(value + e), exactly
  * the stream env value + e of one big handle starts from; stream-ordered); "spin_cap"
- * (256..2^31-1, default 2^22: sleep iterations, checked every 256 a wave of a multi-wave step kernel waits for another
- * wave's hand-off before it gives up and flags FJSP_STATUS_SPIN_TIMEOUT / fjsp_faults); "test_stall"
- * (0..2^20, default 0; tests only: later k_step_ag and k_step_pipe<lds,2emit,predraw> launches
+ * (256..2^31-1, default 2^22: sleep iterations, checked every 256, a wave of k_step_ag waits for another
+ * wave's hand-off before it gives up and flags FJSP_STATUS_SPIN_TIMEOUT / fjsp_faults; no other step
+ * kernel has a hand-off wait); "test_stall"
+ * (0..2^20, default 0; tests only: later k_step_ag launches
  * run a test build in which workgroup 0's owner wave sleeps value x ~8k cycles before its first
- * step, so that the other waves' bounded waits give up and the give-up path runs).  spin_cap and test_stall are not part of a snapshot.
+ * step, so that the other waves' bounded waits give up and the give-up path runs; no other kernel
+ * has such a build).  spin_cap and test_stall are not part of a snapshot.
  * Library-wide (h may be NULL; ABI 10): "policy_xmap" (0..3, default 0), "policy_dedup" (0/1,
  * default 1), "policy_split" (0/1, default 1) — the variants of the A2C policy launches listed at
  * fjsp_a2c_policy; "wgrad_waves" (8/16, default 16; ABI 12) — fjsp_a2c_wgrad's workgroups of 8 or
@@ -631,8 +635,8 @@ int fjsp_last_kernel_ms(fjsp_handle* h, float* ms);
 /* Name of the kernel variant the last fjsp_step / fjsp_step_many launched ("" before any):
  * e.g. "k_step_pipe<lds>" (rocprof shows it as k_step_pipe). */
 const char* fjsp_last_kernel(const fjsp_handle* h);
-/* Fault word of the handle's multi-wave step kernels (k_step_ag, k_step_pipe with hand-offs;
- * not changed by fjsp_restore):
+/* Fault word of the handle's step launches (only k_step_ag, the one kernel with flag hand-offs
+ * between its waves, can raise it; not changed by fjsp_restore):
  * bit 0 = some workgroup's wave gave up a bounded wait for another wave's hand-off (its envs
  * also carry FJSP_STATUS_SPIN_TIMEOUT).  Never set by a correct kernel: the bound (option
  * "spin_cap", sleep iterations, default 2^22 ~ 0.1 s) exists so that a hand-off bug ends the

@@ -416,7 +416,7 @@ constexpr uint32_t DROP_LISTS = (1u << L_STORAGE) | (1u << L_M0Q) | (1u << L_M1Q
 // state words are updated with selects, so a wavefront whose lanes take all 8 actions executes
 // one path instead of the union of 8 branchy ones.  Only the memory operations sit in (two)
 // small guarded blocks: the PICKUP pop's loads and the DROP push's stores.
-// DEFER (the pipelined kernel's AGV-ahead wave): a drop at packaging is not routed here — the
+// DEFER (k_step_ag's AGV wave P, which runs a step ahead): a drop at packaging is not routed here — the
 // station choice needs the Resource counts after the current run phase — but returned in
 // *pend (1 | slot << 1 | code << 9 | colour << 22) for agv_pack_drop.
 template <bool DEFER = false>
@@ -1229,17 +1229,10 @@ FJSP_DEV double global_reward8(const Cfg& C, int orders_done, int packaged) {
 
 // Actions in dict order, then env.run in closed form.  actions[a] for agent a (canonical order);
 // order = execution order (CANON -> 0..7).  Fills res[8]; returns the shared global reward / 8.
-struct NoMid {
-    FJSP_DEV void operator()(const Env&, int) const {}
-};
-// mid(E, move_to) runs right after the machines' actions (the pipelined kernel hands the
-// pickup / AGV state to other waves there).  ahead: the pickup station and the AGV already
-// acted (on those waves, from the previous step's hand-off); res[0], res[1] hold their results,
-// the caller applied their state words and ahead_move is the AGV's move target.
-template <bool CANON, class Mid = NoMid>
+template <bool CANON>
 FJSP_DEV double env_advance(Env& E, const Tables& T, const Cfg& C, const int* act, const uint8_t* order,
-                            uint32_t* res, Mid mid = Mid(), bool ahead = false, int ahead_move = 0) {
-    int move_to = ahead ? ahead_move : 0, m_start[2] = {-1, -1}, p_started[4] = {0, 0, 0, 0};
+                            uint32_t* res) {
+    int move_to = 0, m_start[2] = {-1, -1}, p_started[4] = {0, 0, 0, 0};
     const int products_before = E.total_packaged();
     // 1. actions in dict order (FJSPSimulation.py:172-174)
 #pragma unroll
@@ -1249,8 +1242,8 @@ FJSP_DEV double env_advance(Env& E, const Tables& T, const Cfg& C, const int* ac
         uint32_t r = 0;
         if (ac != 255) {
             switch (a) {
-            case 0: r = ahead ? res[0] : pickup_execute(E, T, C, ac); break;
-            case 1: r = ahead ? res[1] : agv_execute(E, T, C, ac, &move_to); break;
+            case 0: r = pickup_execute(E, T, C, ac); break;
+            case 1: r = agv_execute(E, T, C, ac, &move_to); break;
             case 2: r = machine_execute<0>(E, T, ac, &m_start[0]); break;
             case 3: r = machine_execute<1>(E, T, ac, &m_start[1]); break;
             case 4: r = pack_execute<0>(E, ac, &p_started[0]); break;
@@ -1261,7 +1254,6 @@ FJSP_DEV double env_advance(Env& E, const Tables& T, const Cfg& C, const int* ac
         }
         res[a] = r;
         if (CANON) FJSP_STAMP_AGENT(E, i);
-        if (CANON && i == 3) mid(E, move_to);
     }
     FJSP_STAMP(E, 1);
     // 2. env.run(until=now+step_size) in closed form

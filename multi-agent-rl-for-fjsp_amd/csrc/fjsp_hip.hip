@@ -338,6 +338,15 @@ __device__ __forceinline__ void tables_copy_in(const DevState& S, const Tables& 
             }
     }
 }
+// ... and back at the end of the launch.
+__device__ __forceinline__ void tables_copy_out(const DevState& S, const Tables& T, int e, int norders, int nslots) {
+    for (int o = 0; o < norders; o++) S.orders[(size_t)o * S.n + e] = T.orders[o * T.stride];
+    for (int q = 0; q < nslots; q++) {
+        S.scode[(size_t)q * S.n + e] = T.scode[q * T.stride];
+        S.snext[(size_t)q * S.n + e] = T.snext[q * T.stride];
+        S.scstep[(size_t)q * S.n + e] = T.scstep[q * T.stride];
+    }
+}
 
 // K fused steps.  LDS = true stages the env's order table and tray-slot arena in LDS for
 // the whole launch (one 64-lane workgroup = 64 envs, 97.5 KB of LDS), so the linked-list
@@ -380,6 +389,8 @@ __global__ void __launch_bounds__(BLOCK) k_step_many(DevState S, Cfg C, int K, u
         FJSP_STAMP(E, 0);
         step_and_emit<true, FULL>(E, T, C, S, e, act, nullptr, autoreset, out, (uint32_t)k);
     }
+    // tables_copy_out, spelled out: through the helper the compiler picks other compare encodings
+    // all over the kernel, <lds> 0.5 % slower per step (profiles/pipe_ahead_removed/)
     if constexpr (LDS) {
         for (int o = 0; o < E.norders(); o++) S.orders[(size_t)o * S.n + e] = T.orders[o * BLOCK];
         for (int s = 0; s < E.slot_next(); s++) {
@@ -395,7 +406,8 @@ __global__ void __launch_bounds__(BLOCK) k_step_many(DevState S, Cfg C, int K, u
     )
 }
 
-// K fused steps, pipelined over 2 or 3 wavefronts per 64-env workgroup (lean outputs only).
+// K fused steps, pipelined over 2 or 3 wavefronts per 64-env workgroup, plus an optional
+// pre-draw wave (PG, below); lean outputs only.  Every agent of the env runs on the sim wave.
 // Wave 0 ("sim") advances the env state: actions, action phase, SimPy run, auto-reset; after
 // each step it leaves a snapshot of the pre-reset state (the 22 words the observation reads),
 // the 8 action-result words and the step's completed orders / packaged products in LDS.  The
@@ -781,9 +793,9 @@ __device__ __forceinline__ fjsp_out out_at(const FJSP_KARG A* a) {
     return r;
 }
 
-// STALL: the test build of the kernel (option "test_stall"): the production instances carry no
-// code of it (any code there shifted k_step_ag's register allocation: +1.2 % per step, measured).
-template <bool LDS, int NEMIT, bool PG = false, bool STALL = false>
+// The waves of a workgroup meet only at the one barrier per step: the kernel has no flag
+// hand-off, so no wait that could give up (ST_SPIN_TIMEOUT, fault bit 0: k_step_ag only).
+template <bool LDS, int NEMIT, bool PG = false>
 __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 2))) k_step_pipe(DevState S, Cfg Ck, int K, uint64_t seed,
                                                               uint32_t gid0, uint32_t step0, int mode, int autoreset,
                                                               fjsp_out out) {
@@ -795,18 +807,6 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
     __shared__ uint32_t s_nxt[PG ? MAX_ORDERS * BLOCK : 1];
     __shared__ uint32_t s_mb[PG ? 4 : 1][2][BLOCK];   // sim: epi | nord << 8, cursor word; pre-draw: ready, cursor
     __shared__ uint4 s_cp[PG ? PG_CR : 1][3][BLOCK];   // MT rows in flight (pre-draw copies)
-    // Pickup + AGV ahead (PG, uniform-random actions).  Neither agent's next action depends on
-    // anything the packaging agents or the run phase of the current step change, except where
-    // a drop at packaging routes the tray (deferred: agv_pack_drop).  So after the machines'
-    // actions of step k the sim wave posts the words they read (s_post, then s_postflag = k+1);
-    // emit wave 1 runs step k+1's pickup on them (s_pick, s_pickflag = k+1), emit wave 2 step
-    // k+1's AGV on both, while the sim wave finishes step k; at the top of step k+1 the sim
-    // wave applies both (lanes that just reset run the two agents themselves).
-    constexpr int NPOST = 10;   // W0, W4, W5, W6 (loc after the move), W7..W12 (lists 0..5)
-    __shared__ uint32_t s_post[PG ? NPOST : 1][BLOCK];
-    __shared__ uint32_t s_pick[PG ? 6 : 1][BLOCK];   // next_order, W4, W5, W7, result, flags
-    __shared__ uint32_t s_agv[PG ? 12 : 1][BLOCK];   // W5, W6, W7..W12, result, flags, move, pend
-    __shared__ uint32_t s_postflag, s_pickflag, s_abort, s_cap;
     __shared__ uint16_t s_code[LDS ? MAX_SLOTS * BLOCK : 1];
     __shared__ uint8_t s_next[LDS ? MAX_SLOTS * BLOCK : 1];
     __shared__ uint16_t s_cstep[LDS ? MAX_SLOTS * BLOCK : 1];
@@ -826,9 +826,7 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
         s_act[0][0][lane] = pack_actions(act, 0);
         s_act[0][1][lane] = pack_actions(act, 4);
     }
-    if (threadIdx.x == 0) { s_abort = 0; s_cap = aux_words(S)[AUX_SPIN_CAP]; }
     if constexpr (PG) {   // step-0 mailboxes
-        if (threadIdx.x == 0) { s_postflag = 0; s_pickflag = 0; }
         if (wave == 0 && valid) {
             s_mb[0][0][lane] = ((S.words[e] >> 16) & 0xFFu) << 8;   // episode counter 0 | num_orders
             s_mb[1][0][lane] = S.words[3 * n + e];
@@ -847,9 +845,6 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
         }
     }
     __syncthreads();
-    if constexpr (STALL) {
-        if (wave == 0 && blockIdx.x == 0) stall_for_test(S);
-    }
     if (wave == 0) {
         // the config and the action stream read in this branch (kargs_flat)
         const PipeArgs* pa = kargs_flat<PipeArgs>();
@@ -875,7 +870,6 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
         E.st_t0 = __builtin_amdgcn_s_memtime();
         )
         int epi = 0;   // episodes started in this launch (mod 256), the pre-draw tag
-        bool fresh = true;   // this step's pickup runs here (first step of the launch / after a reset)
         for (int k = 0; k <= K; k++) {
             if (k < K && valid) {
                 int act[NA];
@@ -888,39 +882,8 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
                 }
                 FJSP_STAMP(E, 0);
                 uint32_t res[NA];
-                bool ahead = false;
-                int ahead_move = 0;
-                if constexpr (PG) {
-                    if (pre && !fresh) {   // step k's pickup and AGV ran on the emit waves
-                        E.w[0] = (E.w[0] & 0x00FFFFFFu) | (s_pick[0][lane] << 24);
-                        E.w[4] = s_pick[1][lane];
-                        res[0] = s_pick[4][lane];
-#pragma unroll
-                        for (int i = 0; i < 8; i++) E.w[5 + i] = s_agv[i][lane];   // W5..W12
-                        res[1] = s_agv[8][lane];
-                        E.w[2] |= s_pick[5][lane] | s_agv[9][lane];
-                        ahead_move = (int)s_agv[10][lane];
-                        const uint32_t pend = s_agv[11][lane];
-                        if (pend) agv_pack_drop(E, T, C, pend);
-                        ahead = true;
-                    }
-                }
-                auto mid = [&](const Env& Em, int mv) {
-                    if constexpr (PG) {
-                        if (pre) {
-                            s_post[0][lane] = Em.w[0];
-                            s_post[1][lane] = Em.w[4];
-                            s_post[2][lane] = Em.w[5];
-                            s_post[3][lane] = mv ? ((Em.w[6] & ~7u) | (uint32_t)mv) : Em.w[6];
-#pragma unroll
-                            for (int i = 0; i < 6; i++) s_post[4 + i][lane] = Em.w[7 + i];
-                            __hip_atomic_store(&s_postflag, (uint32_t)(k + 1), __ATOMIC_RELEASE,
-                                               __HIP_MEMORY_SCOPE_WORKGROUP);
-                        }
-                    }
-                };
                 const int nc0 = E.ncompleted(), tp0 = E.total_packaged();
-                (void)env_advance<true>(E, T, C, act, nullptr, res, mid, ahead, ahead_move);   // g/8: the emit wave
+                (void)env_advance<true>(E, T, C, act, nullptr, res);   // g/8: the emit wave
                 flag_obs_overflow(E);
                 uint32_t v[SNAP_N];
                 int j = 0;
@@ -938,9 +901,7 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
                 const int truncated = E.step() >= C.max_steps;
                 FJSP_STAMP(E, 3);
                 E.set_step(E.step() + 1);
-                fresh = false;
                 if (autoreset && (all_done || truncated)) {   // reset(seed=None)
-                    fresh = true;
                     if constexpr (PG) {
                         const uint32_t pr = s_mb[2][k & 1][lane];
                         if ((pr & 1u) && ((pr >> 1) & 0xFFu) == (uint32_t)epi && (int)((pr >> 9) & 0x7Fu) == nord)
@@ -961,19 +922,9 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
             __syncthreads();
         }
         if (valid) {
-            if constexpr (LDS) {
-                for (int o = 0; o < E.norders(); o++) S.orders[(size_t)o * S.n + e] = T.orders[o * BLOCK];
-                for (int q = 0; q < E.slot_next(); q++) {
-                    S.scode[(size_t)q * S.n + e] = T.scode[q * BLOCK];
-                    S.snext[(size_t)q * S.n + e] = T.snext[q * BLOCK];
-                    S.scstep[(size_t)q * S.n + e] = T.scstep[q * BLOCK];
-                }
-            }
-            // every wait happened before the last barrier: a give-up is visible here
-            if (s_abort) E.w[2] |= ST_SPIN_TIMEOUT | ST_DIVERGED;
+            if constexpr (LDS) tables_copy_out(S, T, e, E.norders(), E.slot_next());
             env_store(E, S.words, S.n, e);
         }
-        if (lane == 0) report_abort(S, s_abort);
         FJSP_DIAG(
         if (lane == 0)
             for (int i = 0; i < 8; i++) atomicAdd((unsigned long long*)&g_stamps[i], (unsigned long long)E.st_acc[i]);
@@ -998,12 +949,8 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
             FJSP_DIAG(
             const uint64_t et0 = __builtin_amdgcn_s_memtime();
             )
-            // order within a step (PG): wave 1 first draws step k + 1's actions, writes step
-            // k - 1's rewards and runs step k + 1's pickup as soon as the sim wave posts (early
-            // in step k), then the observation fields; wave 2 writes its fields, then runs step
-            // k + 1's AGV (needs that pickup)
-            int act_next[NA];
-            if (part == 0 && pre && k + 1 < K) {
+            if (part == 0 && pre && k + 1 < K) {   // step k + 1's uniform actions
+                int act_next[NA];
                 synth_uniform(seed, gid0 + (uint32_t)e, step0 + (uint32_t)(k + 1), act_next);
                 s_act[(k + 1) & 1][0][lane] = pack_actions(act_next, 0);
                 s_act[(k + 1) & 1][1][lane] = pack_actions(act_next, 4);
@@ -1029,29 +976,6 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
                          g8 + C.lut[reward_index(a, r & 0xFFFF00FFu, (int)((r >> 8) & 0xFu))]);
                 }
             }
-            if constexpr (PG) {   // step k + 1's pickup, once the sim wave has posted its state
-                if (part == 0 && pre && k + 1 < K) {
-                    spin_until(&s_postflag, (uint32_t)(k + 1), &s_abort, &s_cap);
-                    if (valid) {
-                        Env Ep;
-#pragma unroll
-                        for (int i = 0; i < NSTATE; i++) Ep.w[i] = 0u;
-                        Ep.w[0] = s_post[0][lane];
-                        Ep.w[4] = s_post[1][lane];
-                        Ep.w[5] = s_post[2][lane];
-                        Ep.w[7 + L_PREADY] = s_post[4 + L_PREADY][lane];
-                        const Tables Tp{s_orders + lane, s_code + lane, s_next + lane, s_cstep + lane, BLOCK};
-                        const uint32_t r = pickup_execute(Ep, Tp, C, act_next[0]);
-                        s_pick[0][lane] = Ep.w[0] >> 24;
-                        s_pick[1][lane] = Ep.w[4];
-                        s_pick[2][lane] = Ep.w[5];
-                        s_pick[3][lane] = Ep.w[7 + L_PREADY];
-                        s_pick[4][lane] = r;
-                        s_pick[5][lane] = Ep.w[2];
-                    }
-                    __hip_atomic_store(&s_pickflag, (uint32_t)(k + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-            }
             if (have) {
                 if (part == 0) {   // int32 / float32 fields (+ everything when NEMIT == 1)
                     PartSink<NEMIT == 1 ? -1 : 0> ps{sink};
@@ -1067,34 +991,7 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
                     const int truncated = E.step() >= C.max_steps;
                     if (out.term) st32(out.term, t * n + ue, (uint8_t)all_done);
                     if (out.trunc) st32(out.trunc, t * n + ue, (uint8_t)truncated);
-                    if (out.status)
-                        st32(out.status, t * n + ue, E.status() | (s_abort ? ST_SPIN_TIMEOUT | ST_DIVERGED : 0u));
-                }
-            }
-            if constexpr (PG) {   // step k + 1's AGV, on the posted state and that step's pickup
-                if (part == 1 && pre && k + 1 < K) {
-                    spin_until(&s_pickflag, (uint32_t)(k + 1), &s_abort, &s_cap);
-                    if (valid) {
-                        Env Ea;
-#pragma unroll
-                        for (int i = 0; i < NSTATE; i++) Ea.w[i] = 0u;
-                        Ea.w[5] = s_pick[2][lane];
-                        Ea.w[6] = s_post[3][lane];
-#pragma unroll
-                        for (int i = 0; i < 6; i++) Ea.w[7 + i] = s_post[4 + i][lane];
-                        Ea.w[7 + L_PREADY] = s_pick[3][lane];
-                        const Tables Ta{s_orders + lane, s_code + lane, s_next + lane, s_cstep + lane, BLOCK};
-                        const int a1 = (int)((s_act[(k + 1) & 1][0][lane] >> 8) & 0xFFu);
-                        int mv = 0;
-                        uint32_t pend = 0;
-                        const uint32_t r = agv_execute<true>(Ea, Ta, C, a1, &mv, &pend);
-#pragma unroll
-                        for (int i = 0; i < 8; i++) s_agv[i][lane] = Ea.w[5 + i];
-                        s_agv[8][lane] = r;
-                        s_agv[9][lane] = Ea.w[2];
-                        s_agv[10][lane] = (uint32_t)mv;
-                        s_agv[11][lane] = pend;
-                    }
+                    if (out.status) st32(out.status, t * n + ue, E.status());
                 }
             }
             FJSP_DIAG(
@@ -1299,7 +1196,9 @@ __device__ __forceinline__ void ag_emit(const uint32_t* v, uint32_t t, uint32_t 
 
 // EPW: envs per workgroup (64, 32 or 16; lanes >= EPW idle): fewer envs per CU spread N envs
 // over more CUs (every workgroup keeps its 150 KB of LDS, so one workgroup per CU).
-template <int EPW, bool STALL = false>   // STALL: the test build (option "test_stall"), see k_step_pipe
+// STALL: the test build of the kernel (option "test_stall"): the production instances carry no
+// code of it (any code there shifted the register allocation: +1.2 % per step, measured).
+template <int EPW, bool STALL = false>
 __global__ void __launch_bounds__(AG_WAVES * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 2)))
 k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step0, int autoreset, fjsp_out out) {
     static_assert(EPW == 64 || EPW == 32 || EPW == 16, "envs per workgroup");
@@ -2604,9 +2503,7 @@ int fjsp_step_many(fjsp_handle* h, int32_t K, uint64_t action_seed, uint32_t env
     case SV_PIPE_2EMIT: launch(k_step_pipe<false, 2>); break;
     case SV_PIPE_LDS_1EMIT: launch(k_step_pipe<true, 1>); break;
     case SV_PIPE_LDS_2EMIT: launch(k_step_pipe<true, 2>); break;
-    case SV_PIPE_LDS_2EMIT_PREDRAW:
-        p.stall ? launch(k_step_pipe<true, 2, true, true>) : launch(k_step_pipe<true, 2, true>);
-        break;
+    case SV_PIPE_LDS_2EMIT_PREDRAW: launch(k_step_pipe<true, 2, true>); break;
     case SV_AG:
         with_epw(p.epw, [&](auto epw) {
             constexpr int EPW = decltype(epw)::value;

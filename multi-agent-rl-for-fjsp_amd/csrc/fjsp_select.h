@@ -20,7 +20,7 @@ struct StepOpts {
     int agents;       // agent-group pipeline k_step_ag for uniform-random actions
     int ag_envs;      // k_step_ag envs per workgroup: 64 / 32 / 16, 0 = auto
     int step_envs;    // k_step envs per workgroup: 64 / 32 / 16, 0 = 64
-    int test_stall;   // tests: launch the STALL builds of the multi-wave kernels
+    int test_stall;   // tests: launch k_step_ag's STALL build
 };
 
 enum StepFamily : int { STEP_MANY, STEP_PIPE, STEP_AG };
@@ -39,7 +39,7 @@ struct StepKernel {
     bool lds, full;   // k_step_many<LDS, FULL>, k_step_pipe<LDS, ..>
     int nemit;        // k_step_pipe<.., NEMIT, ..>
     bool predraw;     // k_step_pipe<.., PG>
-    bool has_stall;   // a STALL (test_stall) build exists
+    bool has_stall;   // a STALL (test_stall) build exists: k_step_ag only, the one kernel with bounded waits
 };
 
 constexpr StepKernel STEP_KERNELS[SV_COUNT] = {
@@ -51,7 +51,7 @@ constexpr StepKernel STEP_KERNELS[SV_COUNT] = {
     /* SV_PIPE_2EMIT */             {"k_step_pipe<2emit>", STEP_PIPE, false, false, 2, false, false},
     /* SV_PIPE_LDS_1EMIT */         {"k_step_pipe<lds,1emit>", STEP_PIPE, true, false, 1, false, false},
     /* SV_PIPE_LDS_2EMIT */         {"k_step_pipe<lds,2emit>", STEP_PIPE, true, false, 2, false, false},
-    /* SV_PIPE_LDS_2EMIT_PREDRAW */ {"k_step_pipe<lds,2emit,predraw>", STEP_PIPE, true, false, 2, true, true},
+    /* SV_PIPE_LDS_2EMIT_PREDRAW */ {"k_step_pipe<lds,2emit,predraw>", STEP_PIPE, true, false, 2, true, false},
     // k_step_ag<EPW>: fixed roles (four emit waves, pre-draw); every EPW reports the one name
     /* SV_AG */                  {"k_step_ag<lds,predraw>", STEP_AG, true, false, 4, true, true},
 };

@@ -197,8 +197,13 @@ void agv_replay(int envs, int steps, int num_orders, uint64_t seed, int64_t* out
             }
             const AgvPre pre = agv_pre(S.E, TS, C, nxt[1]);   // step k + 1's AGV, its own half
             if (pend) agv_pack_drop(S.E, TS, C, pend);
+            // the rest of step k: the move lands inside the run (machine_execute does not read the
+            // location), the pickup station and the AGV have acted (255 = no action)
+            if (mv) S.E.set_loc(mv);
+            int rest[NA];
+            for (int a = 0; a < NA; a++) rest[a] = a < 2 ? 255 : act[a];
+            env_advance<true>(S.E, TS, C, rest, nullptr, res);
             res[0] = r0; res[1] = r1;
-            env_advance<true>(S.E, TS, C, act, nullptr, res, NoMid(), true, mv);
             // compare: state words, results, the live tables.  The carried slot's link is dead (no
             // list holds it; every push rewrites it) and agv_pre may already have cleared it.
             bool ok = memcmp(R.E.w, S.E.w, sizeof(R.E.w)) == 0;

@@ -249,27 +249,26 @@ def test_agents_envs_per_workgroup(G, epw):
     _same_views(runs[0][1], runs[1][1])
 
 
-@pytest.mark.parametrize("agents", [1, 0])
-def test_bounded_handoff_waits(G, agents):
-    """The hand-off waits of the multi-wave kernels (k_step_ag's flag spins, k_step_pipe's
-    mailboxes) are bounded.  At the default bound a 4 096-env x 1 024-step bench launch never
+def test_bounded_handoff_waits(G):
+    """k_step_ag's hand-off waits (its flag spins; no other step kernel has any) are bounded.
+    At the default bound a 4 096-env x 1 024-step bench launch never
     gives up (fault word 0, no env carries FJSP_STATUS_SPIN_TIMEOUT).  At the smallest bound (256
     sleeps, ~7 us: the first step waits that long for the tables' copy-in) a wait may give up:
     the launch still ends, and a workgroup that gave up
     flags every env it holds (status bit 0x80 | DIVERGED, fault word bit 0) while workgroups that
     did not are byte-identical to the unbounded run; with one workgroup's owner wave held back
     (option "test_stall") the give-up path provably runs."""
-    env = _env(G, 4096, agents)
+    env = _env(G, 4096, 1)
     env.reset(num_orders=30)
     st = G.to_np(env.rollout(1024, action_seed=3, policy="random"))["status"]
     torch.cuda.synchronize()
-    assert env.last_kernel() == (AG if agents else "k_step_pipe<lds,2emit,predraw>")
+    assert env.last_kernel() == AG
     assert env.faults() == 0 and not (st & 0x80).any()
     n = 256
-    ref = _env(G, n, agents)
+    ref = _env(G, n, 1)
     ref.reset(num_orders=30)
     r0 = G.to_np(ref.rollout(64, action_seed=5, policy="random"))
-    tight = _env(G, n, agents)
+    tight = _env(G, n, 1)
     G.native.check(G.native.lib().fjsp_set_option(tight.handle, b"spin_cap", 256))
     tight.reset(num_orders=30)
     r1 = G.to_np(tight.rollout(64, action_seed=5, policy="random"))
@@ -284,12 +283,12 @@ def test_bounded_handoff_waits(G, agents):
         assert np.array_equal(r1[k][:, ok], r0[k][:, ok]), k
     if flagged.any():
         assert ((r1["status"][-1][flagged] & 0x81) == 0x81).all()
-    # the give-up path itself: workgroup 0's owner wave (k_step_ag's AM, k_step_pipe's sim wave)
+    # the give-up path itself: workgroup 0's owner wave (AM)
     # sleeps ~0.25 ms before its first step (option "test_stall"), far past the 256-sleep bound
     # of the other waves' waits for its first post: they give up, the launch still ends, the fault
     # word says so, and exactly workgroup 0's envs are flagged (env 0 among them); every other
     # env is byte-identical to the unbounded run
-    stalled = _env(G, n, agents)
+    stalled = _env(G, n, 1)
     G.native.check(G.native.lib().fjsp_set_option(stalled.handle, b"spin_cap", 256))
     G.native.check(G.native.lib().fjsp_set_option(stalled.handle, b"test_stall", 64))
     stalled.reset(num_orders=30)

@@ -133,10 +133,12 @@ def test_predraw_snapshot_restore(G):
         assert P.bits_equal(a[k], b[k]) and P.bits_equal(a[k], c[k]), k
 
 
-def test_pickup_ahead_desynchronised_episodes(G):
-    """Uniform-random actions (emit wave 1 runs each step's pickup ahead of the sim wave):
-    lanes whose episodes end at different steps (staggered masked resets, short episodes)
-    must match the single-wave kernel, across launch boundaries and resets."""
+def test_uniform_random_predraw_desynchronised_episodes(G):
+    """Uniform-random actions with pre-draw (emit wave 1 draws each step's actions a step ahead,
+    the pre-draw wave the next tables): lanes whose episodes end at different steps (staggered
+    masked resets, short episodes) must be byte-equal to the single-wave kernel, across launch
+    boundaries and resets.  The kernel has no hand-off wait that could give up: at the smallest
+    bound (option "spin_cap") 256 envs x 64 steps raise no fault and no FJSP_STATUS_SPIN_TIMEOUT."""
     n = 320
     cfg = dict(max_episode_steps=37)
     outs = []
@@ -158,3 +160,10 @@ def test_pickup_ahead_desynchronised_episodes(G):
         for k in x:
             assert P.bits_equal(x[k], y[k]), (i, k)
     assert (outs[0][-1]["trunc"].sum(axis=1) > 0).sum() > 5   # truncations spread over many steps
+    env = _env(G, 256, 1)
+    G.native.check(G.native.lib().fjsp_set_option(env.handle, b"agents", 0))
+    G.native.check(G.native.lib().fjsp_set_option(env.handle, b"spin_cap", 256))
+    env.reset(num_orders=30)
+    st = G.to_np(env.rollout(64, action_seed=5, policy="random"))["status"]
+    assert env.last_kernel() == "k_step_pipe<lds,2emit,predraw>"
+    assert env.faults() == 0 and not (st & 0x80).any()

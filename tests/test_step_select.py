@@ -94,12 +94,12 @@ def test_selected_kernel(select, n, dev, name, grid, waves, epw):
 
 
 def test_stall_builds(select):
-    """test_stall picks the STALL build of k_step_ag (every epw) and of
-    k_step_pipe<lds,2emit,predraw>, of nothing else, and changes no name."""
+    """test_stall picks the STALL build of k_step_ag (every epw), the one kernel with bounded
+    hand-off waits, of nothing else, and changes no name."""
     for n, dev, name, grid, waves, _ in ROWS:
         p = select(n, test_stall=1, **dev)
         assert (p["name"], p["grid"], p["waves"]) == (name, grid, waves)
-        assert p["stall"] == (name in (AG_NAME, "k_step_pipe<lds,2emit,predraw>")), name
+        assert p["stall"] == (name == AG_NAME), name
     assert {select(n, test_stall=1)["epw"] for n in (4096, 8192, 16384)} == {16, 32, 64}
 
 
