@@ -403,6 +403,79 @@ int fjsp_kpi_scan(const uint32_t* results,              /* u32 [T][8][N] or NULL
                   int64_t* count,  /* device i64 [1], read and advanced on the device */
                   void* temp, uint64_t temp_bytes, void* stream);
 
+/* ---- Per-operation schedules (DESIGN.md §4 "Schedules"): which tray of which order was on which
+ * machine from when to when, and what the AGV carried from where to where.
+ *
+ * Held-tray words: three u32 per env and step, rows 0 = AGV, 1 = small machine, 2 = big machine,
+ * of the state after the step's run and before an auto-reset (where `status` is taken):
+ *   bits [0,13)  tray code: order [0,6) | first product [6,10) | count [10,13)
+ *   bit 13       holds a tray (AGV: carrying_tray, machine: current_tray)
+ *   bit 14       is_busy (machines; 0 for the AGV)
+ *   bits [16,19) the AGV's location (LocationType value) after the step; 0 for the machines
+ * Not holding -> bits [0,13) are 0; holding an empty tray -> order and first product are 0. */
+#define FJSP_HELD_ROWS 3
+#define FJSP_HELD_CODE_MASK 0x1FFFu
+#define FJSP_HELD_HOLDS 0x2000u
+#define FJSP_HELD_BUSY 0x4000u
+#define FJSP_HELD_LOC_SHIFT 16
+
+/* fjsp_step that also stores the step's held-tray words: held = device u32 [3][N], not NULL.
+ * Everything else (arguments, outputs, the state left behind) is fjsp_step's. */
+int fjsp_step_held(fjsp_handle* h, const uint8_t* actions, const uint8_t* agent_order, int32_t autoreset,
+                   const fjsp_out* out, uint32_t* held);
+
+/* The actions fjsp_step_many(action_seed, env_gid0, step0 = step, action_mode) would draw for the
+ * handle's current state at vector step `step`, into actions = device u8 [8][N] (what fjsp_step
+ * takes).  Reads the state only.  With it a per-step loop runs the built-in policies (uniform,
+ * masked, heuristic) through fjsp_step / fjsp_step_held. */
+int fjsp_actions(fjsp_handle* h, int32_t action_mode, uint64_t action_seed, uint32_t env_gid0, uint32_t step,
+                 uint8_t* actions);
+
+/* One record per operation (32 bytes = 2 x 16).  Steps are 0-based within the episode; an
+ * operation lasts (end - start) * step_size. */
+#define FJSP_OP_REC_BYTES 32
+typedef struct fjsp_op_rec {
+    uint32_t env_gid;        /* env_gid0 + e */
+    uint32_t info;           /* resource [0,8) = agent index 1 (AGV), 2 (small), 3 (big) | finished bit 8 |
+                                from [16,20) | to [20,24) (LocationType values; machines: their own) */
+    int64_t episode_start;   /* vector step at which the op's episode began = an fjsp_episode_rec's
+                                end_step - length (with env_gid, the join key) */
+    uint32_t tray;           /* tray code, bits [0,13) */
+    int32_t start;           /* machine: the step of the START; AGV: the step of the pickup */
+    int32_t end;             /* machine: the step at which is_busy fell; AGV: the step of the drop; -1 = the
+                                episode ended first (finished = 0, AGV to = 0) */
+    int32_t reserved;        /* 0 */
+} fjsp_op_rec;
+
+/* int32 words per env of fjsp_schedule_scan's carry (host-only). */
+int fjsp_schedule_carry_words(void);
+/* Bytes of fjsp_schedule_scan's temp buffer for a [T][N] slab (host-only). */
+int fjsp_schedule_temp_bytes(int32_t T, int32_t N, uint64_t* bytes);
+/* Compacts per-step rows into operation records.  Per env, t = 0..T-1 in order, s = the 0-based
+ * step within the episode, resources in the order AGV, small machine, big machine:
+ *   machine m (agent 2 + m): result bit 1 (started_processing) opens an op with the row's held
+ *     code, start = s; then an open op whose held busy bit is 0 closes with end = s (an empty
+ *     tray: end == start);
+ *   AGV (agent 1): result bit 3 (pickup_success) opens an op with tray = the held code, from = the
+ *     held location, start = s; result bit 4 (drop_success) closes it with to = the held location;
+ *   where term | trunc is set, after the row's closes, every op still open is written unfinished
+ *     and the env's carry returns to all zero.
+ * A resource writes at most one record per row.  carry: i32 [fjsp_schedule_carry_words()][N]
+ * in/out (the open episode's length; per resource the open op's word and start step), all zero =
+ * fresh, written back at the end of the slab.  Ordering and capacity as fjsp_episode_scan: record k
+ * of the slab in row-major (t, env, resource) order gets index count_in + k, is written only if
+ * that is < cap, and *count advances by every record of the slab.  results, held and carry 4-byte,
+ * count 8-byte, recs and temp 16-byte aligned; recs may be NULL when cap == 0.  T * N < 2^30.
+ * Three launches ordered by the stream alone (count, offsets, write).  Stream-ordered. */
+int fjsp_schedule_scan(const uint32_t* results,   /* u32 [T][8][N]; rows 1..3 are read */
+                       const uint32_t* held,      /* u32 [T][3][N] */
+                       const uint8_t* term, const uint8_t* trunc,   /* u8 [T][N] */
+                       int32_t T, int32_t N, uint32_t env_gid0, int64_t step0,
+                       int32_t* carry,            /* i32 [words][N] in/out */
+                       fjsp_op_rec* recs, int64_t cap,
+                       int64_t* count,            /* device i64 [1], read and advanced on the device */
+                       void* temp, uint64_t temp_bytes, void* stream);
+
 /* Synchronous host copy of one env's state summary (debug / facade use). */
 int fjsp_read_env(fjsp_handle* h, int32_t env, fjsp_env_view* out);
 /* Wait for all work queued on the handle's stream. */

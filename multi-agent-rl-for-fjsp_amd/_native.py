@@ -78,7 +78,8 @@ EXPORTS = ["fjsp_abi_version", "fjsp_last_error", "fjsp_default_config", "fjsp_c
            "fjsp_a2c_run_sums_bytes", "fjsp_a2c_run_sums", "fjsp_a2c_critic_fused", "fjsp_a2c_shard_keys", "fjsp_a2c_record_head", "fjsp_a2c_pack_mfma", "fjsp_a2c_slab_stats",
            "fjsp_a2c_wgrad", "fjsp_server_start", "fjsp_server_step", "fjsp_server_step_actions", "fjsp_server_stop",
            "fjsp_episode_temp_bytes", "fjsp_episode_scan", "fjsp_a2c_actor_head_ppo",
-           "fjsp_kpi_carry_words", "fjsp_kpi_scan"]
+           "fjsp_kpi_carry_words", "fjsp_kpi_scan", "fjsp_step_held", "fjsp_actions",
+           "fjsp_schedule_carry_words", "fjsp_schedule_temp_bytes", "fjsp_schedule_scan"]
 POLICY_ACTOR_DPAD, POLICY_CRITIC_DPAD = 16, 48
 POLICY_ACTOR_FLOATS = 3 * 256 * 16 // 2 + 256 + 3 * 256 * 256 // 2 + 256 + 8 * 256 + 16
 POLICY_CRITIC_FLOATS = 3 * 256 * 48 // 2 + 256 + 3 * 256 * 256 // 2 + 256 + 3 * 128 * 256 // 2 + 128 + 128 + 16
@@ -215,6 +216,11 @@ def lib():
         "fjsp_episode_scan": (I, [P, P, P, P, P, I, I, U32, ctypes.c_int64, P, P, P, ctypes.c_int64, P, P, U64, P]),
         "fjsp_kpi_carry_words": (I, []),
         "fjsp_kpi_scan": (I, [P, P, P, P, P, P, P, I, I, U32, ctypes.c_int64, P, P, ctypes.c_int64, P, P, U64, P]),
+        "fjsp_step_held": (I, [P, P, P, I, ctypes.POINTER(fjsp_out), P]),
+        "fjsp_actions": (I, [P, I, U64, U32, U32, P]),
+        "fjsp_schedule_carry_words": (I, []),
+        "fjsp_schedule_temp_bytes": (I, [I, I, ctypes.POINTER(U64)]),
+        "fjsp_schedule_scan": (I, [P, P, P, P, I, I, U32, ctypes.c_int64, P, P, ctypes.c_int64, P, P, U64, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

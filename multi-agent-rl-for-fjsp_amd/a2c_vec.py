@@ -1762,7 +1762,7 @@ class VecMultiAgentA2C:
 
     @torch.no_grad()
     def evaluate_kpis(self, num_orders=5, steps=500, seeds=None, deterministic=True, env=None, chunk=64,
-                      trace=False):
+                      trace=False, schedule=False):
         """The learned policy over `steps` vector steps from a reset with auto-reset (an env starts
         its next episode at once), every finished episode accounted twice on the device: returns
         and lengths (episodes.EpisodeLog) and the shop-floor KPIs (kpis.KpiLog: makespan, flow
@@ -1775,6 +1775,10 @@ class VecMultiAgentA2C:
         the actions, with trace).  Runs on `env` or, by default, on the training env, which is
         reset afterwards with the training num_orders as test() does.  The sampling key, the
         rollout slab, the networks and the optimisers are not touched.
+
+        schedule=True: the steps go through fjsp_step_held, whose held-tray words are scanned into
+        a schedule.ScheduleLog beside the two logs, and the result has "ops" = its pop() (one record
+        per machine / AGV operation; schedule.gantt, schedule.check).  Everything else is the same.
 
         KPIs of the training rollouts themselves come from track_kpis=True (account_kpis /
         pop_kpis, learn()'s training_kpis): the collect then fills the same slabs for the batches
@@ -1805,6 +1809,11 @@ class VecMultiAgentA2C:
         cap = max(65536, N * (steps // 16 + 1))
         log = EpisodeLog(N, dev, env_id_base=env.env_id_base, capacity=cap)
         kpi = KpiLog(N, dev, env_id_base=env.env_id_base, capacity=cap)
+        ops = None
+        if schedule:
+            from .schedule import ScheduleLog
+            s["held"] = z(C, 3, N, dt=torch.int32)
+            ops = ScheduleLog(N, dev, env_id_base=env.env_id_base, capacity=max(65536, N * (3 * steps // 2 + 3)))
         env.reset(seeds=seeds, num_orders=num_orders)
         env.pack_a2c(s["feats"][0], s["masks"][0])
         keep = {k: [] for k in s if k not in ("feats", "masks", "status")} if trace else None
@@ -1822,10 +1831,16 @@ class VecMultiAgentA2C:
                 else:
                     s["actions"][t].copy_(self.policy(s["feats"][t], s["masks"][t], deterministic, t=done + t,
                                                       gid0=env.env_id_base)[0])
-                nat.check(L.fjsp_step(h, ctypes.c_void_p(s["actions"][t].data_ptr()), None, 1, ctypes.byref(outs[t])))
+                if schedule:
+                    nat.check(L.fjsp_step_held(h, ctypes.c_void_p(s["actions"][t].data_ptr()), None, 1,
+                                               ctypes.byref(outs[t]), ctypes.c_void_p(s["held"][t].data_ptr())))
+                else:
+                    nat.check(L.fjsp_step(h, ctypes.c_void_p(s["actions"][t].data_ptr()), None, 1, ctypes.byref(outs[t])))
             log.scan(s["rewards"][:k], s["term"][:k], s["trunc"][:k], s["orders_completed"][:k], s["packaged"][:k])
             kpi.scan(s["results"][:k], s["term"][:k], s["trunc"][:k], s["obs_i8"][:k], s["orders_completed"][:k],
                      s["packaged"][:k], s["sim_time"][:k])
+            if schedule:
+                ops.scan(s["results"][:k], s["held"][:k], s["term"][:k], s["trunc"][:k])
             if trace:
                 for name in keep:
                     keep[name].append(s[name][:k].cpu().numpy().copy())
@@ -1833,6 +1848,8 @@ class VecMultiAgentA2C:
             s["masks"][0].copy_(s["masks"][k])
             done += k
         res = {"episodes": log.pop(), "kpis": kpi.pop()}
+        if schedule:
+            res["ops"] = ops.pop()
         if trace:
             import numpy as np
             res["trace"] = {name: np.concatenate(v) for name, v in keep.items()}

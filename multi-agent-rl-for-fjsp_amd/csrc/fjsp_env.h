@@ -1122,6 +1122,21 @@ FJSP_DEV void station_i8(const Env& E, int8_t* v) {
     }
 }
 
+// Held-tray words (include/fjsp.h, fjsp_step_held): what the AGV (v[0]) and the two machines
+// (v[1], v[2]) hold, read from W6, W17 and W18 alone: tray code [0,13) | holds 13 | busy 14 |
+// AGV location [16,19).  The code bits of W6 / W17+m outlive the tray (a drop and a SIGNAL only
+// set the slot to NIL) and an empty tray's code still names its order, so the word is
+// normalised to what the reference's objects say: no tray -> no code, no products -> only the
+// (zero) count.
+FJSP_DEV uint32_t held_word(bool holds, int code) {
+    return holds ? (1u << 13) | (tc_count(code) != 0 ? (uint32_t)code : 0u) : 0u;
+}
+FJSP_DEV void held_words(const Env& E, uint32_t v[3]) {
+    v[0] = held_word(E.carry() != NIL, E.carry_code()) | ((uint32_t)E.loc() << 16);
+#pragma unroll
+    for (int m = 0; m < 2; m++) v[1 + m] = held_word(E.m_cur(m) != NIL, E.m_code(m)) | ((uint32_t)E.m_busy(m) << 14);
+}
+
 // ---------------------------------------------------------------- heuristic policy
 // MultiAgentA2C._get_heuristic_actions (a2c.py:390-537) on the packed state.  The reference
 // compares the AGV position with (2,3) small, (0,3) big, (0,0) pickup, (3,5) packaging and

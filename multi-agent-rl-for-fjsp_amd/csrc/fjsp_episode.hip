@@ -1,5 +1,6 @@
 // fjsp_episode.hip — episode accounting over a rollout slab (include/fjsp.h: fjsp_episode_scan) and,
-// further down, the shop-floor KPIs of the same episodes (fjsp_kpi_scan).
+// further down, the shop-floor KPIs of the same episodes (fjsp_kpi_scan) and the per-operation
+// schedules compacted from the held-tray words (fjsp_schedule_scan).
 //
 // MultiAgentA2C.learn's per-episode bookkeeping (a2c.py:311-313 episode_rewards[agent] += reward,
 // :346-350 total = sum(episode_rewards.values()), episode_end_timesteps, :373 the printed steps)
@@ -509,6 +510,183 @@ bool ep_temp_layout(int32_t T, int32_t N, uint64_t* table, uint64_t* total) {
     return true;
 }
 
+// ---- per-operation schedules (include/fjsp.h: fjsp_schedule_scan) ------------------------------
+// How many records a row writes depends on the ops open at that row, so the walk runs twice with
+// k_episode_offsets between: k_schedule_scan<false> counts, k_schedule_scan<true> writes.  Both are
+// one wave per 64 envs (one lane per env) walking t forward, EP_U rows per load batch with the next
+// batch issued before the current one is consumed (as k_kpi_scan): per row and env the three result
+// words of agents 1..3, the three held-tray words and the two flags, 26 bytes.
+//   count  per row the three ballots of "resource r writes a record" -> cnt[t][w] = their popcounts'
+//          sum (lane 0); the carry is read, never written
+//   write  the same walk; a record's rank is offs[t][w] + the records of the lower lanes in the
+//          three ballots + the lane's own lower resources, i.e. row-major (t, env, resource); the
+//          carry is written back at the end
+// A wave touches only its own cnt words, its envs' carry words and the records of its own ranks;
+// launch boundaries are the only ordering between waves.
+constexpr int SC_LEN = 0;      // carry words [SC_WORDS][N]: steps of the open episode,
+constexpr int SC_OP = 1;       // + 2 r: the open op's word (open 0 | tray code [1,14) | from [16,20)), + 1: its start step
+constexpr int SC_WORDS = 7;
+constexpr int SC_R = 3;        // resources: agent 1 + r
+constexpr uint32_t SC_MACHINE_LOC[SC_R] = {0u, 3u, 2u};   // LocationType SMALL_MACHINE = 3, BIG_MACHINE = 2
+
+static_assert(sizeof(fjsp_op_rec) == FJSP_OP_REC_BYTES && FJSP_OP_REC_BYTES == 32, "fjsp_op_rec is 2 x 16 bytes");
+static_assert(offsetof(fjsp_op_rec, episode_start) == 8 && offsetof(fjsp_op_rec, tray) == 16, "record halves");
+
+struct SchedArgs {
+    const uint32_t* res;
+    const uint32_t* held;
+    const uint8_t* term;
+    const uint8_t* trunc;
+    fjsp_op_rec* recs;
+    int32_t* carry;
+    long long cap, base, step0;
+    uint32_t gid0;
+    int T, N;
+};
+
+struct SchedChunk {
+    uint32_t res[SC_R][EP_U], held[SC_R][EP_U];
+    uint8_t te[EP_U], tr[EP_U];
+    uint32_t off[EP_U];
+};
+
+// Rows t0 .. t0 + EP_U - 1 of the column `col` (rows past the slab clamped to its last row, lanes
+// past the envs to the last env: loaded, never used).  No branch around a load.
+template <bool WRITE>
+__device__ __forceinline__ void sched_load(SchedChunk& c, const SchedArgs& p, const uint32_t* __restrict__ offs, int t0,
+                                           int W, int w, uint32_t col) {
+    const size_t N = (size_t)p.N;
+#pragma unroll
+    for (int j = 0; j < EP_U; j++) {
+        const size_t t = (size_t)(t0 + j < p.T ? t0 + j : p.T - 1);
+        const uint32_t* __restrict__ rr = p.res + (t * EP_A + 1) * N;
+        const uint32_t* __restrict__ hr = p.held + t * SC_R * N;
+#pragma unroll
+        for (int r = 0; r < SC_R; r++) {
+            c.res[r][j] = rr[(size_t)r * N + col];
+            c.held[r][j] = hr[(size_t)r * N + col];
+        }
+        c.te[j] = p.term[t * N + col];
+        c.tr[j] = p.trunc[t * N + col];
+        c.off[j] = WRITE ? offs[t * W + w] : 0u;
+    }
+}
+
+struct SchedState {
+    int32_t len;
+    uint32_t op[SC_R];
+    int32_t start[SC_R];
+};
+
+template <bool WRITE>
+__device__ __forceinline__ void sched_rows(const SchedChunk& c, int t0, const SchedArgs& p, uint32_t* __restrict__ cnt,
+                                           int W, int w, int e, int lane, bool live, SchedState& s) {
+    const int rows = min(EP_U, p.T - t0);
+#pragma unroll
+    for (int j = 0; j < EP_U; j++) {
+        if (j < rows) {   // wave-uniform
+            const bool end = (c.te[j] | c.tr[j]) != 0;
+            bool emit[SC_R];
+            uint32_t info[SC_R], tray[SC_R];
+            int32_t st[SC_R], en[SC_R];
+            uint64_t b[SC_R];
+    #pragma unroll
+            for (int r = 0; r < SC_R; r++) {
+                const uint32_t rw = c.res[r][j], hw = c.held[r][j];
+                const uint32_t loc = r == 0 ? (hw >> FJSP_HELD_LOC_SHIFT) & 7u : SC_MACHINE_LOC[r];
+                const bool opens = r == 0 ? (rw & 8u) != 0 : (rw & 2u) != 0;   // pickup_success / started_processing
+                if (opens) {
+                    s.op[r] = 1u | ((hw & FJSP_HELD_CODE_MASK) << 1) | (loc << 16);
+                    s.start[r] = s.len;
+                }
+                const bool open = (s.op[r] & 1u) != 0;
+                const bool fin = open && (r == 0 ? (rw & 16u) != 0 : (hw & FJSP_HELD_BUSY) == 0);   // drop_success / is_busy fell
+                emit[r] = live && open && (fin || end);
+                const uint32_t from = (s.op[r] >> 16) & 15u;
+                const uint32_t to = r == 0 ? (fin ? loc : 0u) : from;
+                info[r] = (uint32_t)(1 + r) | (fin ? 1u << 8 : 0u) | (from << 16) | (to << 20);
+                tray[r] = (s.op[r] >> 1) & FJSP_HELD_CODE_MASK;
+                st[r] = s.start[r];
+                en[r] = fin ? s.len : -1;
+                if (open && (fin || end)) {
+                    s.op[r] = 0u;
+                    s.start[r] = 0;
+                }
+                b[r] = __ballot(emit[r]);
+            }
+            if (!WRITE) {
+                if (lane == 0) cnt[(size_t)(t0 + j) * W + w] = (uint32_t)(__popcll(b[0]) + __popcll(b[1]) + __popcll(b[2]));
+            } else {
+                long long rank = p.base + (long long)c.off[j] + lanes_below(b[0], lane) + lanes_below(b[1], lane) +
+                                 lanes_below(b[2], lane);
+                const long long es = p.step0 + (long long)(t0 + j) - (long long)s.len;
+    #pragma unroll
+                for (int r = 0; r < SC_R; r++) {
+                    if (emit[r]) {
+                        if ((unsigned long long)rank < (unsigned long long)p.cap) {
+                            uint4* q = reinterpret_cast<uint4*>(p.recs + rank);
+                            q[0] = make_uint4(p.gid0 + (uint32_t)e, info[r], (uint32_t)es, (uint32_t)((unsigned long long)es >> 32));
+                            q[1] = make_uint4(tray[r], (uint32_t)st[r], (uint32_t)en[r], 0u);
+                        }
+                        rank += 1;
+                    }
+                }
+            }
+            s.len = end ? 0 : s.len + 1;
+        }
+    }
+}
+
+template <bool WRITE>
+__global__ void __launch_bounds__(64) k_schedule_scan(SchedArgs p, uint32_t* __restrict__ cnt,
+                                                      const long long* __restrict__ base, int W) {
+    if (WRITE) p.base = base[0];
+    const int lane = threadIdx.x, w = (int)blockIdx.x;
+    const int e = w * 64 + lane;
+    const bool live = e < p.N;
+    const uint32_t col = (uint32_t)min(e, p.N - 1);
+    const size_t N = (size_t)p.N;
+    int32_t* __restrict__ cy = p.carry + col;   // word k of this env: cy[k * N]
+    SchedState s{};
+    s.len = cy[(size_t)SC_LEN * N];
+#pragma unroll
+    for (int r = 0; r < SC_R; r++) {
+        s.op[r] = (uint32_t)cy[(size_t)(SC_OP + 2 * r) * N];
+        s.start[r] = cy[(size_t)(SC_OP + 2 * r + 1) * N];
+    }
+    SchedChunk A, B;
+    int t0 = 0;
+    sched_load<WRITE>(A, p, cnt, 0, W, w, col);
+    for (;;) {   // A holds t0.., B is loaded before A's rows are walked, and the other way round
+        sched_load<WRITE>(B, p, cnt, t0 + EP_U, W, w, col);
+        sched_rows<WRITE>(A, t0, p, cnt, W, w, e, lane, live, s);
+        t0 += EP_U;
+        if (t0 >= p.T) break;
+        sched_load<WRITE>(A, p, cnt, t0 + EP_U, W, w, col);
+        sched_rows<WRITE>(B, t0, p, cnt, W, w, e, lane, live, s);
+        t0 += EP_U;
+        if (t0 >= p.T) break;
+    }
+    if (WRITE && live) {
+        cy[(size_t)SC_LEN * N] = s.len;
+#pragma unroll
+        for (int r = 0; r < SC_R; r++) {
+            cy[(size_t)(SC_OP + 2 * r) * N] = (int32_t)s.op[r];
+            cy[(size_t)(SC_OP + 2 * r + 1) * N] = s.start[r];
+        }
+    }
+}
+
+// temp: the counts / offsets table u32 [T][W] (padded to 16 bytes), then 16 bytes for the count at
+// entry.  Up to three records per env and row: T W 64 <= 2^30 keeps the sums in 32 bits.
+bool sched_temp_layout(int32_t T, int32_t N, uint64_t* table, uint64_t* total) {
+    const int64_t W = ((int64_t)N + 63) / 64, L = (int64_t)T * W;
+    if (L * 64 > (int64_t)1 << 30) return false;
+    *table = ((uint64_t)L * 4 + 15) & ~(uint64_t)15;
+    *total = *table + 16;
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -605,6 +783,60 @@ int fjsp_kpi_scan(const uint32_t* results, const uint8_t* term, const uint8_t* t
     p.T = T;
     p.N = N;
     hipLaunchKernelGGL(k_kpi_scan, dim3((unsigned)W), dim3(64 * EP_A), 0, st, flags, offs, base, p, W);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        fjsp_internal_fail(hipGetErrorString(e));
+        return -2;
+    }
+    return 0;
+}
+
+int fjsp_schedule_carry_words(void) { return SC_WORDS; }
+
+int fjsp_schedule_temp_bytes(int32_t T, int32_t N, uint64_t* bytes) {
+    if (T <= 0 || N <= 0) return fjsp_internal_fail("fjsp_schedule_temp_bytes: T and N must be > 0");
+    if (!bytes) return fjsp_internal_fail("fjsp_schedule_temp_bytes: null pointer");
+    uint64_t table, total;
+    if (!sched_temp_layout(T, N, &table, &total)) return fjsp_internal_fail("fjsp_schedule_temp_bytes: T * N must be < 2^30");
+    *bytes = total;
+    return 0;
+}
+
+int fjsp_schedule_scan(const uint32_t* results, const uint32_t* held, const uint8_t* term, const uint8_t* trunc, int32_t T,
+                       int32_t N, uint32_t env_gid0, int64_t step0, int32_t* carry, fjsp_op_rec* recs, int64_t cap,
+                       int64_t* count, void* temp, uint64_t temp_bytes, void* stream) {
+    if (T <= 0 || N <= 0) return fjsp_internal_fail("fjsp_schedule_scan: T and N must be > 0");
+    if (cap < 0) return fjsp_internal_fail("fjsp_schedule_scan: cap must be >= 0");
+    if (!results || !held || !term || !trunc || !carry || !count || !temp || (cap > 0 && !recs))
+        return fjsp_internal_fail("fjsp_schedule_scan: null buffer");
+    uint64_t table, total;
+    if (!sched_temp_layout(T, N, &table, &total)) return fjsp_internal_fail("fjsp_schedule_scan: T * N must be < 2^30");
+    if (temp_bytes < total) return fjsp_internal_fail("fjsp_schedule_scan: temp buffer too small");
+    if ((((uintptr_t)recs | (uintptr_t)temp) & 15u) != 0)
+        return fjsp_internal_fail("fjsp_schedule_scan: recs and temp must be 16-byte aligned");
+    if ((((uintptr_t)results | (uintptr_t)held | (uintptr_t)carry) & 3u) != 0 || ((uintptr_t)count & 7u) != 0)
+        return fjsp_internal_fail("fjsp_schedule_scan: results, held and carry must be 4-byte, count 8-byte aligned");
+    const int W = (int)(((int64_t)N + 63) / 64);
+    const int L = T * W;
+    uint32_t* offs = (uint32_t*)temp;
+    long long* base = (long long*)((char*)temp + table);
+    const hipStream_t st = (hipStream_t)stream;
+    SchedArgs p;
+    p.res = results;
+    p.held = held;
+    p.term = term;
+    p.trunc = trunc;
+    p.recs = recs;
+    p.carry = carry;
+    p.cap = cap;
+    p.base = 0;
+    p.step0 = step0;
+    p.gid0 = env_gid0;
+    p.T = T;
+    p.N = N;
+    hipLaunchKernelGGL(k_schedule_scan<false>, dim3((unsigned)W), dim3(64), 0, st, p, offs, base, W);
+    hipLaunchKernelGGL(k_episode_offsets, dim3(1), dim3(EPO_THREADS), 0, st, offs, L, base, (long long*)count);
+    hipLaunchKernelGGL(k_schedule_scan<true>, dim3((unsigned)W), dim3(64), 0, st, p, offs, base, W);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fjsp_internal_fail(hipGetErrorString(e));

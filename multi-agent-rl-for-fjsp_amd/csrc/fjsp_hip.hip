@@ -10,6 +10,7 @@
 // Kernels: one lane per env, 64-lane workgroups (one wavefront; 4096 envs -> 64 CUs).
 //   k_reset      FJSPSimulation.reset (FJSPSimulation.py:286-323)
 //   k_step       FJSPSimulation.step  (FJSPSimulation.py:144-242), actions from HBM
+//   k_actions    the built-in policies' actions for the current state (fjsp_actions)
 //   k_step_many  K fused steps with on-device counter-RNG actions
 //   k_gae        transition_memory.py:83-105 (returns + GAE), one lane per (agent, env) column
 // Compiled with -ffp-contract=off: rewards and GAE follow Python's unfused fp64 op order.
@@ -141,13 +142,29 @@ __device__ __forceinline__ void synth_actions(uint64_t seed, uint32_t gid, uint3
     }
 }
 
+// fjsp_actions: the built-in policies' actions for the current state (no state change)
+__global__ void __launch_bounds__(BLOCK) k_actions(DevState S, Cfg C, int mode, uint64_t seed, uint32_t gid0, uint32_t step,
+                                                   uint8_t* __restrict__ actions) {
+    const int e = blockIdx.x * BLOCK + threadIdx.x;
+    if (e >= S.n) return;
+    Env E;
+    env_load(E, S.words, S.n, e);
+    const Tables T = tables_of(S, e);
+    int act[NA];
+    synth_actions(seed, gid0 + (uint32_t)e, step, mode, E, T, C, act);
+#pragma unroll
+    for (int a = 0; a < NA; a++) actions[(size_t)a * S.n + e] = (uint8_t)act[a];
+}
+
 // One full env step + outputs at trajectory index t; handles auto-reset.
 // EPW: envs per workgroup (64, 32 or 16; lanes >= EPW idle; option "step_envs").  Fewer envs per
 // wave would shorten the union of the lanes' branches and spread 4 096 envs over all 256 CUs; it
 // measured slower (fjsp_step), so 64 stays the default.
-template <bool CANON, int EPW>
+// HP: nothing, or uint32_t* = the held-tray words' destination u32 [3][N] (the HELD instances,
+// fjsp_step_held); without it the kernel has the arguments and the code it had before.
+template <bool CANON, int EPW, class... HP>
 __global__ void __launch_bounds__(BLOCK) k_step(DevState S, Cfg C, const uint8_t* __restrict__ actions, uint64_t order_packed,
-                                                int autoreset, fjsp_out out) {
+                                                int autoreset, fjsp_out out, HP... held) {
     FJSP_DIAG(
     const uint64_t t_entry = __builtin_amdgcn_s_memtime();
     )
@@ -182,7 +199,7 @@ __global__ void __launch_bounds__(BLOCK) k_step(DevState S, Cfg C, const uint8_t
     E.st_acc[0] = E.st_t0 - t_entry;
     (void)t_lut;
                      )
-    step_and_emit<CANON>(E, T, C, S, e, act, order, autoreset, out, 0);
+    step_and_emit<CANON>(E, T, C, S, e, act, order, autoreset, out, 0, held...);
     env_store(E, S.words, S.n, e);
     FJSP_DIAG(
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2288,8 +2305,9 @@ int fjsp_reset(fjsp_handle* h, const uint32_t* seeds, const uint8_t* env_mask, i
     return 0;
 }
 
-int fjsp_step(fjsp_handle* h, const uint8_t* actions, const uint8_t* agent_order, int32_t autoreset, const fjsp_out* out) {
-    if (!h) return fail("null handle");
+// fjsp_step (held == NULL) and fjsp_step_held
+static int step_once(fjsp_handle* h, const uint8_t* actions, const uint8_t* agent_order, int32_t autoreset,
+                     const fjsp_out* out, uint32_t* held) {
     SERVER_QUIESCE(h);
     if (!actions) return fail("null actions");
     if (!h->has_reset) return fail("fjsp_step before fjsp_reset");
@@ -2311,16 +2329,48 @@ int fjsp_step(fjsp_handle* h, const uint8_t* actions, const uint8_t* agent_order
     h->last_kernel = p.name;
     with_epw(p.epw, [&](auto epw) {
         constexpr int EPW = decltype(epw)::value;
-        auto launch = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(p.grid), dim3(BLOCK), 0, h->stream, h->S, h->dcfg, actions, packed, autoreset, o);
-        };
-        p.canon ? launch(k_step<true, EPW>) : launch(k_step<false, EPW>);
+        const dim3 grid(p.grid), block(BLOCK);
+        if (held) {
+            if (p.canon) hipLaunchKernelGGL((k_step<true, EPW, uint32_t*>), grid, block, 0, h->stream, h->S, h->dcfg, actions, packed, autoreset, o, held);
+            else hipLaunchKernelGGL((k_step<false, EPW, uint32_t*>), grid, block, 0, h->stream, h->S, h->dcfg, actions, packed, autoreset, o, held);
+        } else {
+            if (p.canon) hipLaunchKernelGGL((k_step<true, EPW>), grid, block, 0, h->stream, h->S, h->dcfg, actions, packed, autoreset, o);
+            else hipLaunchKernelGGL((k_step<false, EPW>), grid, block, 0, h->stream, h->S, h->dcfg, actions, packed, autoreset, o);
+        }
     });
     HIPCHK(hipGetLastError());
     if (h->timing) {
         HIPCHK(hipEventRecord(h->ev1, h->stream));
         h->timed = 1;
     }
+    return 0;
+}
+
+int fjsp_step(fjsp_handle* h, const uint8_t* actions, const uint8_t* agent_order, int32_t autoreset, const fjsp_out* out) {
+    if (!h) return fail("null handle");
+    return step_once(h, actions, agent_order, autoreset, out, nullptr);
+}
+
+int fjsp_step_held(fjsp_handle* h, const uint8_t* actions, const uint8_t* agent_order, int32_t autoreset,
+                   const fjsp_out* out, uint32_t* held) {
+    if (!held) return fail("fjsp_step_held: null held buffer");
+    if (((uintptr_t)held & 3u) != 0) return fail("fjsp_step_held: held must be 4-byte aligned");
+    if (!h) return fail("null handle");
+    return step_once(h, actions, agent_order, autoreset, out, held);
+}
+
+int fjsp_actions(fjsp_handle* h, int32_t action_mode, uint64_t action_seed, uint32_t env_gid0, uint32_t step,
+                 uint8_t* actions) {
+    if (!h) return fail("null handle");
+    if (!actions) return fail("fjsp_actions: null actions");
+    if (action_mode != FJSP_ACTIONS_UNMASKED && action_mode != FJSP_ACTIONS_MASKED && action_mode != FJSP_ACTIONS_HEURISTIC)
+        return fail("bad action_mode");
+    SERVER_QUIESCE(h);
+    if (!h->has_reset) return fail("fjsp_actions before fjsp_reset");
+    DeviceGuard g(h->device);
+    hipLaunchKernelGGL(k_actions, dim3((h->n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, h->stream, h->S, h->dcfg, action_mode,
+                       action_seed, env_gid0, step, actions);
+    HIPCHK(hipGetLastError());
     return 0;
 }
 

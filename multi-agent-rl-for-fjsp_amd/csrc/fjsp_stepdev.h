@@ -287,10 +287,13 @@ __device__ __forceinline__ uint64_t fmix64(uint64_t z) {
 
 // FULL = false: only obs, masks, rewards, term, trunc and status are written (the other
 // fjsp_out pointers are never read, so they take no SGPRs in the hot loop).
-template <bool CANON, bool FULL = true>
+// HP: nothing, or the held-tray slab u32 [T][3][N] of the HELD instance (fjsp_step_held): a
+// trailing pack, so every other instance keeps its arguments and its code.
+template <bool CANON, bool FULL = true, class... HP>
 __device__ __forceinline__ void step_and_emit(Env& E, const Tables& T, const Cfg& C, const DevState& S, int e,
                                               const int* act, const uint8_t* order, int autoreset, const fjsp_out& out,
-                                              uint32_t t) {
+                                              uint32_t t, HP... held) {
+    static_assert(sizeof...(HP) <= 1, "at most the held-tray slab");
     const uint32_t n = (uint32_t)S.n, ue = (uint32_t)e;
     uint32_t res[NA];
     const double g8 = env_advance<CANON>(E, T, C, act, order, res);
@@ -315,6 +318,13 @@ __device__ __forceinline__ void step_and_emit(Env& E, const Tables& T, const Cfg
     if (FULL && out.packaged) st32(out.packaged, t * n + ue, E.total_packaged());
     if (FULL && out.sim_time) st32(out.sim_time, t * n + ue, (double)(E.step() + 1) * (double)C.step_size);
     if (out.status) st32(out.status, t * n + ue, E.status());
+    if constexpr (sizeof...(HP) == 1) {   // the state the status is of: after the run, before the reset
+        uint32_t* const hp = (held, ...);
+        uint32_t hv[3];
+        held_words(E, hv);
+#pragma unroll
+        for (int r = 0; r < 3; r++) st32(hp, (t * 3u + (uint32_t)r) * n + ue, hv[r]);
+    }
     FJSP_STAMP(E, 5);
     E.set_step(E.step() + 1);
     if (autoreset && (all_done || truncated))

@@ -1,0 +1,266 @@
+"""Per-operation schedules: which tray of which order was on which machine from when to when, and
+what the AGV carried from where to where (the data of a Gantt chart).
+
+The reference shows this through its logger and grid view (utils/Logger.py processing_start /
+tray_pickup / tray_drop, visualization.py).  Here a step emits three held-tray words per env
+(fjsp_step_held: the AGV's carrying_tray and position, the machines' current_tray and is_busy)
+beside the action-result words, and a scan compacts the per-step rows into one record per
+operation.  ``schedule_reference`` is that scan in plain Python ints (the specification, usable on
+numpy arrays and CPU tensors); ``ScheduleLog`` is the same scan on the device
+(fjsp_schedule_scan, csrc/fjsp_episode.hip), appending fjsp_op_rec records to a device-resident
+log with no host synchronisation until ``pop()``; ``gantt`` and ``check`` work on the records.
+
+Rules, per env and row, s = the 0-based step within the episode, resources in the order AGV, small
+machine, big machine:
+  machine   result bit 1 (started_processing) opens an op with the row's held code, start = s; then
+            an open op whose held busy bit is 0 closes with end = s (the completion due at time
+            s * step_size fires in that row's run, so (end - start) * step_size = count * pt; an
+            empty tray gives end == start)
+  AGV       result bit 3 (pickup_success) opens an op with the held code, from = the held location;
+            result bit 4 (drop_success) closes it with to = the held location
+  episode end (term | trunc)  after the row's closes every op still open is written unfinished
+            (finished = 0, end = -1, AGV to = 0)
+A record's (env, episode_start) equals an EpisodeLog / KpiLog record's (env, end_step - length).
+
+Not covered: packaging batches (one START grants a whole queue of runs of several orders, batches
+overlap), the pickup station's tray release times, the fused and training step paths.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _native as nat
+
+# include/fjsp.h fjsp_op_rec (32 bytes)
+OP_DTYPE = np.dtype([("env_gid", "<u4"), ("info", "<u4"), ("episode_start", "<i8"), ("tray", "<u4"),
+                     ("start", "<i4"), ("end", "<i4"), ("reserved", "<i4")])
+assert OP_DTYPE.itemsize == 32
+HELD_ROWS = 3                       # AGV, small machine, big machine = agents 1..3
+HELD_CODE_MASK, HELD_HOLDS, HELD_BUSY, HELD_LOC_SHIFT = 0x1FFF, 0x2000, 0x4000, 16
+RES_AGV_PICKUP, RES_AGV_DROP, RES_MACHINE_START = 1 << 3, 1 << 4, 1 << 1   # spec.RESULT_KEYS bit order
+RESOURCES = ("agv", "small_machine", "big_machine")                          # resource = 1 + index
+MACHINE_LOC = (0, 3, 2)             # LocationType: SMALL_MACHINE = 3, BIG_MACHINE = 2
+INFO_FINISHED = 1 << 8
+# carry words per env (fjsp_schedule_carry_words): the open episode's length, then per resource the
+# open op's word (open bit 0 | tray code [1,14) | from [16,20)) and its start step
+C_LEN, C_OP, CARRY_WORDS = 0, 1, 7
+NA = 8
+
+
+def tray_fields(code):
+    """(order, first product, count) of a tray code (array or int)."""
+    c = np.asarray(code).astype(np.int64)
+    return c & 63, (c >> 6) & 15, (c >> 10) & 7
+
+
+def schedule_reference(results, held, term, trunc, carry=None, step0=0, env_gid0=0):
+    """The specification of fjsp_schedule_scan on the host.  results [T, 8, N] (the 32-bit result
+    words, any integer dtype), held [T, 3, N], term / trunc [T, N]; carry int32 [CARRY_WORDS, N] =
+    the open episodes' state (None: fresh).  Returns (records, carry): records an OP_DTYPE array in
+    (t, env, resource) order and the carry after the slab."""
+    term = np.asarray(term)
+    T, N = term.shape
+    trunc = np.asarray(trunc).reshape(T, N)
+    res = (np.asarray(results).astype(np.int64) & 0xFFFFFFFF).reshape(T, NA, N)
+    hld = (np.asarray(held).astype(np.int64) & 0xFFFFFFFF).reshape(T, HELD_ROWS, N)
+    cy = np.zeros((CARRY_WORDS, N), np.int64) if carry is None else np.asarray(carry).astype(np.int64).copy()
+    out = []
+    for e in range(N):
+        ln = int(cy[C_LEN, e])
+        op = [int(cy[C_OP + 2 * r, e]) & 0xFFFFFFFF for r in range(HELD_ROWS)]
+        st = [int(cy[C_OP + 2 * r + 1, e]) for r in range(HELD_ROWS)]
+        for t in range(T):
+            end = bool(term[t, e]) or bool(trunc[t, e])
+            for r in range(HELD_ROWS):
+                rw, hw = int(res[t, 1 + r, e]), int(hld[t, r, e])
+                loc = (hw >> HELD_LOC_SHIFT) & 7 if r == 0 else MACHINE_LOC[r]
+                if rw & (RES_AGV_PICKUP if r == 0 else RES_MACHINE_START):
+                    op[r] = 1 | ((hw & HELD_CODE_MASK) << 1) | (loc << 16)
+                    st[r] = ln
+                if not op[r] & 1:
+                    continue
+                fin = bool(rw & RES_AGV_DROP) if r == 0 else not hw & HELD_BUSY
+                if fin or end:
+                    frm = (op[r] >> 16) & 15
+                    to = (loc if fin else 0) if r == 0 else frm
+                    info = (1 + r) | (INFO_FINISHED if fin else 0) | (frm << 16) | (to << 20)
+                    out.append((t, e, r, (env_gid0 + e, info, step0 + t - ln, (op[r] >> 1) & HELD_CODE_MASK,
+                                          st[r], ln if fin else -1, 0)))
+                    op[r], st[r] = 0, 0
+            ln = 0 if end else ln + 1
+        cy[C_LEN, e] = ln
+        for r in range(HELD_ROWS):
+            cy[C_OP + 2 * r, e], cy[C_OP + 2 * r + 1, e] = op[r], st[r]
+    out.sort(key=lambda x: x[:3])
+    recs = np.zeros(len(out), dtype=OP_DTYPE)
+    for k, x in enumerate(out):
+        recs[k] = x[3]
+    return recs, cy.astype(np.int32)
+
+
+def records_dict(recs, dropped=0):
+    """OP_DTYPE array -> the dict of arrays ScheduleLog.pop() returns."""
+    info = recs["info"].astype(np.int64)
+    order, first, count = tray_fields(recs["tray"])
+    return {"env": recs["env_gid"].copy(), "episode_start": recs["episode_start"].copy(),
+            "resource": (info & 0xFF).astype(np.int32), "finished": (info & INFO_FINISHED) != 0,
+            "order": order.astype(np.int32), "first": first.astype(np.int32), "count": count.astype(np.int32),
+            "start": recs["start"].copy(), "end": recs["end"].copy(),
+            "from_loc": ((info >> 16) & 15).astype(np.int32), "to_loc": ((info >> 20) & 15).astype(np.int32),
+            "records": recs, "dropped": int(dropped)}
+
+
+def _as_dict(ops):
+    return ops if isinstance(ops, dict) else records_dict(np.asarray(ops))
+
+
+def _cfg(config, key):
+    if config is None:
+        config = nat.default_config()
+    return int(config[key] if isinstance(config, dict) else getattr(config, key))
+
+
+def gantt(ops, config=None):
+    """The bars of a Gantt chart: {(env, episode_start, resource): dict of arrays} with the group's
+    ops ordered by start and start_time / end_time = step * step_size beside the record's fields
+    (end_time NaN for an unfinished op).  ops: ScheduleLog.pop()'s dict or an OP_DTYPE array;
+    config: an fjsp_config or anything with step_size (None = the default config)."""
+    d = _as_dict(ops)
+    step_size = float(_cfg(config, "step_size"))
+    keys = ("order", "first", "count", "start", "end", "finished", "from_loc", "to_loc")
+    n = len(d["env"])
+    idx = np.lexsort((np.arange(n), d["start"], d["resource"], d["episode_start"], d["env"]))
+    groups = {}
+    for i in idx.tolist():
+        groups.setdefault((int(d["env"][i]), int(d["episode_start"][i]), int(d["resource"][i])), []).append(i)
+    out = {}
+    for k, rows in groups.items():
+        rows = np.asarray(rows)
+        g = {f: d[f][rows] for f in keys}
+        g["start_time"] = g["start"].astype(np.float64) * step_size
+        g["end_time"] = np.where(g["finished"], g["end"].astype(np.float64) * step_size, np.nan)
+        out[k] = g
+    return out
+
+
+def check(ops, config=None):
+    """Raise ValueError unless, per (env, episode, resource), the ops do not overlap (each ends no
+    later than the next starts; an unfinished op is the group's last) and every finished machine
+    op lasts count * processing_time / step_size steps."""
+    step_size = _cfg(config, "step_size")
+    pts = {2: _cfg(config, "pt_small") // step_size, 3: _cfg(config, "pt_big") // step_size}
+    for (env, es, res), g in gantt(ops, config).items():
+        n = len(g["start"])
+        for i in range(n):
+            s, e, fin = int(g["start"][i]), int(g["end"][i]), bool(g["finished"][i])
+            where = f"env {env} episode_start {es} resource {res} op {i}"
+            if fin and e < s:
+                raise ValueError(f"{where}: ends at {e} before its start {s}")
+            if not fin and i != n - 1:
+                raise ValueError(f"{where}: unfinished but not the last op of its episode")
+            if i + 1 < n and fin and e > int(g["start"][i + 1]):
+                raise ValueError(f"{where}: ends at {e}, after the next op's start {int(g['start'][i + 1])}")
+            if fin and res in pts and e - s != int(g["count"][i]) * pts[res]:
+                raise ValueError(f"{where}: lasts {e - s} steps, {int(g['count'][i])} products need "
+                                 f"{int(g['count'][i]) * pts[res]}")
+
+
+def carry_words():
+    return int(nat.lib().fjsp_schedule_carry_words())
+
+
+def temp_bytes(T, N):
+    n = ctypes.c_uint64()
+    nat.check(nat.lib().fjsp_schedule_temp_bytes(int(T), int(N), ctypes.byref(n)))
+    return int(n.value)
+
+
+def _ptr(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+class ScheduleLog:
+    """Device-resident operation log of num_envs envs: the carry of the open episodes (length, open
+    ops), a record buffer of `capacity` fjsp_op_rec, the device-side record count and the running
+    vector-step counter step0.  scan() appends without synchronising; pop() copies the records to
+    the host (the only synchronisation) and empties the log."""
+
+    def __init__(self, num_envs, device, env_id_base=0, capacity=1 << 20):
+        import torch
+        self.N = int(num_envs)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise nat.FjspNativeError("ScheduleLog needs a GPU (HIP); no CPU fallback exists")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.capacity = int(capacity)
+        self.env_id_base = int(env_id_base)
+        words = carry_words()
+        assert words == CARRY_WORDS, (words, CARRY_WORDS)
+        self.carry = torch.zeros(words, self.N, dtype=torch.int32, device=self.device)
+        self.recs = torch.zeros(max(self.capacity, 1) * OP_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+        self.count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.step0 = 0
+        self._temp = None
+
+    def _temp_for(self, T):
+        import torch
+        need = temp_bytes(T, self.N)
+        if self._temp is None or self._temp.numel() < need:
+            self._temp = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._temp
+
+    def scan(self, results, held, term, trunc):
+        """Compact the slab (contiguous device tensors: results int32 / uint32 [T, 8, N], held int32 /
+        uint32 [T, 3, N], term / trunc u8 [T, N]) on the current stream; advances step0 by T."""
+        import torch
+        T = int(term.shape[0])
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        for name, x, dts, shape in (("results", results, words, (T, NA, self.N)),
+                                    ("held", held, words, (T, HELD_ROWS, self.N)),
+                                    ("term", term, (torch.uint8,), (T, self.N)),
+                                    ("trunc", trunc, (torch.uint8,), (T, self.N))):
+            if x is None:
+                raise ValueError(f"{name} is required")
+            if tuple(x.shape) != shape or x.dtype not in dts:
+                raise ValueError(f"{name} must be {dts[0]} {list(shape)}")
+            if not x.is_contiguous() or x.device != self.device:
+                raise ValueError("ScheduleLog.scan takes contiguous tensors on the log's device")
+        temp = self._temp_for(T)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            nat.check(nat.lib().fjsp_schedule_scan(
+                _ptr(results), _ptr(held), _ptr(term), _ptr(trunc), T, self.N, self.env_id_base, self.step0,
+                _ptr(self.carry), _ptr(self.recs), self.capacity, _ptr(self.count), _ptr(temp), temp.numel(),
+                ctypes.c_void_p(stream)))
+        self.step0 += T
+
+    def pop_records(self):
+        """(records, dropped): the records logged since the last pop as an OP_DTYPE array in the
+        order they were numbered (the bytes the kernel wrote) and the number that did not fit the
+        capacity.  Synchronises; empties the log, keeps the carry."""
+        count = int(self.count.item())
+        n = min(count, self.capacity)
+        recs = self.recs[:n * OP_DTYPE.itemsize].cpu().numpy().view(OP_DTYPE).copy()
+        self.count.zero_()
+        return recs, max(0, count - self.capacity)
+
+    def pop(self):
+        """Every record logged since the last pop as a dict of numpy arrays: env, episode_start,
+        resource (1 AGV, 2 small machine, 3 big machine), finished, order, first, count, start,
+        end, from_loc, to_loc, the raw `records` and dropped = the ops that did not fit the
+        capacity.  Synchronises; empties the log (the carry of the open episodes is kept)."""
+        return records_dict(*self.pop_records())
+
+    def reset(self, env_mask=None):
+        """Zero the carry of the selected envs (all by default): after a manual env.reset."""
+        import torch
+        if env_mask is None:
+            self.carry.zero_()
+            return
+        m = torch.as_tensor(env_mask, device=self.device).bool()
+        self.carry.masked_fill_(m[None, :], 0)
+
+
+__all__ = ["OP_DTYPE", "ScheduleLog", "schedule_reference", "gantt", "check", "records_dict", "tray_fields",
+           "CARRY_WORDS", "carry_words", "temp_bytes"]

@@ -23,8 +23,10 @@ def _ptr(t):
 class Buffers:
     """Output tensors for T steps of N envs (T = 1 for step/reset)."""
 
-    def __init__(self, T, N, device, infos=True, next_obs=False, feats=False, obs=True):
+    def __init__(self, T, N, device, infos=True, next_obs=False, feats=False, obs=True, held=False):
         z = lambda *s, dt: torch.zeros(*s, dtype=dt, device=device)  # noqa: E731
+        # held: the held-tray words int32 [T, 3, N] (fjsp_step_held; not part of fjsp_out)
+        self.held = z(T, 3, N, dt=torch.int32) if held else None
         # feats: a2c global-state features f32 [T, 38, N] of the post-auto-reset observation
         self.feats = z(T, NFEAT, N, dt=torch.float32) if feats else None
         if not obs:   # a2c-only outputs: features, post-reset masks, rewards, term, trunc
@@ -66,6 +68,19 @@ class Buffers:
             t = getattr(self, k, None)
             setattr(o, k, t.data_ptr() if t is not None else None)
         return o
+
+
+class RowBuffers:
+    """Row k of a [T, ...] Buffers as the T = 1 outputs of one step (views, no copies)."""
+
+    def __init__(self, b, k):
+        for f in nat.OUT_FIELDS:
+            t = getattr(b, f, None)
+            setattr(self, f, None if t is None else t[k:k + 1])
+        self._struct = Buffers.struct(self)
+
+    def struct(self):
+        return self._struct
 
 
 class FJSPVecEnv:
@@ -143,10 +158,25 @@ class FJSPVecEnv:
         nat.check(nat.lib().fjsp_reset(self._h, _ptr(s), _ptr(m), self._num_orders, ctypes.byref(out)))
         return b
 
-    def step(self, actions, agent_order=None, autoreset=True, buffers=None):
+    def actions(self, policy="heuristic", action_seed=0, step=0, out=None):
+        """The actions rollout(policy=..., action_seed=..., step0=step) would draw for the current
+        state at vector step `step` (fjsp_actions): uint8 [8, N], what step() takes."""
+        self._sync_stream()
+        if out is None:
+            out = torch.empty(NA, self.num_envs, dtype=torch.uint8, device=self.device)
+        if out.dtype != torch.uint8 or not out.is_contiguous() or out.device != self.device or \
+                tuple(out.shape) != (NA, self.num_envs):
+            raise ValueError(f"out must be a contiguous uint8 [8, {self.num_envs}] tensor on the env's device")
+        nat.check(nat.lib().fjsp_actions(self._h, POLICIES[policy], int(action_seed) & (2**64 - 1), self.env_id_base,
+                                         int(step), _ptr(out)))
+        return out
+
+    def step(self, actions, agent_order=None, autoreset=True, buffers=None, held=None):
         """One FJSPSimulation.step per env (FJSPSimulation.py:144-242).
 
-        actions: uint8 tensor [8, N] (agent-major) on the env's device."""
+        actions: uint8 tensor [8, N] (agent-major) on the env's device.  held: an int32 / uint32
+        [3, N] tensor (or a [1, 3, N] slab row) that receives the step's held-tray words
+        (fjsp_step_held, schedule.py); None: plain fjsp_step."""
         self._sync_stream()
         a = actions
         if a.dtype != torch.uint8 or not a.is_contiguous() or a.device != self.device:
@@ -161,6 +191,13 @@ class FJSPVecEnv:
         if agent_order is not None:
             order = (ctypes.c_uint8 * 8)(*[int(x) for x in agent_order])
         out = buffers.struct()
+        if held is not None:
+            if held.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not held.is_contiguous() or \
+                    held.device != self.device or held.numel() != 3 * self.num_envs:
+                raise ValueError(f"held must be a contiguous int32 [3, {self.num_envs}] tensor on the env's device")
+            nat.check(nat.lib().fjsp_step_held(self._h, _ptr(a), order, int(bool(autoreset)), ctypes.byref(out),
+                                               _ptr(held)))
+            return buffers
         nat.check(nat.lib().fjsp_step(self._h, _ptr(a), order, int(bool(autoreset)), ctypes.byref(out)))
         return buffers
 
@@ -283,6 +320,40 @@ class FJSPVecEnv:
                      b.sim_time[:k])
             done += k
         return {"episodes": log.pop(), "kpis": kpi.pop()}
+
+    def evaluate_schedule(self, policy="heuristic", num_orders=5, steps=500, seeds=None, action_seed=0, chunk=256):
+        """evaluate_kpis with the per-operation schedule beside it: from a reset, per vector step
+        the policy's actions (fjsp_actions) and one fjsp_step_held into row k of a chunk slab, each
+        chunk scanned into an EpisodeLog, a kpis.KpiLog and a schedule.ScheduleLog.  The states and
+        outputs are rollout()'s with the same seeds.  Returns {"episodes", "kpis", "ops"}; an op's
+        (env, episode_start) is an episode record's (env, end_step - length).  Only the records
+        reach the host."""
+        from .episodes import EpisodeLog
+        from .kpis import KpiLog
+        from .schedule import ScheduleLog
+        steps, chunk = int(steps), max(1, min(int(chunk), int(steps)))
+        self.reset(seeds=seeds, num_orders=num_orders)
+        cap = max(65536, self.num_envs * (steps // 16 + 1))   # as evaluate_episodes
+        log = EpisodeLog(self.num_envs, self.device, env_id_base=self.env_id_base, capacity=cap)
+        kpi = KpiLog(self.num_envs, self.device, env_id_base=self.env_id_base, capacity=cap)
+        # an op takes at least one step per resource, an AGV op two (pickup, drop): 3 per 2 steps bounds it
+        ops = ScheduleLog(self.num_envs, self.device, env_id_base=self.env_id_base,
+                          capacity=max(65536, self.num_envs * (3 * steps // 2 + 3)))
+        b = Buffers(chunk, self.num_envs, self.device, infos=True, held=True)
+        rows = [RowBuffers(b, k) for k in range(chunk)]
+        act = torch.empty(NA, self.num_envs, dtype=torch.uint8, device=self.device)
+        done = 0
+        while done < steps:
+            k = min(chunk, steps - done)
+            for j in range(k):
+                self.actions(policy, action_seed=action_seed, step=done + j, out=act)
+                self.step(act, autoreset=True, buffers=rows[j], held=b.held[j])
+            log.scan(b.rewards[:k], b.term[:k], b.trunc[:k], b.orders_completed[:k], b.packaged[:k])
+            kpi.scan(b.results[:k], b.term[:k], b.trunc[:k], b.obs_i8[:k], b.orders_completed[:k], b.packaged[:k],
+                     b.sim_time[:k])
+            ops.scan(b.results[:k], b.held[:k], b.term[:k], b.trunc[:k])
+            done += k
+        return {"episodes": log.pop(), "kpis": kpi.pop(), "ops": ops.pop()}
 
     def pack_a2c(self, feats=None, masks=None):
         """a2c features f32 [38, N] and masks int8 [29, N] of the current observations
@@ -418,4 +489,4 @@ def gae_shared(rewards, values, done, gamma, lamb, out_ret=None, out_adv=None):
     return ret, adv
 
 
-__all__ = ["FJSPVecEnv", "Buffers", "gae", "gae_shared", "AGENTS"]
+__all__ = ["FJSPVecEnv", "Buffers", "RowBuffers", "gae", "gae_shared", "AGENTS"]
