@@ -476,6 +476,75 @@ int fjsp_schedule_scan(const uint32_t* results,   /* u32 [T][8][N]; rows 1..3 ar
                        int64_t* count,            /* device i64 [1], read and advanced on the device */
                        void* temp, uint64_t temp_bytes, void* stream);
 
+/* ---- Packaging runs in the schedule (DESIGN.md §4 "Packaging runs"): how long a tray waited at a
+ * packaging station, in which batch it was packaged and when (the reference's logger events
+ * packaging_start / packaging_complete, PackagingAgent.py).
+ *
+ * Pack words: four u32 per env and step, row s = station s (agents 4..7: blue_1, blue_2, red,
+ * green), of the state the held-tray words are of (after the run, before an auto-reset):
+ *   bits [0,8)   runs: tray runs at the station, queued and in flight.  A run is the products of
+ *                one tray as FJSPSimulation.add_tray_to_packaging appended them to the station's
+ *                product_queue (all of one order)
+ *   bits [8,20)  pending: products queued + in flight (len(product_queue) + resource.count)
+ *   bits [20,32) completed: products the station packaged this episode (products_completed)
+ * runs <= 255 (the tray-slot arena), pending <= 255 * 7 and completed <= 64 * 15, both < 4 096. */
+#define FJSP_PACK_ROWS 4
+#define FJSP_PACK_RUNS_MASK 0xFFu
+#define FJSP_PACK_PENDING_SHIFT 8
+#define FJSP_PACK_COMPLETED_SHIFT 20
+#define FJSP_PACK_FIELD_MASK 0xFFFu
+
+/* fjsp_step_held that also stores the step's pack words: held = device u32 [3][N], pack = device
+ * u32 [4][N], both not NULL and 4-byte aligned.  Everything else is fjsp_step_held's. */
+int fjsp_step_sched(fjsp_handle* h, const uint8_t* actions, const uint8_t* agent_order, int32_t autoreset,
+                    const fjsp_out* out, uint32_t* held, uint32_t* pack);
+
+/* fjsp_op_rec.info of a packaging record: resource [0,8) = 4 + s | finished bit 8 | granted bit 9 |
+ * from [16,20) = to [20,24) = 5 (LocationType PACKAGING). */
+#define FJSP_OP_GRANTED 0x200u
+
+/* int32 words per env of fjsp_packaging_scan's carry (host-only). */
+int fjsp_packaging_carry_words(void);
+/* Bytes of fjsp_packaging_scan's ring for N envs: u32 [4][256][N], 4 KB per env (host-only). */
+int fjsp_packaging_ring_bytes(int32_t N, uint64_t* bytes);
+/* Bytes of fjsp_packaging_scan's temp buffer for a [T][N] slab (host-only). */
+int fjsp_packaging_temp_bytes(int32_t T, int32_t N, uint64_t* bytes);
+/* Compacts per-step rows into one fjsp_op_rec per tray run at a packaging station.  Per station the
+ * runs are FIFO: arrival order = grant order = completion order (PackagingAgent.run grants the
+ * whole product_queue at a START and a batch completes at once).  Per env, t = 0..T-1 in order,
+ * ln = the 0-based step within the episode, prev_s / Hprev = station s's pack word / the AGV's held
+ * word of the episode's previous row (0 at its first), stations in the order 0..3:
+ *   arrival     the AGV's result word has drop_success (bit 4) and delivered_to_packaging (bit 5) and
+ *               pending + completed of s is higher than in prev_s: a run with tray code
+ *               Hprev & FJSP_HELD_CODE_MASK joins the tail of s's FIFO, ungranted (a drop whose
+ *               products are lost raises no station's counters and adds nothing);
+ *   start       the result word of agent 4 + s has started_packaging (bit 1): every ungranted run
+ *               of the FIFO, the one that arrived in this row included, is granted with start = ln;
+ *   completion  the runs the FIFO holds beyond runs(now) leave its head, each written finished with
+ *               its start and end = ln;
+ *   episode end (term | trunc), after the completions: every run left is written in FIFO order,
+ *               unfinished: granted runs keep their start and get end = -1, ungranted ones get
+ *               start = end = -1; the env's carry returns to all zero.
+ * tray = the run's code, reserved = 0, episode_start as in fjsp_schedule_scan's records.  Envs whose
+ * status has DIVERGED / PKG_WAIT get records of the library's own state.
+ * carry: i32 [fjsp_packaging_carry_words()][N] and ring: u32 [4][256][N] (fjsp_packaging_ring_bytes),
+ * both in/out and the scan's own, all zero = fresh; scanning a slab in pieces gives the records of
+ * scanning it whole.  Ordering and capacity as fjsp_schedule_scan: record k of the slab in row-major
+ * (t, env, station, FIFO position) order gets index count_in + k, is written only if that is < cap,
+ * and *count advances by every record of the slab.  results, held, pack, carry and ring 4-byte, count
+ * 8-byte, recs and temp 16-byte aligned; recs may be NULL when cap == 0.  T * N < 2^30.  Three
+ * launches ordered by the stream alone (count, offsets, write).  Stream-ordered. */
+int fjsp_packaging_scan(const uint32_t* results,   /* u32 [T][8][N]; rows 1 and 4..7 are read */
+                        const uint32_t* held,      /* u32 [T][3][N]; row 0 is read */
+                        const uint32_t* pack,      /* u32 [T][4][N] */
+                        const uint8_t* term, const uint8_t* trunc,   /* u8 [T][N] */
+                        int32_t T, int32_t N, uint32_t env_gid0, int64_t step0,
+                        int32_t* carry,            /* i32 [words][N] in/out */
+                        uint32_t* ring,            /* u32 [4][256][N] in/out */
+                        fjsp_op_rec* recs, int64_t cap,
+                        int64_t* count,            /* device i64 [1], read and advanced on the device */
+                        void* temp, uint64_t temp_bytes, void* stream);
+
 /* Synchronous host copy of one env's state summary (debug / facade use). */
 int fjsp_read_env(fjsp_handle* h, int32_t env, fjsp_env_view* out);
 /* Wait for all work queued on the handle's stream. */

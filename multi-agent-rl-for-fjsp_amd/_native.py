@@ -79,7 +79,9 @@ EXPORTS = ["fjsp_abi_version", "fjsp_last_error", "fjsp_default_config", "fjsp_c
            "fjsp_a2c_wgrad", "fjsp_server_start", "fjsp_server_step", "fjsp_server_step_actions", "fjsp_server_stop",
            "fjsp_episode_temp_bytes", "fjsp_episode_scan", "fjsp_a2c_actor_head_ppo",
            "fjsp_kpi_carry_words", "fjsp_kpi_scan", "fjsp_step_held", "fjsp_actions",
-           "fjsp_schedule_carry_words", "fjsp_schedule_temp_bytes", "fjsp_schedule_scan"]
+           "fjsp_schedule_carry_words", "fjsp_schedule_temp_bytes", "fjsp_schedule_scan",
+           "fjsp_step_sched", "fjsp_packaging_carry_words", "fjsp_packaging_ring_bytes",
+           "fjsp_packaging_temp_bytes", "fjsp_packaging_scan"]
 POLICY_ACTOR_DPAD, POLICY_CRITIC_DPAD = 16, 48
 POLICY_ACTOR_FLOATS = 3 * 256 * 16 // 2 + 256 + 3 * 256 * 256 // 2 + 256 + 8 * 256 + 16
 POLICY_CRITIC_FLOATS = 3 * 256 * 48 // 2 + 256 + 3 * 256 * 256 // 2 + 256 + 3 * 128 * 256 // 2 + 128 + 128 + 16
@@ -221,6 +223,11 @@ def lib():
         "fjsp_schedule_carry_words": (I, []),
         "fjsp_schedule_temp_bytes": (I, [I, I, ctypes.POINTER(U64)]),
         "fjsp_schedule_scan": (I, [P, P, P, P, I, I, U32, ctypes.c_int64, P, P, ctypes.c_int64, P, P, U64, P]),
+        "fjsp_step_sched": (I, [P, P, P, I, ctypes.POINTER(fjsp_out), P, P]),
+        "fjsp_packaging_carry_words": (I, []),
+        "fjsp_packaging_ring_bytes": (I, [I, ctypes.POINTER(U64)]),
+        "fjsp_packaging_temp_bytes": (I, [I, I, ctypes.POINTER(U64)]),
+        "fjsp_packaging_scan": (I, [P, P, P, P, P, I, I, U32, ctypes.c_int64, P, P, P, ctypes.c_int64, P, P, U64, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

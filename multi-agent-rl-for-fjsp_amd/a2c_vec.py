@@ -1762,7 +1762,7 @@ class VecMultiAgentA2C:
 
     @torch.no_grad()
     def evaluate_kpis(self, num_orders=5, steps=500, seeds=None, deterministic=True, env=None, chunk=64,
-                      trace=False, schedule=False):
+                      trace=False, schedule=False, packaging=False):
         """The learned policy over `steps` vector steps from a reset with auto-reset (an env starts
         its next episode at once), every finished episode accounted twice on the device: returns
         and lengths (episodes.EpisodeLog) and the shop-floor KPIs (kpis.KpiLog: makespan, flow
@@ -1779,12 +1779,17 @@ class VecMultiAgentA2C:
         schedule=True: the steps go through fjsp_step_held, whose held-tray words are scanned into
         a schedule.ScheduleLog beside the two logs, and the result has "ops" = its pop() (one record
         per machine / AGV operation; schedule.gantt, schedule.check).  Everything else is the same.
+        packaging=True (needs schedule=True): the steps go through fjsp_step_sched instead, whose
+        pack words feed a schedule.PackagingLog with the same rows, and the result has "pack_ops" =
+        its pop() (one record per tray run at a packaging station; schedule.check_packaging).
 
         KPIs of the training rollouts themselves come from track_kpis=True (account_kpis /
         pop_kpis, learn()'s training_kpis): the collect then fills the same slabs for the batches
         the update trains on, and no separate rollout is needed."""
         from .episodes import EpisodeLog
         from .kpis import KpiLog
+        if packaging and not schedule:
+            raise ValueError("packaging=True needs schedule=True: the pack words come with the held words")
         on_train = env is None or env is self.env
         env = self.env if env is None else env
         N, dev = env.num_envs, self.device
@@ -1814,6 +1819,11 @@ class VecMultiAgentA2C:
             from .schedule import ScheduleLog
             s["held"] = z(C, 3, N, dt=torch.int32)
             ops = ScheduleLog(N, dev, env_id_base=env.env_id_base, capacity=max(65536, N * (3 * steps // 2 + 3)))
+        pk = None
+        if packaging:
+            from .schedule import PackagingLog
+            s["pack"] = z(C, 4, N, dt=torch.int32)
+            pk = PackagingLog(N, dev, env_id_base=env.env_id_base, capacity=max(65536, N * (steps // 2 + 1)))
         env.reset(seeds=seeds, num_orders=num_orders)
         env.pack_a2c(s["feats"][0], s["masks"][0])
         keep = {k: [] for k in s if k not in ("feats", "masks", "status")} if trace else None
@@ -1831,7 +1841,11 @@ class VecMultiAgentA2C:
                 else:
                     s["actions"][t].copy_(self.policy(s["feats"][t], s["masks"][t], deterministic, t=done + t,
                                                       gid0=env.env_id_base)[0])
-                if schedule:
+                if packaging:
+                    nat.check(L.fjsp_step_sched(h, ctypes.c_void_p(s["actions"][t].data_ptr()), None, 1,
+                                                ctypes.byref(outs[t]), ctypes.c_void_p(s["held"][t].data_ptr()),
+                                                ctypes.c_void_p(s["pack"][t].data_ptr())))
+                elif schedule:
                     nat.check(L.fjsp_step_held(h, ctypes.c_void_p(s["actions"][t].data_ptr()), None, 1,
                                                ctypes.byref(outs[t]), ctypes.c_void_p(s["held"][t].data_ptr())))
                 else:
@@ -1841,6 +1855,8 @@ class VecMultiAgentA2C:
                      s["packaged"][:k], s["sim_time"][:k])
             if schedule:
                 ops.scan(s["results"][:k], s["held"][:k], s["term"][:k], s["trunc"][:k])
+            if packaging:
+                pk.scan(s["results"][:k], s["held"][:k], s["pack"][:k], s["term"][:k], s["trunc"][:k])
             if trace:
                 for name in keep:
                     keep[name].append(s[name][:k].cpu().numpy().copy())
@@ -1850,6 +1866,8 @@ class VecMultiAgentA2C:
         res = {"episodes": log.pop(), "kpis": kpi.pop()}
         if schedule:
             res["ops"] = ops.pop()
+        if packaging:
+            res["pack_ops"] = pk.pop()
         if trace:
             import numpy as np
             res["trace"] = {name: np.concatenate(v) for name, v in keep.items()}

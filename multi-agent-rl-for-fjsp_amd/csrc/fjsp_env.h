@@ -1137,6 +1137,18 @@ FJSP_DEV void held_words(const Env& E, uint32_t v[3]) {
     for (int m = 0; m < 2; m++) v[1 + m] = held_word(E.m_cur(m) != NIL, E.m_code(m)) | ((uint32_t)E.m_busy(m) << 14);
 }
 
+// Pack words (include/fjsp.h, fjsp_step_sched): one per packaging station s, taken where the held
+// words are: runs [0,8) = the length of list L_PKG + s (tray runs queued and in flight) |
+// pending [8,20) = p_queued + p_inflight (len(product_queue) + resource.count) | completed [20,32)
+// = p_completed (products_completed).  runs <= 255 by the slot arena; pending <= 255 slots x 7
+// products = 1 785 and completed <= 64 orders x 15 products = 960, both below 4 096.  Reads only.
+FJSP_DEV void pack_words(const Env& E, uint32_t v[4]) {
+#pragma unroll
+    for (int s = 0; s < 4; s++)
+        v[s] = ((uint32_t)E.ll(L_PKG + s) & 0xFFu) | (((uint32_t)(E.p_queued(s) + E.p_inflight(s)) & 0xFFFu) << 8) |
+               (((uint32_t)E.p_completed(s) & 0xFFFu) << 20);
+}
+
 // ---------------------------------------------------------------- heuristic policy
 // MultiAgentA2C._get_heuristic_actions (a2c.py:390-537) on the packed state.  The reference
 // compares the AGV position with (2,3) small, (0,3) big, (0,0) pickup, (3,5) packaging and

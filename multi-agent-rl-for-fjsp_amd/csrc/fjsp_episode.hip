@@ -687,6 +687,243 @@ bool sched_temp_layout(int32_t T, int32_t N, uint64_t* table, uint64_t* total) {
     return true;
 }
 
+// ---- packaging runs (include/fjsp.h: fjsp_packaging_scan) --------------------------------------
+// One record per tray run at a packaging station.  Per station the runs are FIFO (arrival order =
+// grant order = completion order), so the records a row writes follow from the pack words'
+// counters and the walk keeps k_schedule_scan's shape: k_packaging_scan<false> counts,
+// k_episode_offsets, k_packaging_scan<true> writes; one wave per 64 envs, one lane per env, EP_U
+// rows per load batch with the next batch issued before the current one is walked.  Per row and
+// env: the result words of the AGV and the four stations, the AGV's held word, the four pack words
+// and the two flags, 42 bytes.
+//   count  a lane's records of a row = sum over s of the runs that left station s's FIFO, plus at
+//          an episode end the runs still in it; the lanes' sum -> cnt[t][w] (lane 0).  Needs the
+//          words and the carry only (never the rings), writes neither
+//   write  the FIFO work.  A lane can write many records in one row, so its rank is offs[t][w] +
+//          an exclusive wave prefix sum of the lanes' counts (shuffles), taken only in rows where
+//          some lane writes; the loops at an arrival, a START and a completion sit behind
+//          wave-uniform branches of their own.  Records in (t, env, station, FIFO position) order
+// FIFO: ring u32 [4][PK_RING][N] (lane-contiguous), entry = tray code [0,13) | granted 13 |
+// start << 16; 8-bit head / granted / tail indices (the arena's 255 slots bound an env's pending
+// runs, so 256 entries cannot overflow; a fuller FIFO could only come from rows that are not one
+// env's, and then wraps inside the env's own ring).  The FIFO's length, not runs(prev), is what the
+// departures are taken from (clamped to what the FIFO holds): the two are equal whenever the scan
+// has seen the episode from its first row, and a log attached mid-episode stays self-consistent.
+constexpr int PK_LEN = 0;      // carry words [PK_WORDS][N]: steps of the open episode,
+constexpr int PK_HPREV = 1;    // the AGV's held word of the previous row,
+constexpr int PK_PREV = 2;     // + s: station s's pack word of the previous row,
+constexpr int PK_IDX = 6;      // + s: head [0,8) | first ungranted [8,16) | tail [16,24) of its ring
+constexpr int PK_WORDS = 10;
+constexpr int PK_S = 4;        // stations: agent 4 + s
+constexpr int PK_RING = 256;
+constexpr uint32_t PK_GRANTED = 1u << 13;
+
+struct PackArgs {
+    const uint32_t* res;
+    const uint32_t* held;
+    const uint32_t* pack;
+    const uint8_t* term;
+    const uint8_t* trunc;
+    fjsp_op_rec* recs;
+    int32_t* carry;
+    uint32_t* ring;
+    long long cap, base, step0;
+    uint32_t gid0;
+    int T, N;
+};
+
+template <bool WRITE>
+struct PackChunk {
+    uint32_t agv[EP_U], pk[PK_S][EP_U];
+    uint32_t st[WRITE ? PK_S : 1][EP_U], held[EP_U];   // the count pass loads neither
+    uint8_t te[EP_U], tr[EP_U];
+    uint32_t off[EP_U];
+};
+
+template <bool WRITE>
+__device__ __forceinline__ void pack_load(PackChunk<WRITE>& c, const PackArgs& p, const uint32_t* __restrict__ offs, int t0,
+                                          int W, int w, uint32_t col) {
+    const size_t N = (size_t)p.N;
+#pragma unroll
+    for (int j = 0; j < EP_U; j++) {
+        const size_t t = (size_t)(t0 + j < p.T ? t0 + j : p.T - 1);
+        const uint32_t* __restrict__ rr = p.res + t * EP_A * N;
+        const uint32_t* __restrict__ pr = p.pack + t * PK_S * N;
+        c.agv[j] = rr[N + col];
+#pragma unroll
+        for (int s = 0; s < PK_S; s++) {
+            c.pk[s][j] = pr[(size_t)s * N + col];
+            if constexpr (WRITE) c.st[s][j] = rr[(size_t)(4 + s) * N + col];
+        }
+        if constexpr (WRITE) c.held[j] = p.held[t * SC_R * N + col];
+        c.te[j] = p.term[t * N + col];
+        c.tr[j] = p.trunc[t * N + col];
+        c.off[j] = WRITE ? offs[t * W + w] : 0u;
+    }
+}
+
+struct PackState {
+    int32_t len;
+    uint32_t hprev;
+    uint32_t prev[PK_S], idx[PK_S];
+};
+
+__device__ __forceinline__ uint32_t pk_total(uint32_t w) { return ((w >> 8) & 0xFFFu) + (w >> 20); }   // pending + completed
+
+template <bool WRITE>
+__device__ __forceinline__ void pack_rows(const PackChunk<WRITE>& c, int t0, const PackArgs& p, uint32_t* __restrict__ cnt,
+                                          int W, int w, int e, int lane, bool live, PackState& s) {
+    const int rows = min(EP_U, p.T - t0);
+    const size_t N = (size_t)p.N;
+    uint32_t* __restrict__ ring = p.ring + (live ? e : 0);   // entry i of station q: ring[(q * PK_RING + i) * N]
+#pragma unroll
+    for (int j = 0; j < EP_U; j++) {
+        if (j < rows) {   // wave-uniform
+            const bool end = (c.te[j] | c.tr[j]) != 0;
+            const bool drop = (c.agv[j] & 0x30u) == 0x30u;   // drop_success and delivered_to_packaging
+            uint32_t leave[PK_S], rest[PK_S];
+            uint32_t n = 0, arr = 0;   // arr: bit q = a run joins station q (at most one)
+#pragma unroll
+            for (int q = 0; q < PK_S; q++) {
+                const uint32_t now = c.pk[q][j];
+                const bool arrived = drop && pk_total(now) > pk_total(s.prev[q]);
+                const uint32_t have = ((s.idx[q] >> 16) - s.idx[q] & 0xFFu) + (arrived ? 1u : 0u);
+                const uint32_t stay = min(now & 0xFFu, have);
+                leave[q] = have - stay;
+                rest[q] = end ? stay : 0u;
+                n += leave[q] + rest[q];
+                arr |= arrived ? 1u << q : 0u;
+                s.prev[q] = end ? 0u : now;
+            }
+            if (!live) n = 0;
+            if constexpr (!WRITE) {
+                uint32_t sum = n;   // the wave's sum: every lane gets it
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+                if (lane == 0) cnt[(size_t)(t0 + j) * W + w] = sum;
+#pragma unroll
+                for (int q = 0; q < PK_S; q++) {   // the indices as the write pass leaves them, lengths only
+                    const uint32_t h = s.idx[q] + leave[q] & 0xFFu, tl = (s.idx[q] >> 16) + (arr >> q & 1u) & 0xFFu;
+                    s.idx[q] = end ? 0u : h | h << 8 | tl << 16;
+                }
+            } else {
+                const uint32_t ln = (uint32_t)s.len;
+                if (__ballot(live && arr != 0)) {   // an arrival: the previous row's AGV code joins the tail
+                    if (live && arr != 0) {
+                        const uint32_t q = (uint32_t)__ffs((int)arr) - 1u;
+                        uint32_t ix = s.idx[0];
+#pragma unroll
+                        for (int k = 1; k < PK_S; k++) ix = q == (uint32_t)k ? s.idx[k] : ix;
+                        const uint32_t tl = ix >> 16 & 0xFFu;
+                        ring[((size_t)q * PK_RING + tl) * N] = s.hprev & FJSP_HELD_CODE_MASK;
+                        ix = (ix & 0xFFFFu) | (tl + 1u & 0xFFu) << 16;
+#pragma unroll
+                        for (int k = 0; k < PK_S; k++) s.idx[k] = q == (uint32_t)k ? ix : s.idx[k];
+                    }
+                }
+                bool go[PK_S];
+                bool any_go = false;
+#pragma unroll
+                for (int q = 0; q < PK_S; q++) {   // started_packaging with an ungranted run in the FIFO
+                    go[q] = live && (c.st[q][j] & 2u) != 0 && (s.idx[q] >> 8 & 0xFFu) != (s.idx[q] >> 16 & 0xFFu);
+                    any_go = any_go || go[q];
+                }
+                if (__ballot(any_go)) {   // a START: every ungranted run gets the grant and this step
+#pragma unroll
+                    for (int q = 0; q < PK_S; q++) {
+                        if (go[q]) {
+                            const uint32_t tl = s.idx[q] >> 16 & 0xFFu;
+                            for (uint32_t i = s.idx[q] >> 8 & 0xFFu; i != tl; i = i + 1u & 0xFFu) {
+                                uint32_t* __restrict__ en = ring + ((size_t)q * PK_RING + i) * N;
+                                *en = (*en & FJSP_HELD_CODE_MASK) | PK_GRANTED | ln << 16;
+                            }
+                            s.idx[q] = (s.idx[q] & 0xFF00FFu) | tl << 8;
+                        }
+                    }
+                }
+                if (__ballot(n != 0)) {   // some lane writes: ranks by an exclusive prefix sum of the counts
+                    uint32_t inc = n;
+#pragma unroll
+                    for (int d = 1; d < 64; d <<= 1) {
+                        const uint32_t o = __shfl_up(inc, d);
+                        if (lane >= d) inc += o;
+                    }
+                    long long rank = p.base + (long long)c.off[j] + (long long)(inc - n);
+                    const long long es = p.step0 + (long long)(t0 + j) - (long long)s.len;
+                    if (n != 0) {
+#pragma unroll
+                        for (int q = 0; q < PK_S; q++) {
+                            const uint32_t m = leave[q] + rest[q];
+                            uint32_t h = s.idx[q] & 0xFFu;
+                            for (uint32_t i = 0; i < m; i++) {
+                                const uint32_t en = ring[((size_t)q * PK_RING + h) * N];
+                                const bool fin = i < leave[q], granted = (en & PK_GRANTED) != 0;
+                                if ((unsigned long long)rank < (unsigned long long)p.cap) {
+                                    const uint32_t info = (uint32_t)(4 + q) | (fin ? 1u << 8 : 0u) | (granted ? 1u << 9 : 0u) |
+                                                          5u << 16 | 5u << 20;
+                                    uint4* o = reinterpret_cast<uint4*>(p.recs + rank);
+                                    o[0] = make_uint4(p.gid0 + (uint32_t)e, info, (uint32_t)es, (uint32_t)((unsigned long long)es >> 32));
+                                    o[1] = make_uint4(en & FJSP_HELD_CODE_MASK, granted ? en >> 16 : ~0u, fin ? ln : ~0u, 0u);
+                                }
+                                rank += 1;
+                                h = h + 1u & 0xFFu;
+                            }
+                            s.idx[q] = (s.idx[q] & 0xFFFF00u) | h;
+                        }
+                    }
+                }
+                if (end) {
+#pragma unroll
+                    for (int q = 0; q < PK_S; q++) s.idx[q] = 0u;
+                }
+                s.hprev = end ? 0u : c.held[j];
+            }
+            s.len = end ? 0 : s.len + 1;
+        }
+    }
+}
+
+template <bool WRITE>
+__global__ void __launch_bounds__(64) k_packaging_scan(PackArgs p, uint32_t* __restrict__ cnt,
+                                                       const long long* __restrict__ base, int W) {
+    if (WRITE) p.base = base[0];
+    const int lane = threadIdx.x, w = (int)blockIdx.x;
+    const int e = w * 64 + lane;
+    const bool live = e < p.N;
+    const uint32_t col = (uint32_t)min(e, p.N - 1);
+    const size_t N = (size_t)p.N;
+    int32_t* __restrict__ cy = p.carry + col;   // word k of this env: cy[k * N]
+    PackState s{};
+    s.len = cy[(size_t)PK_LEN * N];
+    s.hprev = (uint32_t)cy[(size_t)PK_HPREV * N];
+#pragma unroll
+    for (int q = 0; q < PK_S; q++) {
+        s.prev[q] = (uint32_t)cy[(size_t)(PK_PREV + q) * N];
+        s.idx[q] = (uint32_t)cy[(size_t)(PK_IDX + q) * N];
+    }
+    PackChunk<WRITE> A, B;
+    int t0 = 0;
+    pack_load<WRITE>(A, p, cnt, 0, W, w, col);
+    for (;;) {   // A holds t0.., B is loaded before A's rows are walked, and the other way round
+        pack_load<WRITE>(B, p, cnt, t0 + EP_U, W, w, col);
+        pack_rows<WRITE>(A, t0, p, cnt, W, w, e, lane, live, s);
+        t0 += EP_U;
+        if (t0 >= p.T) break;
+        pack_load<WRITE>(A, p, cnt, t0 + EP_U, W, w, col);
+        pack_rows<WRITE>(B, t0, p, cnt, W, w, e, lane, live, s);
+        t0 += EP_U;
+        if (t0 >= p.T) break;
+    }
+    if (WRITE && live) {
+        cy[(size_t)PK_LEN * N] = s.len;
+        cy[(size_t)PK_HPREV * N] = (int32_t)s.hprev;
+#pragma unroll
+        for (int q = 0; q < PK_S; q++) {
+            cy[(size_t)(PK_PREV + q) * N] = (int32_t)s.prev[q];
+            cy[(size_t)(PK_IDX + q) * N] = (int32_t)s.idx[q];
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -837,6 +1074,72 @@ int fjsp_schedule_scan(const uint32_t* results, const uint32_t* held, const uint
     hipLaunchKernelGGL(k_schedule_scan<false>, dim3((unsigned)W), dim3(64), 0, st, p, offs, base, W);
     hipLaunchKernelGGL(k_episode_offsets, dim3(1), dim3(EPO_THREADS), 0, st, offs, L, base, (long long*)count);
     hipLaunchKernelGGL(k_schedule_scan<true>, dim3((unsigned)W), dim3(64), 0, st, p, offs, base, W);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        fjsp_internal_fail(hipGetErrorString(e));
+        return -2;
+    }
+    return 0;
+}
+
+int fjsp_packaging_carry_words(void) { return PK_WORDS; }
+
+int fjsp_packaging_ring_bytes(int32_t N, uint64_t* bytes) {
+    if (N <= 0) return fjsp_internal_fail("fjsp_packaging_ring_bytes: N must be > 0");
+    if (!bytes) return fjsp_internal_fail("fjsp_packaging_ring_bytes: null pointer");
+    *bytes = (uint64_t)PK_S * PK_RING * 4 * (uint64_t)N;
+    return 0;
+}
+
+int fjsp_packaging_temp_bytes(int32_t T, int32_t N, uint64_t* bytes) {
+    if (T <= 0 || N <= 0) return fjsp_internal_fail("fjsp_packaging_temp_bytes: T and N must be > 0");
+    if (!bytes) return fjsp_internal_fail("fjsp_packaging_temp_bytes: null pointer");
+    uint64_t table, total;
+    if (!sched_temp_layout(T, N, &table, &total)) return fjsp_internal_fail("fjsp_packaging_temp_bytes: T * N must be < 2^30");
+    *bytes = total;
+    return 0;
+}
+
+int fjsp_packaging_scan(const uint32_t* results, const uint32_t* held, const uint32_t* pack, const uint8_t* term,
+                        const uint8_t* trunc, int32_t T, int32_t N, uint32_t env_gid0, int64_t step0, int32_t* carry,
+                        uint32_t* ring, fjsp_op_rec* recs, int64_t cap, int64_t* count, void* temp, uint64_t temp_bytes,
+                        void* stream) {
+    if (T <= 0 || N <= 0) return fjsp_internal_fail("fjsp_packaging_scan: T and N must be > 0");
+    if (cap < 0) return fjsp_internal_fail("fjsp_packaging_scan: cap must be >= 0");
+    if (!results || !held || !pack || !term || !trunc || !carry || !ring || !count || !temp || (cap > 0 && !recs))
+        return fjsp_internal_fail("fjsp_packaging_scan: null buffer");
+    uint64_t table, total;
+    // at most one arrival per env and row, and 255 runs per env carried in: the sums stay in 32 bits
+    if (!sched_temp_layout(T, N, &table, &total)) return fjsp_internal_fail("fjsp_packaging_scan: T * N must be < 2^30");
+    if (temp_bytes < total) return fjsp_internal_fail("fjsp_packaging_scan: temp buffer too small");
+    if ((((uintptr_t)recs | (uintptr_t)temp) & 15u) != 0)
+        return fjsp_internal_fail("fjsp_packaging_scan: recs and temp must be 16-byte aligned");
+    if ((((uintptr_t)results | (uintptr_t)held | (uintptr_t)pack | (uintptr_t)carry | (uintptr_t)ring) & 3u) != 0 ||
+        ((uintptr_t)count & 7u) != 0)
+        return fjsp_internal_fail("fjsp_packaging_scan: results, held, pack, carry and ring must be 4-byte, count 8-byte aligned");
+    const int W = (int)(((int64_t)N + 63) / 64);
+    const int L = T * W;
+    uint32_t* offs = (uint32_t*)temp;
+    long long* base = (long long*)((char*)temp + table);
+    const hipStream_t st = (hipStream_t)stream;
+    PackArgs p;
+    p.res = results;
+    p.held = held;
+    p.pack = pack;
+    p.term = term;
+    p.trunc = trunc;
+    p.recs = recs;
+    p.carry = carry;
+    p.ring = ring;
+    p.cap = cap;
+    p.base = 0;
+    p.step0 = step0;
+    p.gid0 = env_gid0;
+    p.T = T;
+    p.N = N;
+    hipLaunchKernelGGL(k_packaging_scan<false>, dim3((unsigned)W), dim3(64), 0, st, p, offs, base, W);
+    hipLaunchKernelGGL(k_episode_offsets, dim3(1), dim3(EPO_THREADS), 0, st, offs, L, base, (long long*)count);
+    hipLaunchKernelGGL(k_packaging_scan<true>, dim3((unsigned)W), dim3(64), 0, st, p, offs, base, W);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fjsp_internal_fail(hipGetErrorString(e));

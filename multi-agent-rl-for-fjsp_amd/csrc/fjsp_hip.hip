@@ -161,7 +161,8 @@ __global__ void __launch_bounds__(BLOCK) k_actions(DevState S, Cfg C, int mode, 
 // wave would shorten the union of the lanes' branches and spread 4 096 envs over all 256 CUs; it
 // measured slower (fjsp_step), so 64 stays the default.
 // HP: nothing, or uint32_t* = the held-tray words' destination u32 [3][N] (the HELD instances,
-// fjsp_step_held); without it the kernel has the arguments and the code it had before.
+// fjsp_step_held), or that and the pack words' destination u32 [4][N] (the SCHED instances,
+// fjsp_step_sched); without them the kernel has the arguments and the code it had before.
 template <bool CANON, int EPW, class... HP>
 __global__ void __launch_bounds__(BLOCK) k_step(DevState S, Cfg C, const uint8_t* __restrict__ actions, uint64_t order_packed,
                                                 int autoreset, fjsp_out out, HP... held) {
@@ -2305,9 +2306,9 @@ int fjsp_reset(fjsp_handle* h, const uint32_t* seeds, const uint8_t* env_mask, i
     return 0;
 }
 
-// fjsp_step (held == NULL) and fjsp_step_held
+// fjsp_step (held == NULL), fjsp_step_held (pack == NULL) and fjsp_step_sched
 static int step_once(fjsp_handle* h, const uint8_t* actions, const uint8_t* agent_order, int32_t autoreset,
-                     const fjsp_out* out, uint32_t* held) {
+                     const fjsp_out* out, uint32_t* held, uint32_t* pack = nullptr) {
     SERVER_QUIESCE(h);
     if (!actions) return fail("null actions");
     if (!h->has_reset) return fail("fjsp_step before fjsp_reset");
@@ -2330,7 +2331,10 @@ static int step_once(fjsp_handle* h, const uint8_t* actions, const uint8_t* agen
     with_epw(p.epw, [&](auto epw) {
         constexpr int EPW = decltype(epw)::value;
         const dim3 grid(p.grid), block(BLOCK);
-        if (held) {
+        if (held && pack) {
+            if (p.canon) hipLaunchKernelGGL((k_step<true, EPW, uint32_t*, uint32_t*>), grid, block, 0, h->stream, h->S, h->dcfg, actions, packed, autoreset, o, held, pack);
+            else hipLaunchKernelGGL((k_step<false, EPW, uint32_t*, uint32_t*>), grid, block, 0, h->stream, h->S, h->dcfg, actions, packed, autoreset, o, held, pack);
+        } else if (held) {
             if (p.canon) hipLaunchKernelGGL((k_step<true, EPW, uint32_t*>), grid, block, 0, h->stream, h->S, h->dcfg, actions, packed, autoreset, o, held);
             else hipLaunchKernelGGL((k_step<false, EPW, uint32_t*>), grid, block, 0, h->stream, h->S, h->dcfg, actions, packed, autoreset, o, held);
         } else {
@@ -2357,6 +2361,14 @@ int fjsp_step_held(fjsp_handle* h, const uint8_t* actions, const uint8_t* agent_
     if (((uintptr_t)held & 3u) != 0) return fail("fjsp_step_held: held must be 4-byte aligned");
     if (!h) return fail("null handle");
     return step_once(h, actions, agent_order, autoreset, out, held);
+}
+
+int fjsp_step_sched(fjsp_handle* h, const uint8_t* actions, const uint8_t* agent_order, int32_t autoreset,
+                    const fjsp_out* out, uint32_t* held, uint32_t* pack) {
+    if (!held || !pack) return fail("fjsp_step_sched: null held or pack buffer");
+    if ((((uintptr_t)held | (uintptr_t)pack) & 3u) != 0) return fail("fjsp_step_sched: held and pack must be 4-byte aligned");
+    if (!h) return fail("null handle");
+    return step_once(h, actions, agent_order, autoreset, out, held, pack);
 }
 
 int fjsp_actions(fjsp_handle* h, int32_t action_mode, uint64_t action_seed, uint32_t env_gid0, uint32_t step,

@@ -288,12 +288,13 @@ __device__ __forceinline__ uint64_t fmix64(uint64_t z) {
 // FULL = false: only obs, masks, rewards, term, trunc and status are written (the other
 // fjsp_out pointers are never read, so they take no SGPRs in the hot loop).
 // HP: nothing, or the held-tray slab u32 [T][3][N] of the HELD instance (fjsp_step_held): a
-// trailing pack, so every other instance keeps its arguments and its code.
+// trailing pack, so every other instance keeps its arguments and its code; or that slab and the
+// pack slab u32 [T][4][N] of the SCHED instance (fjsp_step_sched).
 template <bool CANON, bool FULL = true, class... HP>
 __device__ __forceinline__ void step_and_emit(Env& E, const Tables& T, const Cfg& C, const DevState& S, int e,
                                               const int* act, const uint8_t* order, int autoreset, const fjsp_out& out,
                                               uint32_t t, HP... held) {
-    static_assert(sizeof...(HP) <= 1, "at most the held-tray slab");
+    static_assert(sizeof...(HP) <= 2, "at most the held-tray slab and the pack slab");
     const uint32_t n = (uint32_t)S.n, ue = (uint32_t)e;
     uint32_t res[NA];
     const double g8 = env_advance<CANON>(E, T, C, act, order, res);
@@ -324,6 +325,16 @@ __device__ __forceinline__ void step_and_emit(Env& E, const Tables& T, const Cfg
         held_words(E, hv);
 #pragma unroll
         for (int r = 0; r < 3; r++) st32(hp, (t * 3u + (uint32_t)r) * n + ue, hv[r]);
+    }
+    if constexpr (sizeof...(HP) == 2) {   // SCHED (fjsp_step_sched): the held words and the pack words
+        uint32_t* const hp[2] = {held...};
+        uint32_t hv[3], pv[4];
+        held_words(E, hv);
+        pack_words(E, pv);
+#pragma unroll
+        for (int r = 0; r < 3; r++) st32(hp[0], (t * 3u + (uint32_t)r) * n + ue, hv[r]);
+#pragma unroll
+        for (int s = 0; s < 4; s++) st32(hp[1], (t * 4u + (uint32_t)s) * n + ue, pv[s]);
     }
     FJSP_STAMP(E, 5);
     E.set_step(E.step() + 1);

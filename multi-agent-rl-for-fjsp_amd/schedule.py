@@ -22,8 +22,30 @@ machine, big machine:
             (finished = 0, end = -1, AGV to = 0)
 A record's (env, episode_start) equals an EpisodeLog / KpiLog record's (env, end_step - length).
 
-Not covered: packaging batches (one START grants a whole queue of runs of several orders, batches
-overlap), the pickup station's tray release times, the fused and training step paths.
+
+Packaging runs (agents 4..7; the reference's logger events packaging_start / packaging_complete).
+One START grants a whole queue of tray runs of several orders and batches overlap, but per station
+the runs are FIFO: arrival order = grant order = completion order.  fjsp_step_sched stores four
+pack words per env beside the held words (``pack_fields``: runs, pending, completed of each
+station), and ``packaging_reference`` / ``PackagingLog`` (fjsp_packaging_scan) turn them into one
+record per tray run, the same 32-byte record with resource 4 + station.  Rules, per env and row,
+ln = the step within the episode, prev_s = station s's pack word and Hprev = the AGV's held word of
+the episode's previous row (0 at its first):
+  arrival     the AGV's result has drop_success and delivered_to_packaging (bits 4, 5) and pending +
+              completed of s rose against prev_s: a run with code Hprev & HELD_CODE_MASK joins the
+              tail of s's FIFO, ungranted (a drop whose products are lost raises no counter)
+  start       result bit 1 of agent 4 + s (started_packaging) grants every ungranted run of the
+              FIFO, the one that arrived in this row included, with start = ln
+  completion  runs(prev_s) + arrived - runs(now) runs leave the FIFO's head, finished, end = ln
+              (taken from the FIFO's own length, which is runs(prev_s) whenever the scan saw the
+              episode from its first row)
+  episode end after the completions every run left is written in FIFO order, unfinished: granted
+              runs keep their start and get end = -1, ungranted ones get start = end = -1
+``check_packaging`` checks the records, ``arrivals`` joins them to the AGV's drops (start - arrival
+is the wait in the station's queue), and ``gantt`` takes them as they are.
+
+Not covered: the pickup station's tray release times, the fused and training step paths,
+multi-GPU aggregation of the logs.
 """
 import ctypes
 
@@ -124,7 +146,9 @@ def gantt(ops, config=None):
     """The bars of a Gantt chart: {(env, episode_start, resource): dict of arrays} with the group's
     ops ordered by start and start_time / end_time = step * step_size beside the record's fields
     (end_time NaN for an unfinished op).  ops: ScheduleLog.pop()'s dict or an OP_DTYPE array;
-    config: an fjsp_config or anything with step_size (None = the default config)."""
+    config: an fjsp_config or anything with step_size (None = the default config).  It groups any
+    resource number, so PackagingLog.pop()'s dict (resources 4..7, one bar per tray run; an
+    ungranted run has start = -1) goes through unchanged."""
     d = _as_dict(ops)
     step_size = float(_cfg(config, "step_size"))
     keys = ("order", "first", "count", "start", "end", "finished", "from_loc", "to_loc")
@@ -163,6 +187,141 @@ def check(ops, config=None):
             if fin and res in pts and e - s != int(g["count"][i]) * pts[res]:
                 raise ValueError(f"{where}: lasts {e - s} steps, {int(g['count'][i])} products need "
                                  f"{int(g['count'][i]) * pts[res]}")
+
+
+# ---- packaging runs ---------------------------------------------------------------------------
+PACK_ROWS = 4                       # blue_1, blue_2, red, green = agents 4..7
+STATIONS = ("packaging_blue_1", "packaging_blue_2", "packaging_red", "packaging_green")   # resource = 4 + index
+RES_PACK_START, RES_AGV_TO_PACK = 1 << 1, 1 << 5
+INFO_GRANTED = 1 << 9
+LOC_PACKAGING = 5
+PACK_CARRY_WORDS, PACK_RING = 10, 256
+
+
+def pack_fields(word):
+    """(runs, pending, completed) of a pack word (array or int): the tray runs at the station, the
+    products queued + in flight, the products packaged this episode."""
+    w = np.asarray(word).astype(np.int64) & 0xFFFFFFFF
+    return w & 0xFF, (w >> 8) & 0xFFF, (w >> 20) & 0xFFF
+
+
+def _pack_fresh():
+    return {"ln": 0, "hprev": 0, "prev": [0] * PACK_ROWS, "fifo": [[] for _ in range(PACK_ROWS)]}
+
+
+def packaging_reference(results, held, pack, term, trunc, state=None, step0=0, env_gid0=0):
+    """The specification of fjsp_packaging_scan on the host, in plain Python ints.  results
+    [T, 8, N], held [T, 3, N], pack [T, 4, N] (any integer dtype), term / trunc [T, N]; state = what
+    an earlier call returned (None: fresh): per env the open episode's length, the previous row's
+    AGV held word and pack words and per station the FIFO of [code, granted, start].  Returns
+    (records, state): records an OP_DTYPE array in (t, env, station, FIFO position) order."""
+    term = np.asarray(term)
+    T, N = term.shape
+    trunc = np.asarray(trunc).reshape(T, N)
+    res = (np.asarray(results).astype(np.int64) & 0xFFFFFFFF).reshape(T, NA, N)
+    hld = (np.asarray(held).astype(np.int64) & 0xFFFFFFFF).reshape(T, HELD_ROWS, N)
+    pk = (np.asarray(pack).astype(np.int64) & 0xFFFFFFFF).reshape(T, PACK_ROWS, N)
+    state = [_pack_fresh() for _ in range(N)] if state is None else \
+        [{"ln": s["ln"], "hprev": s["hprev"], "prev": list(s["prev"]), "fifo": [[list(x) for x in f] for f in s["fifo"]]}
+         for s in state]
+    out = []
+    for e in range(N):
+        S = state[e]
+        for t in range(T):
+            end = bool(term[t, e]) or bool(trunc[t, e])
+            ln, agv = S["ln"], int(res[t, 1, e])
+            drop = agv & RES_AGV_DROP and agv & RES_AGV_TO_PACK
+            pos = 0
+
+            def write(s, run, fin):
+                nonlocal pos
+                code, granted, start = run
+                info = (4 + s) | (INFO_FINISHED if fin else 0) | (INFO_GRANTED if granted else 0) | \
+                    (LOC_PACKAGING << 16) | (LOC_PACKAGING << 20)
+                out.append((t, e, pos, (env_gid0 + e, info, step0 + t - ln, code, start if granted else -1,
+                                        ln if fin else -1, 0)))
+                pos += 1
+            for s in range(PACK_ROWS):
+                now, prev, fifo = int(pk[t, s, e]), S["prev"][s], S["fifo"][s]
+                rise = ((now >> 8) & 0xFFF) + (now >> 20) - ((prev >> 8) & 0xFFF) - (prev >> 20)
+                if drop and rise > 0:
+                    code = S["hprev"] & HELD_CODE_MASK
+                    assert rise == (code >> 10) & 7, (t, e, s, rise, code)   # the device does not check this
+                    fifo.append([code, 0, 0])
+                if int(res[t, 4 + s, e]) & RES_PACK_START:
+                    for run in fifo:
+                        if not run[1]:
+                            run[1], run[2] = 1, ln
+                for _ in range(max(0, len(fifo) - (now & 0xFF))):
+                    write(s, fifo.pop(0), True)
+                if end:
+                    while fifo:
+                        write(s, fifo.pop(0), False)
+                S["prev"][s] = 0 if end else now
+            S["hprev"] = 0 if end else int(hld[t, 0, e])
+            S["ln"] = 0 if end else ln + 1
+    out.sort(key=lambda x: x[:3])
+    recs = np.zeros(len(out), dtype=OP_DTYPE)
+    for k, x in enumerate(out):
+        recs[k] = x[3]
+    return recs, state
+
+
+def pack_records_dict(recs, dropped=0):
+    """OP_DTYPE array of packaging records -> the dict PackagingLog.pop() returns: records_dict's
+    fields plus station (0..3 = resource - 4) and granted."""
+    d = records_dict(recs, dropped)
+    d["station"] = d["resource"] - 4
+    d["granted"] = (recs["info"].astype(np.int64) & INFO_GRANTED) != 0
+    return d
+
+
+def _as_pack_dict(pack_ops):
+    return pack_ops if isinstance(pack_ops, dict) else pack_records_dict(np.asarray(pack_ops))
+
+
+def check_packaging(pack_ops, config=None):
+    """Raise ValueError unless every finished run lasts pt_packaging // step_size steps and, per
+    (env, episode, station) in record order, start and end do not decrease (the granted runs'
+    start, the finished runs' end) and no finished run follows an unfinished one."""
+    d = _as_pack_dict(pack_ops)
+    dur = _cfg(config, "pt_packaging") // _cfg(config, "step_size")
+    last = {}   # group -> [last start, last end, an unfinished run seen]
+    for i in range(len(d["env"])):
+        key = (int(d["env"][i]), int(d["episode_start"][i]), int(d["resource"][i]))
+        s, e, fin, granted = int(d["start"][i]), int(d["end"][i]), bool(d["finished"][i]), bool(d["granted"][i])
+        where = f"env {key[0]} episode_start {key[1]} resource {key[2]} record {i}"
+        g = last.setdefault(key, [-1, -1, False])
+        if fin and not granted:
+            raise ValueError(f"{where}: finished but never granted")
+        if fin and e - s != dur:
+            raise ValueError(f"{where}: lasts {e - s} steps, packaging takes {dur}")
+        if fin and g[2]:
+            raise ValueError(f"{where}: finished after an unfinished run of its station")
+        if granted:
+            if s < g[0]:
+                raise ValueError(f"{where}: starts at {s}, before the previous run's start {g[0]}")
+            g[0] = s
+        if fin:
+            if e < g[1]:
+                raise ValueError(f"{where}: ends at {e}, before the previous run's end {g[1]}")
+            g[1] = e
+        else:
+            g[2] = True
+
+
+def arrivals(ops, pack_ops):
+    """Per packaging record the step at which the AGV dropped that tray at packaging: the end of the
+    finished AGV record with the same (env, episode_start, tray) and to_loc == 5, -1 where the log
+    holds none.  start - arrival is the run's wait in the station's queue (a tray code is unique
+    within an episode)."""
+    a, p = _as_dict(ops), _as_pack_dict(pack_ops)
+    drops = {}
+    m = (a["resource"] == 1) & a["finished"] & (a["to_loc"] == LOC_PACKAGING)
+    for i in np.flatnonzero(m).tolist():
+        drops[(int(a["env"][i]), int(a["episode_start"][i]), int(a["records"]["tray"][i]))] = int(a["end"][i])
+    return np.array([drops.get((int(p["env"][i]), int(p["episode_start"][i]), int(p["records"]["tray"][i])), -1)
+                     for i in range(len(p["env"]))], dtype=np.int64)
 
 
 def carry_words():
@@ -262,5 +421,94 @@ class ScheduleLog:
         self.carry.masked_fill_(m[None, :], 0)
 
 
+class PackagingLog:
+    """Device-resident log of the packaging runs of num_envs envs (fjsp_packaging_scan): the carry
+    of the open episodes, the per-station FIFO rings (4 KB per env), a record buffer of `capacity`
+    fjsp_op_rec, the device-side record count and the running vector-step counter step0.  scan()
+    appends without synchronising; pop() copies the records to the host and empties the log."""
+
+    def __init__(self, num_envs, device, env_id_base=0, capacity=1 << 20):
+        import torch
+        self.N = int(num_envs)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise nat.FjspNativeError("PackagingLog needs a GPU (HIP); no CPU fallback exists")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.capacity = int(capacity)
+        self.env_id_base = int(env_id_base)
+        words = int(nat.lib().fjsp_packaging_carry_words())
+        assert words == PACK_CARRY_WORDS, (words, PACK_CARRY_WORDS)
+        n = ctypes.c_uint64()
+        nat.check(nat.lib().fjsp_packaging_ring_bytes(self.N, ctypes.byref(n)))
+        assert n.value == PACK_ROWS * PACK_RING * 4 * self.N
+        self.carry = torch.zeros(words, self.N, dtype=torch.int32, device=self.device)
+        self.ring = torch.zeros(PACK_ROWS, PACK_RING, self.N, dtype=torch.int32, device=self.device)
+        self.recs = torch.zeros(max(self.capacity, 1) * OP_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+        self.count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.step0 = 0
+        self._temp = None
+
+    def _temp_for(self, T):
+        import torch
+        n = ctypes.c_uint64()
+        nat.check(nat.lib().fjsp_packaging_temp_bytes(int(T), self.N, ctypes.byref(n)))
+        if self._temp is None or self._temp.numel() < n.value:
+            self._temp = torch.empty(int(n.value), dtype=torch.uint8, device=self.device)
+        return self._temp
+
+    def scan(self, results, held, pack, term, trunc):
+        """Compact the slab (contiguous device tensors: results int32 / uint32 [T, 8, N], held
+        [T, 3, N] and pack [T, 4, N] of the same dtypes, term / trunc u8 [T, N]) on the current
+        stream; advances step0 by T."""
+        import torch
+        T = int(term.shape[0])
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        for name, x, dts, shape in (("results", results, words, (T, NA, self.N)),
+                                    ("held", held, words, (T, HELD_ROWS, self.N)),
+                                    ("pack", pack, words, (T, PACK_ROWS, self.N)),
+                                    ("term", term, (torch.uint8,), (T, self.N)),
+                                    ("trunc", trunc, (torch.uint8,), (T, self.N))):
+            if x is None:
+                raise ValueError(f"{name} is required")
+            if tuple(x.shape) != shape or x.dtype not in dts:
+                raise ValueError(f"{name} must be {dts[0]} {list(shape)}")
+            if not x.is_contiguous() or x.device != self.device:
+                raise ValueError("PackagingLog.scan takes contiguous tensors on the log's device")
+        temp = self._temp_for(T)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            nat.check(nat.lib().fjsp_packaging_scan(
+                _ptr(results), _ptr(held), _ptr(pack), _ptr(term), _ptr(trunc), T, self.N, self.env_id_base,
+                self.step0, _ptr(self.carry), _ptr(self.ring), _ptr(self.recs), self.capacity, _ptr(self.count),
+                _ptr(temp), temp.numel(), ctypes.c_void_p(stream)))
+        self.step0 += T
+
+    def pop_records(self):
+        """(records, dropped) as ScheduleLog.pop_records: the bytes the kernel wrote, in the order
+        they were numbered.  Synchronises; empties the log, keeps the carry and the rings."""
+        count = int(self.count.item())
+        n = min(count, self.capacity)
+        recs = self.recs[:n * OP_DTYPE.itemsize].cpu().numpy().view(OP_DTYPE).copy()
+        self.count.zero_()
+        return recs, max(0, count - self.capacity)
+
+    def pop(self):
+        """Every packaging run logged since the last pop as a dict of numpy arrays: records_dict's
+        fields (resource = 4 + station, from_loc = to_loc = 5) plus station (0..3) and granted."""
+        return pack_records_dict(*self.pop_records())
+
+    def reset(self, env_mask=None):
+        """Zero the carry of the selected envs (all by default): after a manual env.reset.  An
+        all-zero carry empties the env's FIFOs, so the rings need no clearing."""
+        import torch
+        if env_mask is None:
+            self.carry.zero_()
+            return
+        m = torch.as_tensor(env_mask, device=self.device).bool()
+        self.carry.masked_fill_(m[None, :], 0)
+
+
 __all__ = ["OP_DTYPE", "ScheduleLog", "schedule_reference", "gantt", "check", "records_dict", "tray_fields",
-           "CARRY_WORDS", "carry_words", "temp_bytes"]
+           "CARRY_WORDS", "carry_words", "temp_bytes", "PACK_ROWS", "pack_fields", "packaging_reference",
+           "PackagingLog", "pack_records_dict", "check_packaging", "arrivals"]

@@ -23,10 +23,12 @@ def _ptr(t):
 class Buffers:
     """Output tensors for T steps of N envs (T = 1 for step/reset)."""
 
-    def __init__(self, T, N, device, infos=True, next_obs=False, feats=False, obs=True, held=False):
+    def __init__(self, T, N, device, infos=True, next_obs=False, feats=False, obs=True, held=False, pack=False):
         z = lambda *s, dt: torch.zeros(*s, dtype=dt, device=device)  # noqa: E731
         # held: the held-tray words int32 [T, 3, N] (fjsp_step_held; not part of fjsp_out)
         self.held = z(T, 3, N, dt=torch.int32) if held else None
+        # pack: the packaging stations' pack words int32 [T, 4, N] (fjsp_step_sched; not part of fjsp_out)
+        self.pack = z(T, 4, N, dt=torch.int32) if pack else None
         # feats: a2c global-state features f32 [T, 38, N] of the post-auto-reset observation
         self.feats = z(T, NFEAT, N, dt=torch.float32) if feats else None
         if not obs:   # a2c-only outputs: features, post-reset masks, rewards, term, trunc
@@ -171,12 +173,15 @@ class FJSPVecEnv:
                                          int(step), _ptr(out)))
         return out
 
-    def step(self, actions, agent_order=None, autoreset=True, buffers=None, held=None):
+    def step(self, actions, agent_order=None, autoreset=True, buffers=None, held=None, pack=None):
         """One FJSPSimulation.step per env (FJSPSimulation.py:144-242).
 
         actions: uint8 tensor [8, N] (agent-major) on the env's device.  held: an int32 / uint32
         [3, N] tensor (or a [1, 3, N] slab row) that receives the step's held-tray words
-        (fjsp_step_held, schedule.py); None: plain fjsp_step."""
+        (fjsp_step_held, schedule.py); None: plain fjsp_step.  pack (needs held): an int32 / uint32
+        [4, N] tensor that receives the packaging stations' pack words (fjsp_step_sched)."""
+        if pack is not None and held is None:
+            raise ValueError("pack needs held: fjsp_step_sched stores both")
         self._sync_stream()
         a = actions
         if a.dtype != torch.uint8 or not a.is_contiguous() or a.device != self.device:
@@ -195,6 +200,13 @@ class FJSPVecEnv:
             if held.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not held.is_contiguous() or \
                     held.device != self.device or held.numel() != 3 * self.num_envs:
                 raise ValueError(f"held must be a contiguous int32 [3, {self.num_envs}] tensor on the env's device")
+            if pack is not None:
+                if pack.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not pack.is_contiguous() or \
+                        pack.device != self.device or pack.numel() != 4 * self.num_envs:
+                    raise ValueError(f"pack must be a contiguous int32 [4, {self.num_envs}] tensor on the env's device")
+                nat.check(nat.lib().fjsp_step_sched(self._h, _ptr(a), order, int(bool(autoreset)), ctypes.byref(out),
+                                                    _ptr(held), _ptr(pack)))
+                return buffers
             nat.check(nat.lib().fjsp_step_held(self._h, _ptr(a), order, int(bool(autoreset)), ctypes.byref(out),
                                                _ptr(held)))
             return buffers
@@ -321,16 +333,19 @@ class FJSPVecEnv:
             done += k
         return {"episodes": log.pop(), "kpis": kpi.pop()}
 
-    def evaluate_schedule(self, policy="heuristic", num_orders=5, steps=500, seeds=None, action_seed=0, chunk=256):
+    def evaluate_schedule(self, policy="heuristic", num_orders=5, steps=500, seeds=None, action_seed=0, chunk=256,
+                          packaging=False):
         """evaluate_kpis with the per-operation schedule beside it: from a reset, per vector step
         the policy's actions (fjsp_actions) and one fjsp_step_held into row k of a chunk slab, each
         chunk scanned into an EpisodeLog, a kpis.KpiLog and a schedule.ScheduleLog.  The states and
         outputs are rollout()'s with the same seeds.  Returns {"episodes", "kpis", "ops"}; an op's
         (env, episode_start) is an episode record's (env, end_step - length).  Only the records
-        reach the host."""
+        reach the host.  packaging=True: the steps go through fjsp_step_sched, whose pack words feed a
+        schedule.PackagingLog with the same rows, and the result has "pack_ops" = its pop() (one
+        record per tray run at a packaging station; schedule.check_packaging, schedule.arrivals)."""
         from .episodes import EpisodeLog
         from .kpis import KpiLog
-        from .schedule import ScheduleLog
+        from .schedule import PackagingLog, ScheduleLog
         steps, chunk = int(steps), max(1, min(int(chunk), int(steps)))
         self.reset(seeds=seeds, num_orders=num_orders)
         cap = max(65536, self.num_envs * (steps // 16 + 1))   # as evaluate_episodes
@@ -339,7 +354,10 @@ class FJSPVecEnv:
         # an op takes at least one step per resource, an AGV op two (pickup, drop): 3 per 2 steps bounds it
         ops = ScheduleLog(self.num_envs, self.device, env_id_base=self.env_id_base,
                           capacity=max(65536, self.num_envs * (3 * steps // 2 + 3)))
-        b = Buffers(chunk, self.num_envs, self.device, infos=True, held=True)
+        # a packaging run needs an AGV carry before it: the same bound
+        pk = PackagingLog(self.num_envs, self.device, env_id_base=self.env_id_base,
+                          capacity=max(65536, self.num_envs * (steps // 2 + 1))) if packaging else None
+        b = Buffers(chunk, self.num_envs, self.device, infos=True, held=True, pack=bool(packaging))
         rows = [RowBuffers(b, k) for k in range(chunk)]
         act = torch.empty(NA, self.num_envs, dtype=torch.uint8, device=self.device)
         done = 0
@@ -347,13 +365,18 @@ class FJSPVecEnv:
             k = min(chunk, steps - done)
             for j in range(k):
                 self.actions(policy, action_seed=action_seed, step=done + j, out=act)
-                self.step(act, autoreset=True, buffers=rows[j], held=b.held[j])
+                self.step(act, autoreset=True, buffers=rows[j], held=b.held[j], pack=b.pack[j] if packaging else None)
             log.scan(b.rewards[:k], b.term[:k], b.trunc[:k], b.orders_completed[:k], b.packaged[:k])
             kpi.scan(b.results[:k], b.term[:k], b.trunc[:k], b.obs_i8[:k], b.orders_completed[:k], b.packaged[:k],
                      b.sim_time[:k])
             ops.scan(b.results[:k], b.held[:k], b.term[:k], b.trunc[:k])
+            if packaging:
+                pk.scan(b.results[:k], b.held[:k], b.pack[:k], b.term[:k], b.trunc[:k])
             done += k
-        return {"episodes": log.pop(), "kpis": kpi.pop(), "ops": ops.pop()}
+        out = {"episodes": log.pop(), "kpis": kpi.pop(), "ops": ops.pop()}
+        if packaging:
+            out["pack_ops"] = pk.pop()
+        return out
 
     def pack_a2c(self, feats=None, masks=None):
         """a2c features f32 [38, N] and masks int8 [29, N] of the current observations
