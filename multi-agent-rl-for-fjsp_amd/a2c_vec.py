@@ -1786,8 +1786,7 @@ class VecMultiAgentA2C:
         KPIs of the training rollouts themselves come from track_kpis=True (account_kpis /
         pop_kpis, learn()'s training_kpis): the collect then fills the same slabs for the batches
         the update trains on, and no separate rollout is needed."""
-        from .episodes import EpisodeLog
-        from .kpis import KpiLog
+        from .slablog import LogSet
         if packaging and not schedule:
             raise ValueError("packaging=True needs schedule=True: the pack words come with the held words")
         on_train = env is None or env is self.env
@@ -1811,19 +1810,11 @@ class VecMultiAgentA2C:
             o.feats = s["feats"][t + 1].data_ptr()
             outs.append(o)
         val = z(N, dt=torch.float32)
-        cap = max(65536, N * (steps // 16 + 1))
-        log = EpisodeLog(N, dev, env_id_base=env.env_id_base, capacity=cap)
-        kpi = KpiLog(N, dev, env_id_base=env.env_id_base, capacity=cap)
-        ops = None
+        logs = LogSet(env, steps, schedule=schedule, packaging=packaging, device=dev)
         if schedule:
-            from .schedule import ScheduleLog
             s["held"] = z(C, 3, N, dt=torch.int32)
-            ops = ScheduleLog(N, dev, env_id_base=env.env_id_base, capacity=max(65536, N * (3 * steps // 2 + 3)))
-        pk = None
         if packaging:
-            from .schedule import PackagingLog
             s["pack"] = z(C, 4, N, dt=torch.int32)
-            pk = PackagingLog(N, dev, env_id_base=env.env_id_base, capacity=max(65536, N * (steps // 2 + 1)))
         env.reset(seeds=seeds, num_orders=num_orders)
         env.pack_a2c(s["feats"][0], s["masks"][0])
         keep = {k: [] for k in s if k not in ("feats", "masks", "status")} if trace else None
@@ -1850,24 +1841,14 @@ class VecMultiAgentA2C:
                                                ctypes.byref(outs[t]), ctypes.c_void_p(s["held"][t].data_ptr())))
                 else:
                     nat.check(L.fjsp_step(h, ctypes.c_void_p(s["actions"][t].data_ptr()), None, 1, ctypes.byref(outs[t])))
-            log.scan(s["rewards"][:k], s["term"][:k], s["trunc"][:k], s["orders_completed"][:k], s["packaged"][:k])
-            kpi.scan(s["results"][:k], s["term"][:k], s["trunc"][:k], s["obs_i8"][:k], s["orders_completed"][:k],
-                     s["packaged"][:k], s["sim_time"][:k])
-            if schedule:
-                ops.scan(s["results"][:k], s["held"][:k], s["term"][:k], s["trunc"][:k])
-            if packaging:
-                pk.scan(s["results"][:k], s["held"][:k], s["pack"][:k], s["term"][:k], s["trunc"][:k])
+            logs.scan(s, k)
             if trace:
                 for name in keep:
                     keep[name].append(s[name][:k].cpu().numpy().copy())
             s["feats"][0].copy_(s["feats"][k])
             s["masks"][0].copy_(s["masks"][k])
             done += k
-        res = {"episodes": log.pop(), "kpis": kpi.pop()}
-        if schedule:
-            res["ops"] = ops.pop()
-        if packaging:
-            res["pack_ops"] = pk.pop()
+        res = logs.pop()
         if trace:
             import numpy as np
             res["trace"] = {name: np.concatenate(v) for name, v in keep.items()}

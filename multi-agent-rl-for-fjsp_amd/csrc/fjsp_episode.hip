@@ -1,24 +1,41 @@
-// fjsp_episode.hip — episode accounting over a rollout slab (include/fjsp.h: fjsp_episode_scan) and,
-// further down, the shop-floor KPIs of the same episodes (fjsp_kpi_scan) and the per-operation
-// schedules compacted from the held-tray words (fjsp_schedule_scan).
+// fjsp_episode.hip — the slab scans: four reductions of a [T][...][N] rollout slab to records in a
+// device-resident log (include/fjsp.h): episode returns (fjsp_episode_scan), the shop-floor KPIs of
+// the same episodes (fjsp_kpi_scan), the per-operation schedules compacted from the held-tray words
+// (fjsp_schedule_scan) and the packaging runs from the pack words (fjsp_packaging_scan).
 //
-// MultiAgentA2C.learn's per-episode bookkeeping (a2c.py:311-313 episode_rewards[agent] += reward,
-// :346-350 total = sum(episode_rewards.values()), episode_end_timesteps, :373 the printed steps)
-// for every env of a [T][8][N] slab, on the device.  Three launches, ordered by the stream only
-// (no flags, no waits between workgroups, no atomics):
+// The skeleton they share, described here once.  Three launches, ordered by the stream only (no
+// flags, no waits between workgroups, no atomics):
+//   count    per row t and wave w of 64 envs the number of records the row writes -> temp[t][w],
+//            u32 [T][W], W = ceil(N / 64).  The episode and KPI scans write one record per episode
+//            end and share k_episode_count; the schedule and packaging scans walk the slab once
+//            without writing (k_*_scan<false>)
+//   offsets  k_episode_offsets, one workgroup: temp <- its exclusive scan in (t, w) order (the
+//            row-major order a sequential reader of the slab meets the records in), the count at
+//            entry kept behind the table (`base`), *count advanced by the total
+//   write    one lane per env walks t forward; a record's rank is base + temp[t][w] + the records
+//            of the lower lanes in that row (a ballot's popcount or a wave prefix sum), and a rank
+//            at or past `cap` is counted but not written
+// The walk loads EP_U rows in one batch and issues the next batch before the current one is
+// consumed (as k_gae): chunk A holds t0.., B is loaded before A's rows are walked, and the other
+// way round.  Rows past the slab are clamped to its last row, loaded and never used, so no load
+// sits behind a branch.  What an env's open episode has accumulated so far is its carry, int32
+// words [WORDS][N] read at the start of a launch and written back at its end; the carry is what
+// lets a rollout be scanned chunk by chunk.  The host entries share one front (scan_front: the
+// argument checks, the temp layout, W / L / offs / base / flags) and one argument head (ScanHead).
+// The A / B loop and the carry's read and write lists are written out in each kernel: behind a
+// shared inlined helper (a walk taking load / rows callables, a carry visitor templated on STORE)
+// the compiler orders the kernels' instructions differently (profiles/scan_skeleton/README.md).
+//
+// Episode accounting: MultiAgentA2C.learn's per-episode bookkeeping (a2c.py:311-313
+// episode_rewards[agent] += reward, :346-350 total = sum(episode_rewards.values()),
+// episode_end_timesteps, :373 the printed steps) for every env of a [T][8][N] slab.
 //   k_episode_count    one wave per 64 envs x EP_U rows: per row the popcount of the ballot of
-//                      (term | trunc) -> temp[t][w], u32 [T][W], W = ceil(N / 64), and per env the
-//                      chunk's flags as one word (2 bits per row), u32 [ceil(T / EP_U)][64 W]
-//   k_episode_offsets  one workgroup: temp <- its exclusive scan in (t, w) order (the row-major
-//                      order a sequential reader of the slab meets the episode ends in), the
-//                      count at entry kept behind the table, *count advanced by the total
+//                      (term | trunc) -> temp[t][w], and per env the chunk's flags as one word
+//                      (2 bits per row), u32 [ceil(T / EP_U)][64 W]
 //   k_episode_scan     one workgroup of 8 waves per 64 envs, wave a = agent a's running sum of the
-//                      64 envs (one lane per env), forward over t with the loads of EP_U rows in one
-//                      batch and the next batch issued before the scan (as k_gae).  Every wave reads
-//                      the same flag words, so every wave derives the same rank temp[t][w] +
-//                      popc(ballot & lanes below) of an episode end by itself; wave a stores
-//                      by_agent[a].  Only
-//                      `total` needs the eight sums in one place: they go through LDS, one barrier
+//                      64 envs.  Every wave reads the same flag words, so every wave derives the same
+//                      rank of an episode end by itself; wave a stores by_agent[a].  Only `total`
+//                      needs the eight sums in one place: they go through LDS, one barrier
 //                      pair per EP_U rows (unconditional: every wave runs the same T loop), and wave
 //                      j % 8 writes the record head of row j's ends (three 16-byte stores).
 // The arithmetic is one fp64 add per (step, agent) and the left-to-right sum of the eight, in the
@@ -26,6 +43,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "../../include/fjsp.h"
 
@@ -42,6 +60,15 @@ constexpr int EPO_THREADS = 1024;
 __device__ __forceinline__ int lanes_below(uint64_t ballot, int lane) {
     return __popcll(ballot & ((1ull << lane) - 1ull));
 }
+
+// What every scan's arguments end with (the last member of each *Args, so that the pointers in
+// front keep their kernarg offsets): the log's capacity, the count at entry (read from temp by the
+// write kernel), the slab's first vector step, its first env's global id and its shape.
+struct ScanHead {
+    long long cap, base, step0;
+    uint32_t gid0;
+    int T, N;
+};
 
 __global__ void __launch_bounds__(256) k_episode_count(const uint8_t* __restrict__ term,
                                                        const uint8_t* __restrict__ trunc, int T, int N, int W,
@@ -141,9 +168,7 @@ struct EpArgs {
     const int32_t* oc;
     const int32_t* pk;
     fjsp_episode_rec* recs;
-    long long cap, base, step0;
-    uint32_t gid0;
-    int T, N;
+    ScanHead h;
 };
 
 // Rows t0 .. t0 + EP_U - 1 of one agent's 64 envs; sh[j][a][lane] = the agent's sum at an end in
@@ -157,10 +182,10 @@ __device__ __forceinline__ void ep_scan(const EpChunk& c, const uint32_t* __rest
     for (int j = 0; j < EP_U; j++) {
         const bool done = ((c.f >> (2 * j)) & 3u) != 0;   // never set past the slab
         const uint64_t b = __ballot(done);
-        if (t0 + j < p.T) acc = acc + c.r[j];             // wave-uniform
+        if (t0 + j < p.h.T) acc = acc + c.r[j];             // wave-uniform
         if (done) {
-            const long long seq = p.base + (long long)c.off[j] + lanes_below(b, lane);
-            if ((unsigned long long)seq < (unsigned long long)p.cap) p.recs[seq].by_agent[a] = acc;
+            const long long seq = p.h.base + (long long)c.off[j] + lanes_below(b, lane);
+            if ((unsigned long long)seq < (unsigned long long)p.h.cap) p.recs[seq].by_agent[a] = acc;
             sh[j][a][lane] = acc;
             acc = 0.0;
         }
@@ -172,18 +197,18 @@ __device__ __forceinline__ void ep_scan(const EpChunk& c, const uint32_t* __rest
         const uint64_t b = __ballot(fj != 0);
         if (fj != 0) {
             const size_t t = (size_t)(t0 + j);
-            const long long seq = p.base + (long long)offs[t * W + w] + lanes_below(b, lane);
-            if ((unsigned long long)seq < (unsigned long long)p.cap) {
+            const long long seq = p.h.base + (long long)offs[t * W + w] + lanes_below(b, lane);
+            if ((unsigned long long)seq < (unsigned long long)p.h.cap) {
                 double total = 0.0;
 #pragma unroll
                 for (int k = 0; k < EP_A; k++) total = total + sh[j][k][lane];
                 const uint32_t prior = c.f & ((1u << (2 * j)) - 1u);
                 const int length = prior ? j - ((31 - __clz(prior)) >> 1) : len + j + 1;
-                const size_t at = t * p.N + e;
+                const size_t at = t * p.h.N + e;
                 const int oc = p.oc ? p.oc[at] : -1, pk = p.pk ? p.pk[at] : -1;
-                const long long end = p.step0 + (long long)t + 1;
+                const long long end = p.h.step0 + (long long)t + 1;
                 uint4* q = reinterpret_cast<uint4*>(p.recs + seq);
-                q[0] = make_uint4(p.gid0 + (uint32_t)e, (uint32_t)length, (uint32_t)end,
+                q[0] = make_uint4(p.h.gid0 + (uint32_t)e, (uint32_t)length, (uint32_t)end,
                                   (uint32_t)((unsigned long long)end >> 32));
                 q[1] = make_uint4((uint32_t)seq, (uint32_t)((unsigned long long)seq >> 32), fj, (uint32_t)oc);
                 const unsigned long long tb = (unsigned long long)__double_as_longlong(total);
@@ -191,7 +216,7 @@ __device__ __forceinline__ void ep_scan(const EpChunk& c, const uint32_t* __rest
             }
         }
     }
-    const int rows = min(EP_U, p.T - t0);
+    const int rows = min(EP_U, p.h.T - t0);
     len = c.f ? rows - 1 - ((31 - __clz(c.f)) >> 1) : len + rows;
     __syncthreads();
 }
@@ -204,7 +229,7 @@ __device__ __forceinline__ void ep_body(const double* __restrict__ r, const uint
     const int lane = threadIdx.x & 63;
     const int a = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int w = blockIdx.x, e = w * 64 + lane;
-    const int T = p.T, N = p.N;
+    const int T = p.h.T, N = p.h.N;
     const bool live = !GUARD || e < N;
     double acc = 0.0;
     int len = 0;
@@ -215,7 +240,7 @@ __device__ __forceinline__ void ep_body(const double* __restrict__ r, const uint
     EpChunk A, B;
     int t0 = 0;
     ep_load<GUARD>(A, r, flags, offs, 0, T, N, W, a, e, w, live);
-    for (;;) {   // A holds t0.., B is loaded before A's scan, and the other way round
+    for (;;) {   // the A / B walk, written out: a shared helper changes the kernel's code (file header)
         ep_load<GUARD>(B, r, flags, offs, t0 + EP_U, T, N, W, a, e, w, live);
         ep_scan(A, offs, t0, p, W, a, w, e, lane, acc, len, sh);
         t0 += EP_U;
@@ -238,15 +263,14 @@ __global__ void __launch_bounds__(64 * EP_A) k_episode_scan(const double* __rest
                                                             double* __restrict__ accp,
                                                             int32_t* __restrict__ lenp) {
     __shared__ double sh[EP_U][EP_A][64];
-    p.base = base[0];
-    if ((int)blockIdx.x * 64 + 64 <= p.N) ep_body<false>(r, flags, offs, p, W, accp, lenp, sh);
+    p.h.base = base[0];
+    if ((int)blockIdx.x * 64 + 64 <= p.h.N) ep_body<false>(r, flags, offs, p, W, accp, lenp, sh);
     else ep_body<true>(r, flags, offs, p, W, accp, lenp, sh);
 }
 
 // ---- shop-floor KPIs (include/fjsp.h: fjsp_kpi_scan) -------------------------------------------
 // The same three launches with k_kpi_scan in k_episode_scan's place: one workgroup of 8 waves per
-// 64 envs, wave a = agent a's eight result counters of the 64 envs (one lane per env), forward
-// over t, EP_U rows per load batch with the next batch issued before the scan.  Waves 0 and 1 also
+// 64 envs, wave a = agent a's eight result counters of the 64 envs.  Waves 0 and 1 also
 // follow one infos counter each (orders_completed / packaged -> the completion-time blocks); wave 0
 // writes the record's first 32 bytes (up to orders_completed), wave 1, which holds packaged, the
 // next 16 (packaged, reserved, makespan: it also batches sim_time); waves 2..7 read their station's
@@ -281,9 +305,7 @@ struct KpiArgs {
     const double* st;
     fjsp_kpi_rec* recs;
     int32_t* carry;
-    long long cap, base, step0;
-    uint32_t gid0;
-    int T, N;
+    ScanHead h;
 };
 
 struct KpiChunk {
@@ -344,7 +366,7 @@ __device__ __forceinline__ void kpi_load(KpiChunk& c, const KpiRows& r, const ui
 template <int ROLE>
 __device__ __forceinline__ void kpi_scan(const KpiChunk& c, int t0, const KpiArgs& p, int a, int e, int lane,
                                          KpiState& s) {
-    const int rows = min(EP_U, p.T - t0);
+    const int rows = min(EP_U, p.h.T - t0);
 #pragma unroll
     for (int j = 0; j < EP_U; j++) {
         if (j < rows) {   // wave-uniform
@@ -371,8 +393,8 @@ __device__ __forceinline__ void kpi_scan(const KpiChunk& c, int t0, const KpiArg
         const uint32_t fj = (c.f >> (2 * j)) & 3u;   // never set past the slab
         const uint64_t b = __ballot(fj != 0);
         if (fj != 0) {
-            const long long seq = p.base + (long long)c.off[j] + lanes_below(b, lane);
-            if ((unsigned long long)seq < (unsigned long long)p.cap) {
+            const long long seq = p.h.base + (long long)c.off[j] + lanes_below(b, lane);
+            if ((unsigned long long)seq < (unsigned long long)p.h.cap) {
                 uint4* q = reinterpret_cast<uint4*>(p.recs + seq);
                 if (ROLE != 2) {
                     // the 48 bytes in front: wave 0 the 32 that end with orders_completed, wave 1 the 16
@@ -380,8 +402,8 @@ __device__ __forceinline__ void kpi_scan(const KpiChunk& c, int t0, const KpiArg
                     // have to wait for the whole batch in flight behind it)
                     if (ROLE == 0) {
                         const int oc = p.oc ? c.x[j] : -1;
-                        const long long end = p.step0 + (long long)(t0 + j) + 1;
-                        q[0] = make_uint4(p.gid0 + (uint32_t)e, (uint32_t)s.len, (uint32_t)end,
+                        const long long end = p.h.step0 + (long long)(t0 + j) + 1;
+                        q[0] = make_uint4(p.h.gid0 + (uint32_t)e, (uint32_t)s.len, (uint32_t)end,
                                           (uint32_t)((unsigned long long)end >> 32));
                         q[1] = make_uint4((uint32_t)seq, (uint32_t)((unsigned long long)seq >> 32), fj, (uint32_t)oc);
                     } else {
@@ -408,12 +430,12 @@ __device__ __forceinline__ void kpi_body(const uint32_t* __restrict__ flags, con
                                          const KpiArgs& p, int W, int w, int a) {
     const int lane = threadIdx.x & 63;
     const int e = w * 64 + lane;
-    const int T = p.T;
-    const size_t N = (size_t)p.N, col = (size_t)w * 64;
-    const bool live = e < p.N;
+    const int T = p.h.T;
+    const size_t N = (size_t)p.h.N, col = (size_t)w * 64;
+    const bool live = e < p.h.N;
     // lanes e >= N load their workgroup's last env's column; their flag words are 0 (temp's padded
     // rows), so they end no episode, and their carry is neither read nor written
-    const uint32_t ll = (uint32_t)min(lane, p.N - w * 64 - 1);
+    const uint32_t ll = (uint32_t)min(lane, p.h.N - w * 64 - 1);
     const char* none = reinterpret_cast<const char*>(flags);
     const int32_t* info = ROLE == 0 ? p.oc : p.pk;
     KpiRows r;
@@ -461,7 +483,7 @@ __device__ __forceinline__ void kpi_body(const uint32_t* __restrict__ flags, con
     KpiChunk A, B;
     int t0 = 0;
     kpi_load<ROLE>(A, r, flags, offs, 0, T, W, (uint32_t)e, w);
-    for (;;) {   // A holds t0.., B is loaded before A's scan, and the other way round
+    for (;;) {   // the A / B walk, written out: a shared helper changes the kernel's code (file header)
         kpi_load<ROLE>(B, r, flags, offs, t0 + EP_U, T, W, (uint32_t)e, w);
         kpi_scan<ROLE>(A, t0, p, a, e, lane, s);
         t0 += EP_U;
@@ -471,7 +493,7 @@ __device__ __forceinline__ void kpi_body(const uint32_t* __restrict__ flags, con
         t0 += EP_U;
         if (t0 >= T) break;
     }
-    if (live) {
+    if (live) {   // the read list's mirror, written out: a STORE-templated visitor changes the kernel's code
         if (ROLE != 2) cy[(size_t)cl * N] = s.len;
 #pragma unroll
         for (int k = 0; k < 8; k++) cy[(size_t)(ca + k) * N] = (int32_t)s.c[k];
@@ -492,7 +514,7 @@ __device__ __forceinline__ void kpi_body(const uint32_t* __restrict__ flags, con
 __global__ void __launch_bounds__(64 * EP_A) k_kpi_scan(const uint32_t* __restrict__ flags,
                                                         const uint32_t* __restrict__ offs,
                                                         const long long* __restrict__ base, KpiArgs p, int W) {
-    p.base = base[0];
+    p.h.base = base[0];
     const int w = (int)blockIdx.x;
     const int a = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (a == 0) kpi_body<0>(flags, offs, p, W, w, a);
@@ -500,22 +522,11 @@ __global__ void __launch_bounds__(64 * EP_A) k_kpi_scan(const uint32_t* __restri
     else kpi_body<2>(flags, offs, p, W, w, a);
 }
 
-// temp: the offsets table u32 [T][W] (padded to 16 bytes), 16 bytes for the count at entry, the
-// flag words u32 [ceil(T / EP_U)][64 W]
-bool ep_temp_layout(int32_t T, int32_t N, uint64_t* table, uint64_t* total) {
-    const int64_t W = ((int64_t)N + 63) / 64, L = (int64_t)T * W;
-    if (L * 64 > INT32_MAX) return false;
-    *table = ((uint64_t)L * 4 + 15) & ~(uint64_t)15;
-    *total = *table + 16 + (uint64_t)((T + EP_U - 1) / EP_U) * (uint64_t)W * 64 * 4;
-    return true;
-}
-
 // ---- per-operation schedules (include/fjsp.h: fjsp_schedule_scan) ------------------------------
 // How many records a row writes depends on the ops open at that row, so the walk runs twice with
 // k_episode_offsets between: k_schedule_scan<false> counts, k_schedule_scan<true> writes.  Both are
-// one wave per 64 envs (one lane per env) walking t forward, EP_U rows per load batch with the next
-// batch issued before the current one is consumed (as k_kpi_scan): per row and env the three result
-// words of agents 1..3, the three held-tray words and the two flags, 26 bytes.
+// one wave per 64 envs; per row and env they load the three result words of agents 1..3, the three
+// held-tray words and the two flags, 26 bytes.
 //   count  per row the three ballots of "resource r writes a record" -> cnt[t][w] = their popcounts'
 //          sum (lane 0); the carry is read, never written
 //   write  the same walk; a record's rank is offs[t][w] + the records of the lower lanes in the
@@ -539,9 +550,7 @@ struct SchedArgs {
     const uint8_t* trunc;
     fjsp_op_rec* recs;
     int32_t* carry;
-    long long cap, base, step0;
-    uint32_t gid0;
-    int T, N;
+    ScanHead h;
 };
 
 struct SchedChunk {
@@ -555,10 +564,10 @@ struct SchedChunk {
 template <bool WRITE>
 __device__ __forceinline__ void sched_load(SchedChunk& c, const SchedArgs& p, const uint32_t* __restrict__ offs, int t0,
                                            int W, int w, uint32_t col) {
-    const size_t N = (size_t)p.N;
+    const size_t N = (size_t)p.h.N;
 #pragma unroll
     for (int j = 0; j < EP_U; j++) {
-        const size_t t = (size_t)(t0 + j < p.T ? t0 + j : p.T - 1);
+        const size_t t = (size_t)(t0 + j < p.h.T ? t0 + j : p.h.T - 1);
         const uint32_t* __restrict__ rr = p.res + (t * EP_A + 1) * N;
         const uint32_t* __restrict__ hr = p.held + t * SC_R * N;
 #pragma unroll
@@ -581,7 +590,7 @@ struct SchedState {
 template <bool WRITE>
 __device__ __forceinline__ void sched_rows(const SchedChunk& c, int t0, const SchedArgs& p, uint32_t* __restrict__ cnt,
                                            int W, int w, int e, int lane, bool live, SchedState& s) {
-    const int rows = min(EP_U, p.T - t0);
+    const int rows = min(EP_U, p.h.T - t0);
 #pragma unroll
     for (int j = 0; j < EP_U; j++) {
         if (j < rows) {   // wave-uniform
@@ -617,15 +626,15 @@ __device__ __forceinline__ void sched_rows(const SchedChunk& c, int t0, const Sc
             if (!WRITE) {
                 if (lane == 0) cnt[(size_t)(t0 + j) * W + w] = (uint32_t)(__popcll(b[0]) + __popcll(b[1]) + __popcll(b[2]));
             } else {
-                long long rank = p.base + (long long)c.off[j] + lanes_below(b[0], lane) + lanes_below(b[1], lane) +
+                long long rank = p.h.base + (long long)c.off[j] + lanes_below(b[0], lane) + lanes_below(b[1], lane) +
                                  lanes_below(b[2], lane);
-                const long long es = p.step0 + (long long)(t0 + j) - (long long)s.len;
+                const long long es = p.h.step0 + (long long)(t0 + j) - (long long)s.len;
     #pragma unroll
                 for (int r = 0; r < SC_R; r++) {
                     if (emit[r]) {
-                        if ((unsigned long long)rank < (unsigned long long)p.cap) {
+                        if ((unsigned long long)rank < (unsigned long long)p.h.cap) {
                             uint4* q = reinterpret_cast<uint4*>(p.recs + rank);
-                            q[0] = make_uint4(p.gid0 + (uint32_t)e, info[r], (uint32_t)es, (uint32_t)((unsigned long long)es >> 32));
+                            q[0] = make_uint4(p.h.gid0 + (uint32_t)e, info[r], (uint32_t)es, (uint32_t)((unsigned long long)es >> 32));
                             q[1] = make_uint4(tray[r], (uint32_t)st[r], (uint32_t)en[r], 0u);
                         }
                         rank += 1;
@@ -640,12 +649,12 @@ __device__ __forceinline__ void sched_rows(const SchedChunk& c, int t0, const Sc
 template <bool WRITE>
 __global__ void __launch_bounds__(64) k_schedule_scan(SchedArgs p, uint32_t* __restrict__ cnt,
                                                       const long long* __restrict__ base, int W) {
-    if (WRITE) p.base = base[0];
+    if (WRITE) p.h.base = base[0];
     const int lane = threadIdx.x, w = (int)blockIdx.x;
     const int e = w * 64 + lane;
-    const bool live = e < p.N;
-    const uint32_t col = (uint32_t)min(e, p.N - 1);
-    const size_t N = (size_t)p.N;
+    const bool live = e < p.h.N;
+    const uint32_t col = (uint32_t)min(e, p.h.N - 1);
+    const size_t N = (size_t)p.h.N;
     int32_t* __restrict__ cy = p.carry + col;   // word k of this env: cy[k * N]
     SchedState s{};
     s.len = cy[(size_t)SC_LEN * N];
@@ -657,17 +666,17 @@ __global__ void __launch_bounds__(64) k_schedule_scan(SchedArgs p, uint32_t* __r
     SchedChunk A, B;
     int t0 = 0;
     sched_load<WRITE>(A, p, cnt, 0, W, w, col);
-    for (;;) {   // A holds t0.., B is loaded before A's rows are walked, and the other way round
+    for (;;) {   // the A / B walk, written out: a shared helper changes the kernel's code (file header)
         sched_load<WRITE>(B, p, cnt, t0 + EP_U, W, w, col);
         sched_rows<WRITE>(A, t0, p, cnt, W, w, e, lane, live, s);
         t0 += EP_U;
-        if (t0 >= p.T) break;
+        if (t0 >= p.h.T) break;
         sched_load<WRITE>(A, p, cnt, t0 + EP_U, W, w, col);
         sched_rows<WRITE>(B, t0, p, cnt, W, w, e, lane, live, s);
         t0 += EP_U;
-        if (t0 >= p.T) break;
+        if (t0 >= p.h.T) break;
     }
-    if (WRITE && live) {
+    if (WRITE && live) {   // the read list's mirror, written out: a STORE-templated visitor changes the kernel's code
         cy[(size_t)SC_LEN * N] = s.len;
 #pragma unroll
         for (int r = 0; r < SC_R; r++) {
@@ -677,24 +686,13 @@ __global__ void __launch_bounds__(64) k_schedule_scan(SchedArgs p, uint32_t* __r
     }
 }
 
-// temp: the counts / offsets table u32 [T][W] (padded to 16 bytes), then 16 bytes for the count at
-// entry.  Up to three records per env and row: T W 64 <= 2^30 keeps the sums in 32 bits.
-bool sched_temp_layout(int32_t T, int32_t N, uint64_t* table, uint64_t* total) {
-    const int64_t W = ((int64_t)N + 63) / 64, L = (int64_t)T * W;
-    if (L * 64 > (int64_t)1 << 30) return false;
-    *table = ((uint64_t)L * 4 + 15) & ~(uint64_t)15;
-    *total = *table + 16;
-    return true;
-}
-
 // ---- packaging runs (include/fjsp.h: fjsp_packaging_scan) --------------------------------------
 // One record per tray run at a packaging station.  Per station the runs are FIFO (arrival order =
 // grant order = completion order), so the records a row writes follow from the pack words'
 // counters and the walk keeps k_schedule_scan's shape: k_packaging_scan<false> counts,
-// k_episode_offsets, k_packaging_scan<true> writes; one wave per 64 envs, one lane per env, EP_U
-// rows per load batch with the next batch issued before the current one is walked.  Per row and
-// env: the result words of the AGV and the four stations, the AGV's held word, the four pack words
-// and the two flags, 42 bytes.
+// k_episode_offsets, k_packaging_scan<true> writes; one wave per 64 envs.  Per row and env: the
+// result words of the AGV and the four stations, the AGV's held word, the four pack words and the
+// two flags, 42 bytes.
 //   count  a lane's records of a row = sum over s of the runs that left station s's FIFO, plus at
 //          an episode end the runs still in it; the lanes' sum -> cnt[t][w] (lane 0).  Needs the
 //          words and the carry only (never the rings), writes neither
@@ -726,9 +724,7 @@ struct PackArgs {
     fjsp_op_rec* recs;
     int32_t* carry;
     uint32_t* ring;
-    long long cap, base, step0;
-    uint32_t gid0;
-    int T, N;
+    ScanHead h;
 };
 
 template <bool WRITE>
@@ -742,10 +738,10 @@ struct PackChunk {
 template <bool WRITE>
 __device__ __forceinline__ void pack_load(PackChunk<WRITE>& c, const PackArgs& p, const uint32_t* __restrict__ offs, int t0,
                                           int W, int w, uint32_t col) {
-    const size_t N = (size_t)p.N;
+    const size_t N = (size_t)p.h.N;
 #pragma unroll
     for (int j = 0; j < EP_U; j++) {
-        const size_t t = (size_t)(t0 + j < p.T ? t0 + j : p.T - 1);
+        const size_t t = (size_t)(t0 + j < p.h.T ? t0 + j : p.h.T - 1);
         const uint32_t* __restrict__ rr = p.res + t * EP_A * N;
         const uint32_t* __restrict__ pr = p.pack + t * PK_S * N;
         c.agv[j] = rr[N + col];
@@ -772,8 +768,8 @@ __device__ __forceinline__ uint32_t pk_total(uint32_t w) { return ((w >> 8) & 0x
 template <bool WRITE>
 __device__ __forceinline__ void pack_rows(const PackChunk<WRITE>& c, int t0, const PackArgs& p, uint32_t* __restrict__ cnt,
                                           int W, int w, int e, int lane, bool live, PackState& s) {
-    const int rows = min(EP_U, p.T - t0);
-    const size_t N = (size_t)p.N;
+    const int rows = min(EP_U, p.h.T - t0);
+    const size_t N = (size_t)p.h.N;
     uint32_t* __restrict__ ring = p.ring + (live ? e : 0);   // entry i of station q: ring[(q * PK_RING + i) * N]
 #pragma unroll
     for (int j = 0; j < EP_U; j++) {
@@ -847,8 +843,8 @@ __device__ __forceinline__ void pack_rows(const PackChunk<WRITE>& c, int t0, con
                         const uint32_t o = __shfl_up(inc, d);
                         if (lane >= d) inc += o;
                     }
-                    long long rank = p.base + (long long)c.off[j] + (long long)(inc - n);
-                    const long long es = p.step0 + (long long)(t0 + j) - (long long)s.len;
+                    long long rank = p.h.base + (long long)c.off[j] + (long long)(inc - n);
+                    const long long es = p.h.step0 + (long long)(t0 + j) - (long long)s.len;
                     if (n != 0) {
 #pragma unroll
                         for (int q = 0; q < PK_S; q++) {
@@ -857,11 +853,11 @@ __device__ __forceinline__ void pack_rows(const PackChunk<WRITE>& c, int t0, con
                             for (uint32_t i = 0; i < m; i++) {
                                 const uint32_t en = ring[((size_t)q * PK_RING + h) * N];
                                 const bool fin = i < leave[q], granted = (en & PK_GRANTED) != 0;
-                                if ((unsigned long long)rank < (unsigned long long)p.cap) {
+                                if ((unsigned long long)rank < (unsigned long long)p.h.cap) {
                                     const uint32_t info = (uint32_t)(4 + q) | (fin ? 1u << 8 : 0u) | (granted ? 1u << 9 : 0u) |
                                                           5u << 16 | 5u << 20;
                                     uint4* o = reinterpret_cast<uint4*>(p.recs + rank);
-                                    o[0] = make_uint4(p.gid0 + (uint32_t)e, info, (uint32_t)es, (uint32_t)((unsigned long long)es >> 32));
+                                    o[0] = make_uint4(p.h.gid0 + (uint32_t)e, info, (uint32_t)es, (uint32_t)((unsigned long long)es >> 32));
                                     o[1] = make_uint4(en & FJSP_HELD_CODE_MASK, granted ? en >> 16 : ~0u, fin ? ln : ~0u, 0u);
                                 }
                                 rank += 1;
@@ -885,12 +881,12 @@ __device__ __forceinline__ void pack_rows(const PackChunk<WRITE>& c, int t0, con
 template <bool WRITE>
 __global__ void __launch_bounds__(64) k_packaging_scan(PackArgs p, uint32_t* __restrict__ cnt,
                                                        const long long* __restrict__ base, int W) {
-    if (WRITE) p.base = base[0];
+    if (WRITE) p.h.base = base[0];
     const int lane = threadIdx.x, w = (int)blockIdx.x;
     const int e = w * 64 + lane;
-    const bool live = e < p.N;
-    const uint32_t col = (uint32_t)min(e, p.N - 1);
-    const size_t N = (size_t)p.N;
+    const bool live = e < p.h.N;
+    const uint32_t col = (uint32_t)min(e, p.h.N - 1);
+    const size_t N = (size_t)p.h.N;
     int32_t* __restrict__ cy = p.carry + col;   // word k of this env: cy[k * N]
     PackState s{};
     s.len = cy[(size_t)PK_LEN * N];
@@ -903,17 +899,17 @@ __global__ void __launch_bounds__(64) k_packaging_scan(PackArgs p, uint32_t* __r
     PackChunk<WRITE> A, B;
     int t0 = 0;
     pack_load<WRITE>(A, p, cnt, 0, W, w, col);
-    for (;;) {   // A holds t0.., B is loaded before A's rows are walked, and the other way round
+    for (;;) {   // the A / B walk, written out: a shared helper changes the kernel's code (file header)
         pack_load<WRITE>(B, p, cnt, t0 + EP_U, W, w, col);
         pack_rows<WRITE>(A, t0, p, cnt, W, w, e, lane, live, s);
         t0 += EP_U;
-        if (t0 >= p.T) break;
+        if (t0 >= p.h.T) break;
         pack_load<WRITE>(A, p, cnt, t0 + EP_U, W, w, col);
         pack_rows<WRITE>(B, t0, p, cnt, W, w, e, lane, live, s);
         t0 += EP_U;
-        if (t0 >= p.T) break;
+        if (t0 >= p.h.T) break;
     }
-    if (WRITE && live) {
+    if (WRITE && live) {   // the read list's mirror, written out: a STORE-templated visitor changes the kernel's code
         cy[(size_t)PK_LEN * N] = s.len;
         cy[(size_t)PK_HPREV * N] = (int32_t)s.hprev;
 #pragma unroll
@@ -924,60 +920,117 @@ __global__ void __launch_bounds__(64) k_packaging_scan(PackArgs p, uint32_t* __r
     }
 }
 
-}  // namespace
+// ---- the host front the four entries share ------------------------------------------------------
+// temp: the counts / offsets table u32 [T][W] (padded to 16 bytes), 16 bytes for the count at entry
+// and, for the scans that k_episode_count feeds, the flag words u32 [ceil(T / EP_U)][64 W].  The
+// slab's T W 64 positions may not exceed `limit`, which keeps the table's sums in 32 bits.
+struct ScanKind {
+    int64_t limit;
+    bool with_flags;
+    const char* bound;
+};
+constexpr ScanKind EPISODES = {INT32_MAX, true, "T * N must be < 2^31"};   // one record per env and row at most
+// up to three ops per env and row; at most one packaging arrival per env and row, and 255 runs per
+// env carried in
+constexpr ScanKind OPS = {(int64_t)1 << 30, false, "T * N must be < 2^30"};
 
-extern "C" {
+bool temp_layout(int32_t T, int32_t N, int64_t limit, bool with_flags, uint64_t* table, uint64_t* total) {
+    const int64_t W = ((int64_t)N + 63) / 64, L = (int64_t)T * W;
+    if (L * 64 > limit) return false;
+    *table = ((uint64_t)L * 4 + 15) & ~(uint64_t)15;
+    *total = *table + 16 + (with_flags ? (uint64_t)((T + EP_U - 1) / EP_U) * (uint64_t)W * 64 * 4 : 0);
+    return true;
+}
 
-int fjsp_episode_temp_bytes(int32_t T, int32_t N, uint64_t* bytes) {
-    if (T <= 0 || N <= 0) return fjsp_internal_fail("fjsp_episode_temp_bytes: T and N must be > 0");
-    if (!bytes) return fjsp_internal_fail("fjsp_episode_temp_bytes: null pointer");
-    uint64_t table, total;
-    if (!ep_temp_layout(T, N, &table, &total)) return fjsp_internal_fail("fjsp_episode_temp_bytes: T * N must be < 2^31");
-    *bytes = total;
+int scan_fail(const char* entry, const char* what) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: %s", entry, what);
+    return fjsp_internal_fail(msg);   // copies the text
+}
+
+int scan_temp_bytes(const char* entry, const ScanKind& kind, int32_t T, int32_t N, uint64_t* bytes) {
+    if (T <= 0 || N <= 0) return scan_fail(entry, "T and N must be > 0");
+    if (!bytes) return scan_fail(entry, "null pointer");
+    uint64_t table;
+    if (!temp_layout(T, N, kind.limit, kind.with_flags, &table, bytes)) return scan_fail(entry, kind.bound);
     return 0;
 }
 
-int fjsp_episode_scan(const double* rewards, const uint8_t* term, const uint8_t* trunc, const int32_t* orders_completed,
-                      const int32_t* packaged, int32_t T, int32_t N, uint32_t env_gid0, int64_t step0, double* acc,
-                      int32_t* len, fjsp_episode_rec* recs, int64_t cap, int64_t* count, void* temp, uint64_t temp_bytes,
-                      void* stream) {
-    if (T <= 0 || N <= 0) return fjsp_internal_fail("fjsp_episode_scan: T and N must be > 0");
-    if (cap < 0) return fjsp_internal_fail("fjsp_episode_scan: cap must be >= 0");
-    if (!rewards || !term || !trunc || !acc || !len || !count || !temp || (cap > 0 && !recs))
-        return fjsp_internal_fail("fjsp_episode_scan: null buffer");
+struct ScanFront {
+    int W, L;          // waves of 64 envs per row, T W
+    uint32_t* offs;    // the counts / offsets table
+    long long* base;   // the count at entry
+    uint32_t* flags;   // k_episode_count's flag words (null for OPS)
+    hipStream_t st;
+};
+
+// The checks every scan entry makes, in the order a bad call's first error is reported in, and the
+// views into temp.  null_slab: one of the entry's own required pointers is null.
+int scan_front(const char* entry, const ScanKind& kind, int32_t T, int32_t N, int64_t cap, bool null_slab,
+               const void* recs, const void* count, void* temp, uint64_t temp_bytes, void* stream, ScanFront* f) {
+    if (T <= 0 || N <= 0) return scan_fail(entry, "T and N must be > 0");
+    if (cap < 0) return scan_fail(entry, "cap must be >= 0");
+    if (null_slab || !count || !temp || (cap > 0 && !recs)) return scan_fail(entry, "null buffer");
     uint64_t table, total;
-    if (!ep_temp_layout(T, N, &table, &total)) return fjsp_internal_fail("fjsp_episode_scan: T * N must be < 2^31");
-    if (temp_bytes < total) return fjsp_internal_fail("fjsp_episode_scan: temp buffer too small");
-    if ((((uintptr_t)recs | (uintptr_t)temp) & 15u) != 0)
-        return fjsp_internal_fail("fjsp_episode_scan: recs and temp must be 16-byte aligned");
-    const int W = (int)(((int64_t)N + 63) / 64);   // T W 64 < 2^31 (checked above)
-    const int L = T * W;
-    uint32_t* offs = (uint32_t*)temp;
-    long long* base = (long long*)((char*)temp + table);
-    uint32_t* flags = (uint32_t*)((char*)temp + table + 16);
-    const hipStream_t st = (hipStream_t)stream;
-    const long long waves = (long long)W * ((T + EP_U - 1) / EP_U);
-    hipLaunchKernelGGL(k_episode_count, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, term, trunc, T, N, W, offs,
-                       flags);
-    hipLaunchKernelGGL(k_episode_offsets, dim3(1), dim3(EPO_THREADS), 0, st, offs, L, base, (long long*)count);
-    EpArgs p;
-    p.oc = orders_completed;
-    p.pk = packaged;
-    p.recs = recs;
-    p.cap = cap;
-    p.base = 0;
-    p.step0 = step0;
-    p.gid0 = env_gid0;
-    p.T = T;
-    p.N = N;
-    hipLaunchKernelGGL(k_episode_scan, dim3((unsigned)W), dim3(64 * EP_A), 0, st, rewards, flags, offs, base, p, W,
-                       acc, len);
+    if (!temp_layout(T, N, kind.limit, kind.with_flags, &table, &total)) return scan_fail(entry, kind.bound);
+    if (temp_bytes < total) return scan_fail(entry, "temp buffer too small");
+    if ((((uintptr_t)recs | (uintptr_t)temp) & 15u) != 0) return scan_fail(entry, "recs and temp must be 16-byte aligned");
+    f->W = (int)(((int64_t)N + 63) / 64);   // T W 64 < 2^31 (checked above)
+    f->L = T * f->W;
+    f->offs = (uint32_t*)temp;
+    f->base = (long long*)((char*)temp + table);
+    f->flags = kind.with_flags ? (uint32_t*)((char*)temp + table + 16) : nullptr;
+    f->st = (hipStream_t)stream;
+    return 0;
+}
+
+ScanHead scan_head(int64_t cap, int64_t step0, uint32_t gid0, int32_t T, int32_t N) {
+    return ScanHead{cap, 0, step0, gid0, T, N};   // base: the write kernel reads it from temp
+}
+
+void launch_offsets(const ScanFront& f, int64_t* count) {
+    hipLaunchKernelGGL(k_episode_offsets, dim3(1), dim3(EPO_THREADS), 0, f.st, f.offs, f.L, f.base, (long long*)count);
+}
+
+// The count and offsets launches of the scans that write one record per episode end.
+void launch_episode_count(const ScanFront& f, const uint8_t* term, const uint8_t* trunc, int32_t T, int32_t N,
+                          int64_t* count) {
+    const long long waves = (long long)f.W * ((T + EP_U - 1) / EP_U);
+    hipLaunchKernelGGL(k_episode_count, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, f.st, term, trunc, T, N, f.W,
+                       f.offs, f.flags);
+    launch_offsets(f, count);
+}
+
+int scan_launched() {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fjsp_internal_fail(hipGetErrorString(e));
         return -2;
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fjsp_episode_temp_bytes(int32_t T, int32_t N, uint64_t* bytes) {
+    return scan_temp_bytes("fjsp_episode_temp_bytes", EPISODES, T, N, bytes);
+}
+
+int fjsp_episode_scan(const double* rewards, const uint8_t* term, const uint8_t* trunc, const int32_t* orders_completed,
+                      const int32_t* packaged, int32_t T, int32_t N, uint32_t env_gid0, int64_t step0, double* acc,
+                      int32_t* len, fjsp_episode_rec* recs, int64_t cap, int64_t* count, void* temp, uint64_t temp_bytes,
+                      void* stream) {
+    ScanFront f;
+    if (scan_front("fjsp_episode_scan", EPISODES, T, N, cap, !rewards || !term || !trunc || !acc || !len, recs, count,
+                   temp, temp_bytes, stream, &f))
+        return -1;
+    launch_episode_count(f, term, trunc, T, N, count);
+    const EpArgs p = {orders_completed, packaged, recs, scan_head(cap, step0, env_gid0, T, N)};
+    hipLaunchKernelGGL(k_episode_scan, dim3((unsigned)f.W), dim3(64 * EP_A), 0, f.st, rewards, f.flags, f.offs, f.base, p,
+                       f.W, acc, len);
+    return scan_launched();
 }
 
 int fjsp_kpi_carry_words(void) { return KPI_WORDS; }
@@ -986,100 +1039,37 @@ int fjsp_kpi_scan(const uint32_t* results, const uint8_t* term, const uint8_t* t
                   const int32_t* orders_completed, const int32_t* packaged, const double* sim_time, int32_t T,
                   int32_t N, uint32_t env_gid0, int64_t step0, int32_t* carry, fjsp_kpi_rec* recs, int64_t cap,
                   int64_t* count, void* temp, uint64_t temp_bytes, void* stream) {
-    if (T <= 0 || N <= 0) return fjsp_internal_fail("fjsp_kpi_scan: T and N must be > 0");
-    if (cap < 0) return fjsp_internal_fail("fjsp_kpi_scan: cap must be >= 0");
-    if (!term || !trunc || !carry || !count || !temp || (cap > 0 && !recs))
-        return fjsp_internal_fail("fjsp_kpi_scan: null buffer");
-    uint64_t table, total;
-    if (!ep_temp_layout(T, N, &table, &total)) return fjsp_internal_fail("fjsp_kpi_scan: T * N must be < 2^31");
-    if (temp_bytes < total) return fjsp_internal_fail("fjsp_kpi_scan: temp buffer too small");
-    if ((((uintptr_t)recs | (uintptr_t)temp) & 15u) != 0)
-        return fjsp_internal_fail("fjsp_kpi_scan: recs and temp must be 16-byte aligned");
-    const int W = (int)(((int64_t)N + 63) / 64);   // T W 64 < 2^31 (checked above)
-    const int L = T * W;
-    uint32_t* offs = (uint32_t*)temp;
-    long long* base = (long long*)((char*)temp + table);
-    uint32_t* flags = (uint32_t*)((char*)temp + table + 16);
-    const hipStream_t st = (hipStream_t)stream;
-    const long long waves = (long long)W * ((T + EP_U - 1) / EP_U);
-    hipLaunchKernelGGL(k_episode_count, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, term, trunc, T, N, W, offs,
-                       flags);
-    hipLaunchKernelGGL(k_episode_offsets, dim3(1), dim3(EPO_THREADS), 0, st, offs, L, base, (long long*)count);
-    KpiArgs p;
-    p.res = results;
-    p.obs = obs_i8;
-    p.oc = orders_completed;
-    p.pk = packaged;
-    p.st = sim_time;
-    p.recs = recs;
-    p.carry = carry;
-    p.cap = cap;
-    p.base = 0;
-    p.step0 = step0;
-    p.gid0 = env_gid0;
-    p.T = T;
-    p.N = N;
-    hipLaunchKernelGGL(k_kpi_scan, dim3((unsigned)W), dim3(64 * EP_A), 0, st, flags, offs, base, p, W);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        fjsp_internal_fail(hipGetErrorString(e));
-        return -2;
-    }
-    return 0;
+    ScanFront f;
+    if (scan_front("fjsp_kpi_scan", EPISODES, T, N, cap, !term || !trunc || !carry, recs, count, temp, temp_bytes, stream,
+                   &f))
+        return -1;
+    launch_episode_count(f, term, trunc, T, N, count);
+    const KpiArgs p = {results, obs_i8, orders_completed, packaged, sim_time, recs, carry,
+                       scan_head(cap, step0, env_gid0, T, N)};
+    hipLaunchKernelGGL(k_kpi_scan, dim3((unsigned)f.W), dim3(64 * EP_A), 0, f.st, f.flags, f.offs, f.base, p, f.W);
+    return scan_launched();
 }
 
 int fjsp_schedule_carry_words(void) { return SC_WORDS; }
 
 int fjsp_schedule_temp_bytes(int32_t T, int32_t N, uint64_t* bytes) {
-    if (T <= 0 || N <= 0) return fjsp_internal_fail("fjsp_schedule_temp_bytes: T and N must be > 0");
-    if (!bytes) return fjsp_internal_fail("fjsp_schedule_temp_bytes: null pointer");
-    uint64_t table, total;
-    if (!sched_temp_layout(T, N, &table, &total)) return fjsp_internal_fail("fjsp_schedule_temp_bytes: T * N must be < 2^30");
-    *bytes = total;
-    return 0;
+    return scan_temp_bytes("fjsp_schedule_temp_bytes", OPS, T, N, bytes);
 }
 
 int fjsp_schedule_scan(const uint32_t* results, const uint32_t* held, const uint8_t* term, const uint8_t* trunc, int32_t T,
                        int32_t N, uint32_t env_gid0, int64_t step0, int32_t* carry, fjsp_op_rec* recs, int64_t cap,
                        int64_t* count, void* temp, uint64_t temp_bytes, void* stream) {
-    if (T <= 0 || N <= 0) return fjsp_internal_fail("fjsp_schedule_scan: T and N must be > 0");
-    if (cap < 0) return fjsp_internal_fail("fjsp_schedule_scan: cap must be >= 0");
-    if (!results || !held || !term || !trunc || !carry || !count || !temp || (cap > 0 && !recs))
-        return fjsp_internal_fail("fjsp_schedule_scan: null buffer");
-    uint64_t table, total;
-    if (!sched_temp_layout(T, N, &table, &total)) return fjsp_internal_fail("fjsp_schedule_scan: T * N must be < 2^30");
-    if (temp_bytes < total) return fjsp_internal_fail("fjsp_schedule_scan: temp buffer too small");
-    if ((((uintptr_t)recs | (uintptr_t)temp) & 15u) != 0)
-        return fjsp_internal_fail("fjsp_schedule_scan: recs and temp must be 16-byte aligned");
+    ScanFront f;
+    if (scan_front("fjsp_schedule_scan", OPS, T, N, cap, !results || !held || !term || !trunc || !carry, recs, count, temp,
+                   temp_bytes, stream, &f))
+        return -1;
     if ((((uintptr_t)results | (uintptr_t)held | (uintptr_t)carry) & 3u) != 0 || ((uintptr_t)count & 7u) != 0)
         return fjsp_internal_fail("fjsp_schedule_scan: results, held and carry must be 4-byte, count 8-byte aligned");
-    const int W = (int)(((int64_t)N + 63) / 64);
-    const int L = T * W;
-    uint32_t* offs = (uint32_t*)temp;
-    long long* base = (long long*)((char*)temp + table);
-    const hipStream_t st = (hipStream_t)stream;
-    SchedArgs p;
-    p.res = results;
-    p.held = held;
-    p.term = term;
-    p.trunc = trunc;
-    p.recs = recs;
-    p.carry = carry;
-    p.cap = cap;
-    p.base = 0;
-    p.step0 = step0;
-    p.gid0 = env_gid0;
-    p.T = T;
-    p.N = N;
-    hipLaunchKernelGGL(k_schedule_scan<false>, dim3((unsigned)W), dim3(64), 0, st, p, offs, base, W);
-    hipLaunchKernelGGL(k_episode_offsets, dim3(1), dim3(EPO_THREADS), 0, st, offs, L, base, (long long*)count);
-    hipLaunchKernelGGL(k_schedule_scan<true>, dim3((unsigned)W), dim3(64), 0, st, p, offs, base, W);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        fjsp_internal_fail(hipGetErrorString(e));
-        return -2;
-    }
-    return 0;
+    const SchedArgs p = {results, held, term, trunc, recs, carry, scan_head(cap, step0, env_gid0, T, N)};
+    hipLaunchKernelGGL(k_schedule_scan<false>, dim3((unsigned)f.W), dim3(64), 0, f.st, p, f.offs, f.base, f.W);
+    launch_offsets(f, count);
+    hipLaunchKernelGGL(k_schedule_scan<true>, dim3((unsigned)f.W), dim3(64), 0, f.st, p, f.offs, f.base, f.W);
+    return scan_launched();
 }
 
 int fjsp_packaging_carry_words(void) { return PK_WORDS; }
@@ -1092,60 +1082,25 @@ int fjsp_packaging_ring_bytes(int32_t N, uint64_t* bytes) {
 }
 
 int fjsp_packaging_temp_bytes(int32_t T, int32_t N, uint64_t* bytes) {
-    if (T <= 0 || N <= 0) return fjsp_internal_fail("fjsp_packaging_temp_bytes: T and N must be > 0");
-    if (!bytes) return fjsp_internal_fail("fjsp_packaging_temp_bytes: null pointer");
-    uint64_t table, total;
-    if (!sched_temp_layout(T, N, &table, &total)) return fjsp_internal_fail("fjsp_packaging_temp_bytes: T * N must be < 2^30");
-    *bytes = total;
-    return 0;
+    return scan_temp_bytes("fjsp_packaging_temp_bytes", OPS, T, N, bytes);
 }
 
 int fjsp_packaging_scan(const uint32_t* results, const uint32_t* held, const uint32_t* pack, const uint8_t* term,
                         const uint8_t* trunc, int32_t T, int32_t N, uint32_t env_gid0, int64_t step0, int32_t* carry,
                         uint32_t* ring, fjsp_op_rec* recs, int64_t cap, int64_t* count, void* temp, uint64_t temp_bytes,
                         void* stream) {
-    if (T <= 0 || N <= 0) return fjsp_internal_fail("fjsp_packaging_scan: T and N must be > 0");
-    if (cap < 0) return fjsp_internal_fail("fjsp_packaging_scan: cap must be >= 0");
-    if (!results || !held || !pack || !term || !trunc || !carry || !ring || !count || !temp || (cap > 0 && !recs))
-        return fjsp_internal_fail("fjsp_packaging_scan: null buffer");
-    uint64_t table, total;
-    // at most one arrival per env and row, and 255 runs per env carried in: the sums stay in 32 bits
-    if (!sched_temp_layout(T, N, &table, &total)) return fjsp_internal_fail("fjsp_packaging_scan: T * N must be < 2^30");
-    if (temp_bytes < total) return fjsp_internal_fail("fjsp_packaging_scan: temp buffer too small");
-    if ((((uintptr_t)recs | (uintptr_t)temp) & 15u) != 0)
-        return fjsp_internal_fail("fjsp_packaging_scan: recs and temp must be 16-byte aligned");
+    ScanFront f;
+    if (scan_front("fjsp_packaging_scan", OPS, T, N, cap, !results || !held || !pack || !term || !trunc || !carry || !ring,
+                   recs, count, temp, temp_bytes, stream, &f))
+        return -1;
     if ((((uintptr_t)results | (uintptr_t)held | (uintptr_t)pack | (uintptr_t)carry | (uintptr_t)ring) & 3u) != 0 ||
         ((uintptr_t)count & 7u) != 0)
         return fjsp_internal_fail("fjsp_packaging_scan: results, held, pack, carry and ring must be 4-byte, count 8-byte aligned");
-    const int W = (int)(((int64_t)N + 63) / 64);
-    const int L = T * W;
-    uint32_t* offs = (uint32_t*)temp;
-    long long* base = (long long*)((char*)temp + table);
-    const hipStream_t st = (hipStream_t)stream;
-    PackArgs p;
-    p.res = results;
-    p.held = held;
-    p.pack = pack;
-    p.term = term;
-    p.trunc = trunc;
-    p.recs = recs;
-    p.carry = carry;
-    p.ring = ring;
-    p.cap = cap;
-    p.base = 0;
-    p.step0 = step0;
-    p.gid0 = env_gid0;
-    p.T = T;
-    p.N = N;
-    hipLaunchKernelGGL(k_packaging_scan<false>, dim3((unsigned)W), dim3(64), 0, st, p, offs, base, W);
-    hipLaunchKernelGGL(k_episode_offsets, dim3(1), dim3(EPO_THREADS), 0, st, offs, L, base, (long long*)count);
-    hipLaunchKernelGGL(k_packaging_scan<true>, dim3((unsigned)W), dim3(64), 0, st, p, offs, base, W);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        fjsp_internal_fail(hipGetErrorString(e));
-        return -2;
-    }
-    return 0;
+    const PackArgs p = {results, held, pack, term, trunc, recs, carry, ring, scan_head(cap, step0, env_gid0, T, N)};
+    hipLaunchKernelGGL(k_packaging_scan<false>, dim3((unsigned)f.W), dim3(64), 0, f.st, p, f.offs, f.base, f.W);
+    launch_offsets(f, count);
+    hipLaunchKernelGGL(k_packaging_scan<true>, dim3((unsigned)f.W), dim3(64), 0, f.st, p, f.offs, f.base, f.W);
+    return scan_launched();
 }
 
 }  // extern "C"

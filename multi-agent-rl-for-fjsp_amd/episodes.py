@@ -12,6 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _native as nat
+from .slablog import EpisodeSlabLog, _ptr
 
 NA = 8
 FLAG_TERMINATED, FLAG_TRUNCATED = 1, 2
@@ -78,75 +79,37 @@ def temp_bytes(T, N):
     return int(n.value)
 
 
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-class EpisodeLog:
+class EpisodeLog(EpisodeSlabLog):
     """Device-resident episode log of num_envs envs: the carry of the open episodes (per-agent
     sums, steps so far), a record buffer of `capacity` fjsp_episode_rec, the device-side episode
     count and the running vector-step counter step0.  scan() appends without synchronising;
     pop() copies the records to the host (the only synchronisation) and empties the log."""
+    REC_DTYPE = REC_DTYPE
+    CARRY = ("acc", "len")
 
     def __init__(self, num_envs, device, capacity=65536, env_id_base=0):
         import torch
-        self.N = int(num_envs)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise nat.FjspNativeError("EpisodeLog needs a GPU (HIP); no CPU fallback exists")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.capacity = int(capacity)
-        self.env_id_base = int(env_id_base)
+        super().__init__(num_envs, device, capacity, env_id_base)
         self.acc = torch.zeros(NA, self.N, dtype=torch.float64, device=self.device)
         self.len = torch.zeros(self.N, dtype=torch.int32, device=self.device)
-        self.recs = torch.zeros(max(self.capacity, 1) * REC_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
-        self.count = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.step0 = 0
-        self._temp = None
-        self._seq0 = 0   # episodes popped so far: seq keeps counting over the log's lifetime
 
-    def _temp_for(self, T):
-        import torch
-        need = temp_bytes(T, self.N)
-        if self._temp is None or self._temp.numel() < need:
-            self._temp = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._temp
+    def _temp_bytes(self, T):
+        return temp_bytes(T, self.N)
 
     def scan(self, rewards, term, trunc, orders_completed=None, packaged=None):
         """Account the [T, 8, N] slab (contiguous device tensors: rewards f64, term / trunc u8 [T, N],
         optional int32 infos slabs) on the current stream; advances step0 by T."""
         import torch
-        T = int(rewards.shape[0])
-        if tuple(rewards.shape) != (T, NA, self.N) or rewards.dtype != torch.float64:
-            raise ValueError(f"rewards must be float64 [T, 8, {self.N}]")
-        for name, x, dt in (("term", term, torch.uint8), ("trunc", trunc, torch.uint8),
-                            ("orders_completed", orders_completed, torch.int32), ("packaged", packaged, torch.int32)):
-            if x is not None and (tuple(x.shape) != (T, self.N) or x.dtype != dt):
-                raise ValueError(f"{name} must be {dt} [T, {self.N}]")
-        for x in (rewards, term, trunc, orders_completed, packaged):
-            if x is not None and (not x.is_contiguous() or x.device != self.device):
-                raise ValueError("EpisodeLog.scan takes contiguous tensors on the log's device")
-        temp = self._temp_for(T)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            nat.check(nat.lib().fjsp_episode_scan(
-                _ptr(rewards), _ptr(term), _ptr(trunc), _ptr(orders_completed), _ptr(packaged), T, self.N,
-                self.env_id_base, self.step0, _ptr(self.acc), _ptr(self.len), _ptr(self.recs), self.capacity,
-                _ptr(self.count), _ptr(temp), temp.numel(), ctypes.c_void_p(stream)))
-        self.step0 += T
-
-    def pop_records(self):
-        """(records, dropped): the records logged since the last pop as a REC_DTYPE array in seq
-        order (the bytes the kernel wrote; seq counted over the log's lifetime) and the number that
-        did not fit the capacity.  Synchronises; empties the log, keeps the carry."""
-        count = int(self.count.item())
-        n = min(count, self.capacity)
-        recs = self.recs[:n * REC_DTYPE.itemsize].cpu().numpy().view(REC_DTYPE).copy()
-        recs["seq"] += np.uint64(self._seq0)
-        self._seq0 += count
-        self.count.zero_()
-        return recs, max(0, count - self.capacity)
+        T, N = int(rewards.shape[0]), self.N
+        self._launch(T, (("rewards", rewards, (torch.float64,), (T, NA, N), True),
+                         ("term", term, (torch.uint8,), (T, N), True),
+                         ("trunc", trunc, (torch.uint8,), (T, N), True),
+                         ("orders_completed", orders_completed, (torch.int32,), (T, N), False),
+                         ("packaged", packaged, (torch.int32,), (T, N), False)),
+                     lambda temp, nbytes, stream: nat.lib().fjsp_episode_scan(
+                         _ptr(rewards), _ptr(term), _ptr(trunc), _ptr(orders_completed), _ptr(packaged), T, N,
+                         self.env_id_base, self.step0, _ptr(self.acc), _ptr(self.len), _ptr(self.recs), self.capacity,
+                         _ptr(self.count), temp, nbytes, stream))
 
     def pop(self):
         """Every record logged since the last pop, in seq order, as a dict of numpy arrays: env,
@@ -154,31 +117,6 @@ class EpisodeLog:
         [8, n], and dropped = the episodes that did not fit the capacity.  Synchronises; empties
         the log (the carry of the open episodes is kept)."""
         return records_dict(*self.pop_records())
-
-    def reset(self, env_mask=None):
-        """Zero the carry of the selected envs (all by default): after a manual env.reset."""
-        import torch
-        if env_mask is None:
-            self.acc.zero_()
-            self.len.zero_()
-            return
-        m = torch.as_tensor(env_mask, device=self.device).bool()
-        self.acc.masked_fill_(m[None, :], 0.0)
-        self.len.masked_fill_(m, 0)
-
-    def state(self):
-        """The carry, step0 and the counts, for a checkpoint (records not yet popped are not part
-        of it: pop() first)."""
-        return {"acc": self.acc.cpu().numpy(), "len": self.len.cpu().numpy(), "step0": int(self.step0),
-                "count": int(self.count.item()) + self._seq0}
-
-    def load_state(self, st):
-        import torch
-        self.acc.copy_(torch.as_tensor(np.asarray(st["acc"], dtype=np.float64)))
-        self.len.copy_(torch.as_tensor(np.asarray(st["len"], dtype=np.int32)))
-        self.step0 = int(st["step0"])
-        self._seq0 = int(st["count"])
-        self.count.zero_()
 
 
 __all__ = ["episodes_reference", "EpisodeLog", "REC_DTYPE", "records_dict", "temp_bytes"]

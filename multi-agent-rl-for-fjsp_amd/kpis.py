@@ -12,13 +12,12 @@ fjsp_kpi_rec per finished episode to a device-resident log with no host synchron
 The records are numbered exactly as EpisodeLog's: scanning the same slabs into both logs from the
 same starting state makes record k of each describe the same episode (equal 40-byte heads).
 """
-import ctypes
-
 import numpy as np
 
 from . import _native as nat
 from . import spec
 from .episodes import FLAG_TERMINATED, FLAG_TRUNCATED, temp_bytes
+from .slablog import EpisodeSlabLog, _ptr, word_dtypes
 
 NA, NS = 8, 6
 TIMES_DTYPE = np.dtype([("first_step", "<i4"), ("last_step", "<i4"), ("step_sum", "<i8")])
@@ -232,84 +231,40 @@ def carry_words():
     return int(nat.lib().fjsp_kpi_carry_words())
 
 
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-class KpiLog:
+class KpiLog(EpisodeSlabLog):
     """Device-resident KPI log of num_envs envs: the carry of the open episodes (their counters so
     far), a record buffer of `capacity` fjsp_kpi_rec, the device-side episode count and the
     running vector-step counter step0.  scan() appends without synchronising; pop() copies the
     records to the host (the only synchronisation) and empties the log."""
+    REC_DTYPE = KPI_DTYPE
 
     def __init__(self, num_envs, device, capacity=65536, env_id_base=0):
         import torch
-        self.N = int(num_envs)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise nat.FjspNativeError("KpiLog needs a GPU (HIP); no CPU fallback exists")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.capacity = int(capacity)
-        self.env_id_base = int(env_id_base)
+        super().__init__(num_envs, device, capacity, env_id_base)
         words = carry_words()
         assert words == CARRY_WORDS, (words, CARRY_WORDS)
         self.carry = torch.zeros(words, self.N, dtype=torch.int32, device=self.device)
-        self.recs = torch.zeros(max(self.capacity, 1) * KPI_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
-        self.count = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.step0 = 0
-        self._temp = None
-        self._seq0 = 0   # episodes popped so far: seq keeps counting over the log's lifetime
 
-    def _temp_for(self, T):
-        import torch
-        need = temp_bytes(T, self.N)
-        if self._temp is None or self._temp.numel() < need:
-            self._temp = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._temp
+    def _temp_bytes(self, T):
+        return temp_bytes(T, self.N)
 
     def scan(self, results, term, trunc, obs_i8=None, orders_completed=None, packaged=None, sim_time=None):
         """Reduce the slab (contiguous device tensors: results int32 / uint32 [T, 8, N], term / trunc
         u8 [T, N], obs_i8 int8 [T, 12, N], int32 infos slabs [T, N], sim_time f64 [T, N]; every one
         but term / trunc may be None) on the current stream; advances step0 by T."""
         import torch
-        T = int(term.shape[0])
-        words = (torch.int32, getattr(torch, "uint32", torch.int32))
-        for name, x, dts, shape in (("results", results, words, (T, NA, self.N)),
-                                    ("term", term, (torch.uint8,), (T, self.N)),
-                                    ("trunc", trunc, (torch.uint8,), (T, self.N)),
-                                    ("obs_i8", obs_i8, (torch.int8,), (T, 2 * NS, self.N)),
-                                    ("orders_completed", orders_completed, (torch.int32,), (T, self.N)),
-                                    ("packaged", packaged, (torch.int32,), (T, self.N)),
-                                    ("sim_time", sim_time, (torch.float64,), (T, self.N))):
-            if x is None:
-                if name in ("term", "trunc"):
-                    raise ValueError(f"{name} is required")
-                continue
-            if tuple(x.shape) != shape or x.dtype not in dts:
-                raise ValueError(f"{name} must be {dts[0]} {list(shape)}")
-            if not x.is_contiguous() or x.device != self.device:
-                raise ValueError("KpiLog.scan takes contiguous tensors on the log's device")
-        temp = self._temp_for(T)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            nat.check(nat.lib().fjsp_kpi_scan(
-                _ptr(results), _ptr(term), _ptr(trunc), _ptr(obs_i8), _ptr(orders_completed), _ptr(packaged),
-                _ptr(sim_time), T, self.N, self.env_id_base, self.step0, _ptr(self.carry), _ptr(self.recs),
-                self.capacity, _ptr(self.count), _ptr(temp), temp.numel(), ctypes.c_void_p(stream)))
-        self.step0 += T
-
-    def pop_records(self):
-        """(records, dropped): the records logged since the last pop as a KPI_DTYPE array in seq
-        order (the bytes the kernel wrote; seq counted over the log's lifetime) and the number that
-        did not fit the capacity.  Synchronises; empties the log, keeps the carry."""
-        count = int(self.count.item())
-        n = min(count, self.capacity)
-        recs = self.recs[:n * KPI_DTYPE.itemsize].cpu().numpy().view(KPI_DTYPE).copy()
-        recs["seq"] += np.uint64(self._seq0)
-        self._seq0 += count
-        self.count.zero_()
-        return recs, max(0, count - self.capacity)
+        T, N = int(term.shape[0]), self.N
+        self._launch(T, (("results", results, word_dtypes(), (T, NA, N), False),
+                         ("term", term, (torch.uint8,), (T, N), True),
+                         ("trunc", trunc, (torch.uint8,), (T, N), True),
+                         ("obs_i8", obs_i8, (torch.int8,), (T, 2 * NS, N), False),
+                         ("orders_completed", orders_completed, (torch.int32,), (T, N), False),
+                         ("packaged", packaged, (torch.int32,), (T, N), False),
+                         ("sim_time", sim_time, (torch.float64,), (T, N), False)),
+                     lambda temp, nbytes, stream: nat.lib().fjsp_kpi_scan(
+                         _ptr(results), _ptr(term), _ptr(trunc), _ptr(obs_i8), _ptr(orders_completed), _ptr(packaged),
+                         _ptr(sim_time), T, N, self.env_id_base, self.step0, _ptr(self.carry), _ptr(self.recs),
+                         self.capacity, _ptr(self.count), temp, nbytes, stream))
 
     def pop(self):
         """Every record logged since the last pop, in seq order, as a dict of numpy arrays: the head
@@ -318,28 +273,6 @@ class KpiLog:
         [6, 4, n], the raw `records` and dropped = the episodes that did not fit the capacity.
         Synchronises; empties the log (the carry of the open episodes is kept)."""
         return records_dict(*self.pop_records())
-
-    def reset(self, env_mask=None):
-        """Zero the carry of the selected envs (all by default): after a manual env.reset."""
-        import torch
-        if env_mask is None:
-            self.carry.zero_()
-            return
-        m = torch.as_tensor(env_mask, device=self.device).bool()
-        self.carry.masked_fill_(m[None, :], 0)
-
-    def state(self):
-        """The carry, step0 and the counts, for a checkpoint (records not yet popped are not part
-        of it: pop() first)."""
-        return {"carry": self.carry.cpu().numpy(), "step0": int(self.step0),
-                "count": int(self.count.item()) + self._seq0}
-
-    def load_state(self, st):
-        import torch
-        self.carry.copy_(torch.as_tensor(np.asarray(st["carry"], dtype=np.int32)))
-        self.step0 = int(st["step0"])
-        self._seq0 = int(st["count"])
-        self.count.zero_()
 
 
 __all__ = ["kpi_reference", "kpi_summary", "KpiLog", "KPI_DTYPE", "TIMES_DTYPE", "HEAD_BYTES", "HEAD_FIELDS",

@@ -52,6 +52,7 @@ import ctypes
 import numpy as np
 
 from . import _native as nat
+from .slablog import SlabLog, _ptr, word_dtypes
 
 # include/fjsp.h fjsp_op_rec (32 bytes)
 OP_DTYPE = np.dtype([("env_gid", "<u4"), ("info", "<u4"), ("episode_start", "<i8"), ("tray", "<u4"),
@@ -334,75 +335,35 @@ def temp_bytes(T, N):
     return int(n.value)
 
 
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-class ScheduleLog:
+class ScheduleLog(SlabLog):
     """Device-resident operation log of num_envs envs: the carry of the open episodes (length, open
     ops), a record buffer of `capacity` fjsp_op_rec, the device-side record count and the running
     vector-step counter step0.  scan() appends without synchronising; pop() copies the records to
     the host (the only synchronisation) and empties the log."""
+    REC_DTYPE = OP_DTYPE
 
     def __init__(self, num_envs, device, env_id_base=0, capacity=1 << 20):
         import torch
-        self.N = int(num_envs)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise nat.FjspNativeError("ScheduleLog needs a GPU (HIP); no CPU fallback exists")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.capacity = int(capacity)
-        self.env_id_base = int(env_id_base)
+        super().__init__(num_envs, device, capacity, env_id_base)
         words = carry_words()
         assert words == CARRY_WORDS, (words, CARRY_WORDS)
         self.carry = torch.zeros(words, self.N, dtype=torch.int32, device=self.device)
-        self.recs = torch.zeros(max(self.capacity, 1) * OP_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
-        self.count = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.step0 = 0
-        self._temp = None
 
-    def _temp_for(self, T):
-        import torch
-        need = temp_bytes(T, self.N)
-        if self._temp is None or self._temp.numel() < need:
-            self._temp = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._temp
+    def _temp_bytes(self, T):
+        return temp_bytes(T, self.N)
 
     def scan(self, results, held, term, trunc):
         """Compact the slab (contiguous device tensors: results int32 / uint32 [T, 8, N], held int32 /
         uint32 [T, 3, N], term / trunc u8 [T, N]) on the current stream; advances step0 by T."""
         import torch
-        T = int(term.shape[0])
-        words = (torch.int32, getattr(torch, "uint32", torch.int32))
-        for name, x, dts, shape in (("results", results, words, (T, NA, self.N)),
-                                    ("held", held, words, (T, HELD_ROWS, self.N)),
-                                    ("term", term, (torch.uint8,), (T, self.N)),
-                                    ("trunc", trunc, (torch.uint8,), (T, self.N))):
-            if x is None:
-                raise ValueError(f"{name} is required")
-            if tuple(x.shape) != shape or x.dtype not in dts:
-                raise ValueError(f"{name} must be {dts[0]} {list(shape)}")
-            if not x.is_contiguous() or x.device != self.device:
-                raise ValueError("ScheduleLog.scan takes contiguous tensors on the log's device")
-        temp = self._temp_for(T)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            nat.check(nat.lib().fjsp_schedule_scan(
-                _ptr(results), _ptr(held), _ptr(term), _ptr(trunc), T, self.N, self.env_id_base, self.step0,
-                _ptr(self.carry), _ptr(self.recs), self.capacity, _ptr(self.count), _ptr(temp), temp.numel(),
-                ctypes.c_void_p(stream)))
-        self.step0 += T
-
-    def pop_records(self):
-        """(records, dropped): the records logged since the last pop as an OP_DTYPE array in the
-        order they were numbered (the bytes the kernel wrote) and the number that did not fit the
-        capacity.  Synchronises; empties the log, keeps the carry."""
-        count = int(self.count.item())
-        n = min(count, self.capacity)
-        recs = self.recs[:n * OP_DTYPE.itemsize].cpu().numpy().view(OP_DTYPE).copy()
-        self.count.zero_()
-        return recs, max(0, count - self.capacity)
+        T, N = int(term.shape[0]), self.N
+        self._launch(T, (("results", results, word_dtypes(), (T, NA, N), True),
+                         ("held", held, word_dtypes(), (T, HELD_ROWS, N), True),
+                         ("term", term, (torch.uint8,), (T, N), True),
+                         ("trunc", trunc, (torch.uint8,), (T, N), True)),
+                     lambda temp, nbytes, stream: nat.lib().fjsp_schedule_scan(
+                         _ptr(results), _ptr(held), _ptr(term), _ptr(trunc), T, N, self.env_id_base, self.step0,
+                         _ptr(self.carry), _ptr(self.recs), self.capacity, _ptr(self.count), temp, nbytes, stream))
 
     def pop(self):
         """Every record logged since the last pop as a dict of numpy arrays: env, episode_start,
@@ -411,32 +372,19 @@ class ScheduleLog:
         capacity.  Synchronises; empties the log (the carry of the open episodes is kept)."""
         return records_dict(*self.pop_records())
 
-    def reset(self, env_mask=None):
-        """Zero the carry of the selected envs (all by default): after a manual env.reset."""
-        import torch
-        if env_mask is None:
-            self.carry.zero_()
-            return
-        m = torch.as_tensor(env_mask, device=self.device).bool()
-        self.carry.masked_fill_(m[None, :], 0)
 
-
-class PackagingLog:
+class PackagingLog(SlabLog):
     """Device-resident log of the packaging runs of num_envs envs (fjsp_packaging_scan): the carry
     of the open episodes, the per-station FIFO rings (4 KB per env), a record buffer of `capacity`
     fjsp_op_rec, the device-side record count and the running vector-step counter step0.  scan()
-    appends without synchronising; pop() copies the records to the host and empties the log."""
+    appends without synchronising; pop() copies the records to the host and empties the log.
+    reset() zeroes the carry only: an all-zero carry empties the env's FIFOs, so the rings need no
+    clearing."""
+    REC_DTYPE = OP_DTYPE
 
     def __init__(self, num_envs, device, env_id_base=0, capacity=1 << 20):
         import torch
-        self.N = int(num_envs)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise nat.FjspNativeError("PackagingLog needs a GPU (HIP); no CPU fallback exists")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.capacity = int(capacity)
-        self.env_id_base = int(env_id_base)
+        super().__init__(num_envs, device, capacity, env_id_base)
         words = int(nat.lib().fjsp_packaging_carry_words())
         assert words == PACK_CARRY_WORDS, (words, PACK_CARRY_WORDS)
         n = ctypes.c_uint64()
@@ -444,69 +392,32 @@ class PackagingLog:
         assert n.value == PACK_ROWS * PACK_RING * 4 * self.N
         self.carry = torch.zeros(words, self.N, dtype=torch.int32, device=self.device)
         self.ring = torch.zeros(PACK_ROWS, PACK_RING, self.N, dtype=torch.int32, device=self.device)
-        self.recs = torch.zeros(max(self.capacity, 1) * OP_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
-        self.count = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.step0 = 0
-        self._temp = None
 
-    def _temp_for(self, T):
-        import torch
+    def _temp_bytes(self, T):
         n = ctypes.c_uint64()
         nat.check(nat.lib().fjsp_packaging_temp_bytes(int(T), self.N, ctypes.byref(n)))
-        if self._temp is None or self._temp.numel() < n.value:
-            self._temp = torch.empty(int(n.value), dtype=torch.uint8, device=self.device)
-        return self._temp
+        return int(n.value)
 
     def scan(self, results, held, pack, term, trunc):
         """Compact the slab (contiguous device tensors: results int32 / uint32 [T, 8, N], held
         [T, 3, N] and pack [T, 4, N] of the same dtypes, term / trunc u8 [T, N]) on the current
         stream; advances step0 by T."""
         import torch
-        T = int(term.shape[0])
-        words = (torch.int32, getattr(torch, "uint32", torch.int32))
-        for name, x, dts, shape in (("results", results, words, (T, NA, self.N)),
-                                    ("held", held, words, (T, HELD_ROWS, self.N)),
-                                    ("pack", pack, words, (T, PACK_ROWS, self.N)),
-                                    ("term", term, (torch.uint8,), (T, self.N)),
-                                    ("trunc", trunc, (torch.uint8,), (T, self.N))):
-            if x is None:
-                raise ValueError(f"{name} is required")
-            if tuple(x.shape) != shape or x.dtype not in dts:
-                raise ValueError(f"{name} must be {dts[0]} {list(shape)}")
-            if not x.is_contiguous() or x.device != self.device:
-                raise ValueError("PackagingLog.scan takes contiguous tensors on the log's device")
-        temp = self._temp_for(T)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            nat.check(nat.lib().fjsp_packaging_scan(
-                _ptr(results), _ptr(held), _ptr(pack), _ptr(term), _ptr(trunc), T, self.N, self.env_id_base,
-                self.step0, _ptr(self.carry), _ptr(self.ring), _ptr(self.recs), self.capacity, _ptr(self.count),
-                _ptr(temp), temp.numel(), ctypes.c_void_p(stream)))
-        self.step0 += T
-
-    def pop_records(self):
-        """(records, dropped) as ScheduleLog.pop_records: the bytes the kernel wrote, in the order
-        they were numbered.  Synchronises; empties the log, keeps the carry and the rings."""
-        count = int(self.count.item())
-        n = min(count, self.capacity)
-        recs = self.recs[:n * OP_DTYPE.itemsize].cpu().numpy().view(OP_DTYPE).copy()
-        self.count.zero_()
-        return recs, max(0, count - self.capacity)
+        T, N = int(term.shape[0]), self.N
+        self._launch(T, (("results", results, word_dtypes(), (T, NA, N), True),
+                         ("held", held, word_dtypes(), (T, HELD_ROWS, N), True),
+                         ("pack", pack, word_dtypes(), (T, PACK_ROWS, N), True),
+                         ("term", term, (torch.uint8,), (T, N), True),
+                         ("trunc", trunc, (torch.uint8,), (T, N), True)),
+                     lambda temp, nbytes, stream: nat.lib().fjsp_packaging_scan(
+                         _ptr(results), _ptr(held), _ptr(pack), _ptr(term), _ptr(trunc), T, N, self.env_id_base,
+                         self.step0, _ptr(self.carry), _ptr(self.ring), _ptr(self.recs), self.capacity,
+                         _ptr(self.count), temp, nbytes, stream))
 
     def pop(self):
         """Every packaging run logged since the last pop as a dict of numpy arrays: records_dict's
         fields (resource = 4 + station, from_loc = to_loc = 5) plus station (0..3) and granted."""
         return pack_records_dict(*self.pop_records())
-
-    def reset(self, env_mask=None):
-        """Zero the carry of the selected envs (all by default): after a manual env.reset.  An
-        all-zero carry empties the env's FIFOs, so the rings need no clearing."""
-        import torch
-        if env_mask is None:
-            self.carry.zero_()
-            return
-        m = torch.as_tensor(env_mask, device=self.device).bool()
-        self.carry.masked_fill_(m[None, :], 0)
 
 
 __all__ = ["OP_DTYPE", "ScheduleLog", "schedule_reference", "gantt", "check", "records_dict", "tray_fields",

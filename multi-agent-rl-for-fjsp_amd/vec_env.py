@@ -10,14 +10,11 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .slablog import LogSet, _ptr
 from .spec import AGENTS
 
 NI32, NI8, NF32, NMASK, NA, NFEAT = 20, 12, 6, 29, 8, 38
 POLICIES = {"random": 0, "unmasked": 0, "masked": 1, "heuristic": 2}   # FJSP_ACTIONS_*
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 class Buffers:
@@ -292,21 +289,7 @@ class FJSPVecEnv:
         into one reused Buffers, each followed by EpisodeLog.scan on the device.  Returns
         EpisodeLog.pop()'s dict of records (env, length, end_step, total, by_agent [8, n], ...).
         Only the records reach the host; no reward slab is copied."""
-        from .episodes import EpisodeLog
-        steps, chunk = int(steps), max(1, min(int(chunk), int(steps)))
-        self.reset(seeds=seeds, num_orders=num_orders)
-        # room for one episode per 16 steps and env (the shortest heuristic episodes take ~30);
-        # what does not fit is counted in the result's `dropped`, never written
-        log = EpisodeLog(self.num_envs, self.device, env_id_base=self.env_id_base,
-                         capacity=max(65536, self.num_envs * (steps // 16 + 1)))
-        b = Buffers(chunk, self.num_envs, self.device, infos=True)
-        done = 0
-        while done < steps:
-            k = min(chunk, steps - done)
-            self.rollout(k, action_seed=action_seed, step0=done, policy=policy, autoreset=True, buffers=b)
-            log.scan(b.rewards[:k], b.term[:k], b.trunc[:k], b.orders_completed[:k], b.packaged[:k])
-            done += k
-        return log.pop()
+        return self._evaluate_logged(policy, num_orders, steps, seeds, action_seed, chunk, kpis=False)["episodes"]
 
     def evaluate_kpis(self, policy="heuristic", num_orders=5, steps=500, seeds=None, action_seed=0, chunk=256):
         """evaluate_episodes with the shop-floor KPIs beside the returns: the same loop, each chunk
@@ -315,23 +298,7 @@ class FJSPVecEnv:
         EpisodeLog.pop(), "kpis": KpiLog.pop()}; record k of each describes the same episode
         (kpis.kpi_summary derives makespan, flow times, utilisation, ... from "kpis").  Only the
         records reach the host."""
-        from .episodes import EpisodeLog
-        from .kpis import KpiLog
-        steps, chunk = int(steps), max(1, min(int(chunk), int(steps)))
-        self.reset(seeds=seeds, num_orders=num_orders)
-        cap = max(65536, self.num_envs * (steps // 16 + 1))   # as evaluate_episodes
-        log = EpisodeLog(self.num_envs, self.device, env_id_base=self.env_id_base, capacity=cap)
-        kpi = KpiLog(self.num_envs, self.device, env_id_base=self.env_id_base, capacity=cap)
-        b = Buffers(chunk, self.num_envs, self.device, infos=True)
-        done = 0
-        while done < steps:
-            k = min(chunk, steps - done)
-            self.rollout(k, action_seed=action_seed, step0=done, policy=policy, autoreset=True, buffers=b)
-            log.scan(b.rewards[:k], b.term[:k], b.trunc[:k], b.orders_completed[:k], b.packaged[:k])
-            kpi.scan(b.results[:k], b.term[:k], b.trunc[:k], b.obs_i8[:k], b.orders_completed[:k], b.packaged[:k],
-                     b.sim_time[:k])
-            done += k
-        return {"episodes": log.pop(), "kpis": kpi.pop()}
+        return self._evaluate_logged(policy, num_orders, steps, seeds, action_seed, chunk)
 
     def evaluate_schedule(self, policy="heuristic", num_orders=5, steps=500, seeds=None, action_seed=0, chunk=256,
                           packaging=False):
@@ -343,40 +310,35 @@ class FJSPVecEnv:
         reach the host.  packaging=True: the steps go through fjsp_step_sched, whose pack words feed a
         schedule.PackagingLog with the same rows, and the result has "pack_ops" = its pop() (one
         record per tray run at a packaging station; schedule.check_packaging, schedule.arrivals)."""
-        from .episodes import EpisodeLog
-        from .kpis import KpiLog
-        from .schedule import PackagingLog, ScheduleLog
+        return self._evaluate_logged(policy, num_orders, steps, seeds, action_seed, chunk, schedule=True,
+                                     packaging=bool(packaging))
+
+    def _evaluate_logged(self, policy, num_orders, steps, seeds, action_seed, chunk, kpis=True, schedule=False,
+                         packaging=False):
+        """The loop behind evaluate_episodes / _kpis / _schedule: from a reset, chunks of rows into one
+        reused Buffers, each scanned into a slablog.LogSet; returns its pop().  Two rollout paths,
+        which launch different kernels: one fjsp_step_many per chunk, or with schedule per row the
+        policy's actions (fjsp_actions) and one fjsp_step_held / fjsp_step_sched."""
         steps, chunk = int(steps), max(1, min(int(chunk), int(steps)))
         self.reset(seeds=seeds, num_orders=num_orders)
-        cap = max(65536, self.num_envs * (steps // 16 + 1))   # as evaluate_episodes
-        log = EpisodeLog(self.num_envs, self.device, env_id_base=self.env_id_base, capacity=cap)
-        kpi = KpiLog(self.num_envs, self.device, env_id_base=self.env_id_base, capacity=cap)
-        # an op takes at least one step per resource, an AGV op two (pickup, drop): 3 per 2 steps bounds it
-        ops = ScheduleLog(self.num_envs, self.device, env_id_base=self.env_id_base,
-                          capacity=max(65536, self.num_envs * (3 * steps // 2 + 3)))
-        # a packaging run needs an AGV carry before it: the same bound
-        pk = PackagingLog(self.num_envs, self.device, env_id_base=self.env_id_base,
-                          capacity=max(65536, self.num_envs * (steps // 2 + 1))) if packaging else None
-        b = Buffers(chunk, self.num_envs, self.device, infos=True, held=True, pack=bool(packaging))
-        rows = [RowBuffers(b, k) for k in range(chunk)]
-        act = torch.empty(NA, self.num_envs, dtype=torch.uint8, device=self.device)
+        logs = LogSet(self, steps, kpis=kpis, schedule=schedule, packaging=packaging)
+        b = Buffers(chunk, self.num_envs, self.device, infos=True, held=schedule, pack=packaging)
+        slabs = {name: getattr(b, name) for name in LogSet.SLABS}
+        if schedule:
+            rows = [RowBuffers(b, k) for k in range(chunk)]
+            act = torch.empty(NA, self.num_envs, dtype=torch.uint8, device=self.device)
         done = 0
         while done < steps:
             k = min(chunk, steps - done)
-            for j in range(k):
-                self.actions(policy, action_seed=action_seed, step=done + j, out=act)
-                self.step(act, autoreset=True, buffers=rows[j], held=b.held[j], pack=b.pack[j] if packaging else None)
-            log.scan(b.rewards[:k], b.term[:k], b.trunc[:k], b.orders_completed[:k], b.packaged[:k])
-            kpi.scan(b.results[:k], b.term[:k], b.trunc[:k], b.obs_i8[:k], b.orders_completed[:k], b.packaged[:k],
-                     b.sim_time[:k])
-            ops.scan(b.results[:k], b.held[:k], b.term[:k], b.trunc[:k])
-            if packaging:
-                pk.scan(b.results[:k], b.held[:k], b.pack[:k], b.term[:k], b.trunc[:k])
+            if schedule:
+                for j in range(k):
+                    self.actions(policy, action_seed=action_seed, step=done + j, out=act)
+                    self.step(act, autoreset=True, buffers=rows[j], held=b.held[j], pack=b.pack[j] if packaging else None)
+            else:
+                self.rollout(k, action_seed=action_seed, step0=done, policy=policy, autoreset=True, buffers=b)
+            logs.scan(slabs, k)
             done += k
-        out = {"episodes": log.pop(), "kpis": kpi.pop(), "ops": ops.pop()}
-        if packaging:
-            out["pack_ops"] = pk.pop()
-        return out
+        return logs.pop()
 
     def pack_a2c(self, feats=None, masks=None):
         """a2c features f32 [38, N] and masks int8 [29, N] of the current observations

@@ -246,6 +246,39 @@ def test_a_finished_order_chains_to_its_completion_step(evaluated):
     assert (arr >= 0).all() and (arr <= pk["start"][m]).all()
 
 
+def test_evaluate_schedule_chunks_equal_one_scan_by_hand(M):
+    """70 envs (one full wave and a partial one), 48 steps in chunks of 16: evaluate_schedule's four
+    results are, byte for byte, what the four logs give when driven by hand over the same 48 rows in
+    one scan each.  Pins the log set's slicing and the chunk carry together."""
+    V = M["V"]
+    n, steps, I = 70, 48, importlib.import_module
+    E, K = I("multi-agent-rl-for-fjsp_amd.episodes"), I("multi-agent-rl-for-fjsp_amd.kpis")
+    seeds = torch.arange(n) * 7 + 3
+    res = V.FJSPVecEnv(n, env_id_base=GID0).evaluate_schedule("heuristic", num_orders=2, steps=steps, seeds=seeds,
+                                                              chunk=16, packaging=True)
+    env = V.FJSPVecEnv(n, env_id_base=GID0)
+    env.reset(seeds=seeds, num_orders=2)
+    b = V.Buffers(steps, n, "cuda", infos=True, held=True, pack=True)
+    act = torch.empty(8, n, dtype=torch.uint8, device="cuda")
+    for t in range(steps):
+        env.actions("heuristic", action_seed=0, step=t, out=act)
+        env.step(act, autoreset=True, buffers=V.RowBuffers(b, t), held=b.held[t], pack=b.pack[t])
+    kw = dict(env_id_base=GID0, capacity=1 << 16)
+    logs = {"episodes": E.EpisodeLog(n, "cuda", **kw), "kpis": K.KpiLog(n, "cuda", **kw),
+            "ops": S.ScheduleLog(n, "cuda", **kw), "pack_ops": S.PackagingLog(n, "cuda", **kw)}
+    logs["episodes"].scan(b.rewards, b.term, b.trunc, b.orders_completed, b.packaged)
+    logs["kpis"].scan(b.results, b.term, b.trunc, b.obs_i8, b.orders_completed, b.packaged, b.sim_time)
+    logs["ops"].scan(b.results, b.held, b.term, b.trunc)
+    logs["pack_ops"].scan(b.results, b.held, b.pack, b.term, b.trunc)
+    want = {k: log.pop() for k, log in logs.items()}
+    assert sorted(res) == sorted(want)
+    for k, field in (("episodes", "total"), ("kpis", "records"), ("ops", "records"), ("pack_ops", "records")):
+        print(k, len(want[k][field]), "records")
+        assert res[k]["dropped"] == want[k]["dropped"] == 0, k
+        assert res[k][field].tobytes() == want[k][field].tobytes(), k
+    assert len(want["ops"]["records"]) > 0
+
+
 # ------------------------------------------------------------------ 4. capacity, appending
 def test_capacity_bounds_the_writes(rollouts):
     # whole logs are compared, so a case in which no env is flagged
