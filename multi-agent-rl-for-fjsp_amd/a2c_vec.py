@@ -757,36 +757,56 @@ def _run_sums(g, gy):
     return torch.cat([ce[..., :1], ce[..., 1:] - ce[..., :-1]], dim=-1).to(gy.dtype)
 
 
+def actor_head_forward(ctx, pu, g, masks, actions, adv, adv_mean, adv_std, count, coef, ppo=None):
+    """The forward of both loss-head Functions (_ActorHead; ppo_vec._ActorHeadPPO with ppo =
+    (logp_old, logp_out, clip_eps)): one launch of fjsp_a2c_actor_head / fjsp_a2c_actor_head_ppo
+    on the agents' per-group probabilities pu [8, 8, Umax] (RowGroups g) -> (per-agent losses f32
+    [8], the kernel's sums f64 [8, 2 or 4]); the per-sample gradients are saved in ctx for
+    actor_head_backward.  masks int8 [T, 29, n], actions u8 [T, 8, n], adv f64 [T, 8, n] (the
+    slab's layouts), adv_mean / adv_std f32 [8] (None: the advantages as they are); logp_old f32
+    [8, S] or None (record mode), logp_out f32 [8, S] or None (written with the current
+    log-probabilities)."""
+    T, _, n = masks.shape
+    S = T * n
+    grad = torch.empty(MASK_DIM, S, dtype=torch.float32, device=pu.device)
+    part = torch.empty(NA, -(-S // 256), 4 if ppo else 2, dtype=torch.float64, device=pu.device)
+    pu_c = pu.detach().contiguous()
+    V = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    head = (V(pu_c), int(pu_c.shape[2]), V(g.inv), T, n, V(masks), V(actions), V(adv), V(adv_mean), V(adv_std))
+    tail = (1.0 / count, coef, V(grad), V(part), ctypes.c_void_p(torch.cuda.current_stream(pu.device).cuda_stream))
+    if ppo:
+        logp_old, logp_out, clip_eps = ppo
+        for t in (logp_old, logp_out):
+            assert t is None or (t.is_contiguous() and t.shape == (NA, S) and t.dtype == torch.float32)
+        nat.check(nat.lib().fjsp_a2c_actor_head_ppo(*head, V(logp_old), V(logp_out), float(clip_eps), *tail))
+    else:
+        nat.check(nat.lib().fjsp_a2c_actor_head(*head, *tail))
+    sums = part.sum(1)
+    ctx.g = g
+    ctx.save_for_backward(grad)
+    return ((-sums[:, 0] - coef * sums[:, 1]) / count).float(), sums
+
+
+def actor_head_backward(ctx, gl, nin):
+    """The backward of both loss-head Functions (nin forward operands): the per-sample gradients
+    summed per group (runs of the sorted order) for the 29 valid (agent, action) rows only: a
+    padded action's probability is an exact 0 out of the softmax, so its gradient is never used
+    (left 0)."""
+    (grad,) = ctx.saved_tensors
+    return (actor_head_group_grads(grad, ctx.g, gl),) + (None,) * (nin - 1)
+
+
 class _ActorHead(torch.autograd.Function):
-    """Per-agent actor losses of A2CLosses from the agents' per-group probabilities pu [8, 8,
-    Umax] (RowGroups g), computed with their per-sample gradient by one HIP kernel; backward:
-    the per-sample gradients summed per group (runs of the sorted order) for the 29 valid
-    (agent, action) rows only: a padded action's probability is an exact 0 out of the softmax,
-    so its gradient is never used (left 0)."""
+    """Per-agent actor losses of A2CLosses, computed with their per-sample gradient by one HIP
+    kernel (actor_head_forward / actor_head_backward)."""
 
     @staticmethod
     def forward(ctx, pu, g, masks, actions, adv, adv_mean, adv_std, count, coef):
-        """masks int8 [T, 29, n], actions u8 [T, 8, n], adv f64 [T, 8, n] (the slab's layouts),
-        adv_mean / adv_std f32 [8] (None: the advantages as they are)."""
-        T, _, n = masks.shape
-        S = T * n
-        grad = torch.empty(MASK_DIM, S, dtype=torch.float32, device=pu.device)
-        part = torch.empty(NA, -(-S // 256), 2, dtype=torch.float64, device=pu.device)
-        pu_c = pu.detach().contiguous()
-        stream = torch.cuda.current_stream(pu.device).cuda_stream
-        V = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        nat.check(nat.lib().fjsp_a2c_actor_head(V(pu_c), int(pu_c.shape[2]), V(g.inv), T, n, V(masks), V(actions),
-                                                V(adv), V(adv_mean), V(adv_std), 1.0 / count, coef, V(grad), V(part),
-                                                ctypes.c_void_p(stream)))
-        sums = part.sum(1)
-        ctx.g = g
-        ctx.save_for_backward(grad)
-        return ((-sums[:, 0] - coef * sums[:, 1]) / count).float()
+        return actor_head_forward(ctx, pu, g, masks, actions, adv, adv_mean, adv_std, count, coef)[0]
 
     @staticmethod
     def backward(ctx, gl):
-        (grad,) = ctx.saved_tensors
-        return actor_head_group_grads(grad, ctx.g, gl), None, None, None, None, None, None, None, None
+        return actor_head_backward(ctx, gl, 9)
 
 
 def actor_head_group_grads(grad, g, gl):
@@ -904,14 +924,107 @@ def cols_of_rows(rows, gidx):
     return cols
 
 
-def cols_of_states(gt, gidx):
-    """ActorStack.forward_rows' cols from the global states as feature rows gt f32 [38, S]."""
-    def cols(agents, idx):                                   # [k, 13, u] from gt
-        k, u = idx.shape
-        c = gt[:, idx.reshape(-1)].view(GLOBAL_DIM, k, u)
-        c = torch.cat([c, c.new_zeros(1, k, u)])
-        return c[gidx[agents], torch.arange(k, device=idx.device)[:, None], :]
-    return cols
+class UpdateBatch:
+    """One batch prepared for its update (A2CLosses.compute: one; ppo_vec.PPOBatch: several epochs):
+    everything that depends on the batch alone and not on the weights.  Here: the key pass,
+    grouping and verification (dedup; two host synchronisations) and the critic's inputs (the
+    distinct global states and their loss coefficients).  On first use, then kept: the groups'
+    representative inputs of the actors, and on the dense / CPU path the [8, S] masks, actions
+    and normalised advantages (the GPU's grouped loss head reads the slabs in place).
+
+    The rollout slab's layouts: feats f32 [T, 38, N], masks int8 [T, 29, N], actions u8 [T, 8, N],
+    ret / adv f64 [T, 8, N] (a single step may drop the T axis; CPU tensors work).  adv_mean /
+    adv_std f32 [8] and count are the GLOBAL statistics of FloatTensor(adv) (a2c.py:724-731)."""
+
+    def __init__(self, feats, masks, actions, ret, adv, gidx, midx, dedup, adv_mean, adv_std, count):
+        f3, masks, actions, ret, adv = (t if t.dim() == 3 else t[None] for t in (feats, masks, actions, ret, adv))
+        f3 = f3.contiguous()
+        T, _, n = f3.shape
+        S = T * n
+        self.T, self.n, self.S, self.cuda = T, n, S, f3.is_cuda
+        self.count, self.mean, self.std, self.norm = count, adv_mean, adv_std, count > 1
+        self.f3, self.gidx, self.midx = f3, gidx, midx
+        self.masks, self.actions, self.adv = masks.contiguous(), actions.contiguous(), adv.contiguous()
+        self.x = self.reps = self.m = None
+        ga = gc = rows = gt = None
+        if dedup:
+            rows = torch.empty(S, GROUP_ROW, dtype=torch.float32, device=f3.device) if self.cuda else None
+            gr = RowGroups(group_keys(f3, rows), STATION_ROWS)      # 8 actor rows + the critic's
+            ga, gc = gr.rows(0, NA), gr.rows(NA, NA + 1)
+            if not self.cuda:
+                self.x, gt = actor_inputs(f3, gidx), f3.permute(1, 0, 2).reshape(GLOBAL_DIM, S)
+            if not group_verify(f3, ga, gc, self.x, gt, rows):      # a hash collision: dense
+                ga = gc = None
+        self.ga, self.gc = ga, gc
+        # with a verified grouping on the GPU the loss head is one kernel on the slabs, and the
+        # groups' representatives are gathered as whole sample-major rows (160 B each) of the keys
+        # pass's rows: no [38, S] copy of the slab, no 38 scattered words per column
+        self.head_kernel = ga is not None and self.cuda
+        self.rows = rows
+        if not self.head_kernel and gt is None:
+            gt = f3.permute(1, 0, 2).reshape(GLOBAL_DIM, S)         # the states as feature rows: one copy
+        # the critic's inputs: the distinct global states (with their loss coefficients on the
+        # grouped GPU path), else every sample's state
+        self.coef = None
+        if gc is not None and self.cuda and gc.gsorted is not None:
+            self.xc = rows.index_select(0, gc.first[0])
+            self.coef = critic_coef(gc, ret, count)
+        elif gc is not None:
+            # the CPU, or a GPU batch of >= 2^31 key elements (RowGroups' torch grouping)
+            self.xc = rows.index_select(0, gc.first[0])[:, :GLOBAL_DIM] if self.cuda else gt[:, gc.first[0]].t()
+        else:
+            self.xc = gt.t()
+        if self.coef is None:
+            self.r32 = ret.float()
+
+    def critic_loss(self, critic):
+        """calc_critic_loss (a2c.py:713-722): the MSE against the fixed returns."""
+        if self.coef is not None:
+            return critic_onepass(critic, self.xc, self.coef)
+        v = mlp_forward(critic.net, self.xc)
+        if self.gc is not None:
+            v = self.gc.gather(v.reshape(1, 1, -1))
+        return ((v.reshape(self.T, 1, self.n) - self.r32) ** 2).sum() / (NA * self.count)
+
+    def actor_probs(self, actors):
+        """The actors' probabilities for the loss head: per group of ga [8, 8, Umax] for the head
+        kernel, else per sample [8, 8, S] (each network once per distinct input when grouped)."""
+        if not self.head_kernel and self.x is None:
+            self.x = actor_inputs(self.f3, self.gidx)                # [8, 13, S]
+        if self.ga is None:
+            return actors(self.x)
+        if self.reps is None:
+            cols = cols_of_rows(self.rows, self.gidx) if self.head_kernel else None
+            self.reps = ActorStack.rep_inputs(self.x, self.ga, cols)
+        pu = actors.forward_reps(*self.reps)
+        return pu if self.head_kernel else self.ga.gather(pu)
+
+    def head_stats(self):
+        """The loss head's (adv_mean, adv_std): None, None for a single sample (no normalisation)."""
+        return (self.mean, self.std) if self.norm else (None, None)
+
+    def dense_operands(self):
+        """The torch loss heads' (float masks [8, 8, S], actions long [8, S], normalised advantages
+        f32 [8, S])."""
+        if self.m is None:
+            S = self.S
+            self.m = agent_masks(self.masks, self.midx)
+            self.acts = self.actions.long().permute(1, 0, 2).reshape(NA, S)
+            adv32 = self.adv.float().permute(1, 0, 2).reshape(NA, S)   # calc_actor_loss: FloatTensor(adv)
+            self.adv_n = (adv32 - self.mean[:, None]) / (self.std[:, None] + 1e-8) if self.norm else adv32
+        return self.m, self.acts, self.adv_n
+
+    def actor_losses(self, actors, entropy_coef):
+        """calc_actor_loss per agent (a2c.py:705-731) -> f32 [8]."""
+        probs = self.actor_probs(actors)
+        if self.head_kernel:
+            # the loss head and its gradient in one kernel (fjsp_a2c_actor_head), on the slabs
+            return _ActorHead.apply(probs, self.ga, self.masks, self.actions, self.adv, *self.head_stats(),
+                                    float(self.count), float(entropy_coef))
+        m, acts, adv_n = self.dense_operands()
+        ent = entropy_of(probs)                                      # [8, S]
+        logp = categorical_log_prob(masked_probs(probs, m), acts)    # [8, S]
+        return -(adv_n * logp).sum(dim=1) / self.count - entropy_coef * ent.sum(dim=1) / self.count
 
 
 class A2CLosses:
@@ -932,79 +1045,13 @@ class A2CLosses:
 
     @staticmethod
     def compute(actors, critic, feats, masks, actions, returns, adv, gidx, midx, entropy_coef,
-                adv_mean, adv_std, count, dedup=False, groups=None):
-        """The rollout slab's layouts: feats f32 [T, 38, N], masks int8 [T, 29, N], actions u8
-        [T, 8, N], returns / adv f64 [T, 8, N] (a single step may drop the T axis).  groups =
-        (ga, gc): a verified grouping computed by the caller; else dedup groups here (keys, sort,
-        check: two host synchronisations).  On the GPU the grouped path's loss head reads actions
-        and advantages in the slab layouts; [8, S] copies are made for the dense / CPU path only."""
-        f3 = feats if feats.dim() == 3 else feats[None]
-        m3 = masks if masks.dim() == 3 else masks[None]
-        a3 = actions if actions.dim() == 3 else actions[None]
-        r3 = returns if returns.dim() == 3 else returns[None]
-        d3 = adv if adv.dim() == 3 else adv[None]
-        T, _, n = f3.shape
-        S = T * n
-        ga = gc = None
-        rows = None
-        if groups is not None:
-            ga, gc = groups
-        elif dedup:
-            f3 = f3.contiguous()
-            rows = torch.empty(S, GROUP_ROW, dtype=torch.float32, device=f3.device) if f3.is_cuda else None
-            gr = RowGroups(group_keys(f3, rows), STATION_ROWS)      # 8 actor rows + the critic's
-            ga, gc = gr.rows(0, NA), gr.rows(NA, NA + 1)
-            x = gv = None
-            if not feats.is_cuda:
-                x, gv = actor_inputs(feats, gidx), f3.permute(1, 0, 2).reshape(GLOBAL_DIM, S)
-            if not group_verify(f3, ga, gc, x, gv, rows):           # a hash collision: dense
-                ga = gc = None
-
-        if ga is not None and feats.is_cuda:
-            # the groups' representatives gathered as whole sample-major rows (160 B each) of the
-            # keys pass's rows: no [38, S] copy of the slab, no 38 scattered words per column
-            if rows is None:
-                rows = feature_rows(f3)
-            cols = cols_of_rows(rows, gidx)
-        else:
-            # the global states as feature rows [38, S]: one copy of the slab, then row-wise
-            # gathers of the groups' representatives
-            gt = f3.permute(1, 0, 2).reshape(GLOBAL_DIM, S)
-            cols = cols_of_states(gt, gidx)
-        # the critic first: its GEMMs keep the GPU busy while the host issues the actors' many
-        # small launches (after the grouping's host synchronisations the queue is empty)
-        critic_loss = None
-        if gc is not None and feats.is_cuda and gc.gsorted is not None:
-            critic_loss = critic_onepass(critic, rows.index_select(0, gc.first[0]), critic_coef(gc, r3, count))
-            v = None
-        elif gc is not None:
-            # the CPU, or a GPU batch of >= 2^31 key elements (RowGroups' torch grouping)
-            xu = rows.index_select(0, gc.first[0])[:, :GLOBAL_DIM] if feats.is_cuda else gt[:, gc.first[0]].t()
-            v = gc.gather(mlp_forward(critic.net, xu).reshape(1, 1, -1)).reshape(-1)   # [S]
-        else:
-            v = mlp_forward(critic.net, gt.t()).reshape(-1)
-        norm = count > 1
-        if ga is not None and feats.is_cuda:
-            # the loss head and its gradient in one kernel (fjsp_a2c_actor_head), on the slabs
-            actor_losses = _ActorHead.apply(actors.forward_rows(None, ga, cols), ga, m3.contiguous(), a3.contiguous(),
-                                            d3.contiguous(), adv_mean if norm else None, adv_std if norm else None,
-                                            float(count), float(entropy_coef))
-        else:
-            x = actor_inputs(feats, gidx)                            # [8, 13, S]
-            acts = a3.long().permute(1, 0, 2).reshape(NA, S)
-            adv32 = d3.float().permute(1, 0, 2).reshape(NA, S)        # calc_actor_loss: FloatTensor(adv)
-            adv_n = (adv32 - adv_mean[:, None]) / (adv_std[:, None] + 1e-8) if norm else adv32
-            if ga is not None:
-                probs = ga.gather(actors.forward_rows(x, ga, cols))  # [8, 8, S]
-            else:
-                probs = actors(x)                                    # [8, 8, S]
-            ent = entropy_of(probs)                                  # [8, S]
-            pm = masked_probs(probs, agent_masks(masks, midx))
-            logp = categorical_log_prob(pm, acts)                    # [8, S]
-            actor_losses = -(adv_n * logp).sum(dim=1) / count - entropy_coef * ent.sum(dim=1) / count
-        if critic_loss is None:
-            critic_loss = ((v.view(T, 1, n) - r3.float()) ** 2).sum() / (NA * count)
-        return actor_losses, critic_loss
+                adv_mean, adv_std, count, dedup=False):
+        """(actor losses f32 [8], critic loss) of one batch (UpdateBatch's layouts).  The critic
+        first: its GEMMs keep the GPU busy while the host issues the actors' many small launches
+        (after the grouping's host synchronisations the queue is empty)."""
+        batch = UpdateBatch(feats, masks, actions, returns, adv, gidx, midx, dedup, adv_mean, adv_std, count)
+        critic_loss = batch.critic_loss(critic)
+        return batch.actor_losses(actors, entropy_coef), critic_loss
 
 
 def clip_per_agent_(actors, max_norm):
@@ -1016,6 +1063,17 @@ def clip_per_agent_(actors, max_norm):
     for g in grads:
         g.mul_(coef.view(NA, *([1] * (g.dim() - 1))))
     return norm
+
+
+def clip_and_step(actors, critic, optim_actor, optim_critic, max_grad_norm, grad_probe=None):
+    """Every update's tail on the (reduced) gradients (a2c.py:675-691): grad_probe(flat f32 grads)
+    when given, each actor's and the critic's norm clipped, both Adam steps."""
+    if grad_probe is not None:
+        grad_probe(flat_grads(actors, critic).detach().clone())
+    clip_per_agent_(actors, max_grad_norm)
+    torch.nn.utils.clip_grad_norm_(critic.parameters(), max_grad_norm)
+    optim_actor.step()
+    optim_critic.step()
 
 
 # ---------------------------------------------------------------- fused policy kernel weights
@@ -1115,24 +1173,18 @@ def flat_grads(actors, critic):
 
 
 def update_core(actors, critic, optim_actor, optim_critic, feats, masks, actions, ret, adv, gidx, midx,
-                entropy_coef, max_grad_norm, group=None, dedup=False, grad_probe=None, groups=None):
+                entropy_coef, max_grad_norm, group=None, dedup=False, grad_probe=None):
     """update_step without the final host copies: returns the (all-reduced) actor losses [8] and
-    critic loss [1] as device tensors.  With groups (a verified grouping) and no group / probe it
-    issues no host synchronisation, so a graph can capture it."""
+    critic loss [1] as device tensors."""
     from . import distributed as D
     count, mean, std = D.adv_stats_slab(adv, group)                  # of FloatTensor(adv), a2c.py:724-731
     optim_actor.zero_grad(set_to_none=True)
     optim_critic.zero_grad(set_to_none=True)
     actor_losses, critic_loss = A2CLosses.compute(actors, critic, feats, masks, actions, ret, adv, gidx, midx,
-                                                  entropy_coef, mean, std, count, dedup, groups)
+                                                  entropy_coef, mean, std, count, dedup)
     (actor_losses.sum() + critic_loss).backward()
     D.allreduce_grads(list(actors.parameters()) + list(critic.parameters()), group)
-    if grad_probe is not None:
-        grad_probe(flat_grads(actors, critic).detach().clone())
-    clip_per_agent_(actors, max_grad_norm)
-    torch.nn.utils.clip_grad_norm_(critic.parameters(), max_grad_norm)
-    optim_actor.step()
-    optim_critic.step()
+    clip_and_step(actors, critic, optim_actor, optim_critic, max_grad_norm, grad_probe)
     al = D.allreduce_sum(actor_losses.detach(), group)
     cl = D.allreduce_sum(critic_loss.detach().view(1), group)
     return al, cl

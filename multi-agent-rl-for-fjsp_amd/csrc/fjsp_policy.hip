@@ -1665,25 +1665,112 @@ __global__ void __launch_bounds__(256) k_shard_keys(const uint64_t* __restrict__
     if (__syncthreads_or(nb) && threadIdx.x == 0) bad[blockIdx.x] = 1;
 }
 
-// The actor loss head of the grouped A2C update for one (agent, sample): the reference's
-// entropy, masked renormalisation / uniform fallback, Categorical log-prob and actor loss
-// (a2c.py:204-220, 705-731; a2c_vec.A2CLosses) and its gradient with respect to the sample's
-// eight probabilities, which are read from the agent's distinct-input outputs through inv.
-// L = sum over agents of -(sum adv_n logp) / count - c (sum entropy) / count; per (a, s):
+// ---- the actor loss heads: k_actor_head<false> (A2C), k_actor_head<true> (PPO) and k_record_head
+// (the shard learner's records).  All three are head_core, the per-sample arithmetic written
+// once, between their own loads (where p, m, act and adv come from), their dL / dlogp and their
+// stores, and block_sums, the workgroup's partial sums.  -ffp-contract=off: the inlined core
+// rounds as the written-out kernels did, so the heads agree bit for bit where their operands do
+// (tests/test_gpu_ppo.py, test_gpu_a2c.py).
+
+// One sample of one agent: the reference's entropy, masked renormalisation / uniform fallback and
+// Categorical log-prob (a2c.py:204-220, 705-731; a2c_vec.A2CLosses) of its eight probabilities p
+// under the float mask m and the taken action act, and g[j] = dL / dp_j for a loss whose entropy
+// term is es * entropy (es = -c / count, times the record's sample count in k_record_head) and
+// whose policy term has the gradient dlogp(logp) = dL / dlogp.
+template <class DLogp>
+__device__ __forceinline__ void head_core(const float (&p)[8], const float (&m)[8], int act, float es, DLogp dlogp,
+                                          float (&g)[8], float& ent, float& logp) {
+    // entropy and its gradient
+    ent = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const float pe = p[j] + 1e-10f;
+        ent += p[j] * logf(pe);
+        g[j] = es * -(logf(pe) + p[j] / pe);
+    }
+    ent = -ent;
+    // masked probabilities: p m / sum(p m), or m / sum(m) when nothing valid is left
+    float sr = 0.0f, sm = 0.0f, pm[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) { sr += p[j] * m[j]; sm += m[j]; }
+#pragma unroll
+    for (int j = 0; j < 8; j++) pm[j] = sr > 0.0f ? (p[j] * m[j]) / sr : m[j] / sm;
+    float s2 = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 8; j++) s2 += pm[j];
+    float qa = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 8; j++) qa = j == act ? pm[j] / s2 : qa;
+    const float eps = 1.1920928955078125e-07f;
+    const float qc = fminf(fmaxf(qa, eps), 1.0f - eps);
+    logp = logf(qc);
+    // dL / dlogp through the clamp (inclusive), q = pm / s2, pm = p m / sr
+    const float gl = dlogp(logp);   // every sample: the PPO head's callable also stores and keeps its terms
+    const float gq = (qa >= eps && qa <= 1.0f - eps) ? gl / qc : 0.0f;
+    if (sr > 0.0f) {
+        float gpm[8], dot = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            gpm[j] = (j == act ? gq / s2 : 0.0f) - gq * qa / s2;   // d q_act / d pm_j
+            dot += gpm[j] * (p[j] * m[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; j++) g[j] += m[j] * (gpm[j] / sr - dot / (sr * sr));
+    }
+}
+
+// dst[k] = the 256-thread workgroup's sum of acc[k]: within each wave by shuffles, the four waves
+// through LDS, one partial K-tuple per workgroup (no atomics: ~16 000 workgroups per agent adding
+// into one address serialise).
+template <int K>
+__device__ __forceinline__ void block_sums(double (&acc)[K], double* __restrict__ dst) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < K; k++) acc[k] += __shfl_xor(acc[k], off);
+    }
+    __shared__ double s_part[4][K];
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < K; k++) s_part[threadIdx.x >> 6][k] = acc[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < K)
+        dst[threadIdx.x] = s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x];
+}
+
+// The loss head of the grouped update for one (agent, sample), the probabilities read from the
+// agent's distinct-input outputs through inv, with its gradient:
 //   grad[mask_off[a] + j][s] = dL / dp_j for the agent's valid actions j < nact[a] (29 rows: a
-//   padded action's probability is an exact 0 out of the softmax, its gradient is never used);
-//   sums[a][block] = the workgroup's (adv_n logp, entropy) sums.
+//   padded action's probability is an exact 0 out of the softmax, its gradient is never used).
+// A2C (PPO = false; logp_old, logp_out and clip_eps unused): L = sum over agents of
+// -(sum adv_n logp) / count - c (sum entropy) / count; sums[a][block] = the workgroup's
+// (adv_n logp, entropy) sums.
+// PPO (ppo_vec.ppo_update; an extension, the reference has A2C only): one more per-sample
+// operand, the behaviour policy's log-probability, and the clipped surrogate in place of
+// adv_n logp.  r = exp(logp - logp_old) (1 in record mode: logp_old NULL), rc = clamp(r, 1 -
+// eps_c, 1 + eps_c), surr = min(r adv, rc adv), L = sum over agents of -(sum surr) / count -
+// c (sum entropy) / count.  d surr / d logp = r adv unless the clip holds the sample (adv > 0 and
+// r > 1 + eps_c, or adv < 0 and r < 1 - eps_c), which is autograd's gradient of min(r adv,
+// clamp(r) adv) (a tie halves, clamp passes at its inclusive bounds).
+//   logp_out[a][s] = logp when given (record mode's output, the later epochs' logp_old);
+//   sums[a][block] = the workgroup's (surr, entropy, (r - 1) - (logp - logp_old) = the
+//   approximate KL term, clipped count) sums.
+template <bool PPO>
 __global__ void __launch_bounds__(256) k_actor_head(const float* __restrict__ pu, int umax,
                                                     const int64_t* __restrict__ inv, int T, int n,
                                                     const int8_t* __restrict__ masks,
                                                     const uint8_t* __restrict__ actions,
                                                     const double* __restrict__ advs, const float* __restrict__ adv_mean,
-                                                    const float* __restrict__ adv_std, float inv_count, float ent_coef,
+                                                    const float* __restrict__ adv_std,
+                                                    const float* __restrict__ logp_old, float* __restrict__ logp_out,
+                                                    float clip_eps, float inv_count, float ent_coef,
                                                     float* __restrict__ grad, double* __restrict__ sums) {
+    constexpr int K = PPO ? 4 : 2;
     const int a = blockIdx.y;
     const size_t S = (size_t)T * n;
     const size_t s = (size_t)blockIdx.x * 256 + threadIdx.x;
-    double sl = 0.0, se = 0.0;
+    double acc[K] = {};
     if (s < S) {
         const size_t t = s / (size_t)n, e = s - t * (size_t)n;
         const size_t u = (size_t)inv[(size_t)a * S + s];
@@ -1699,189 +1786,51 @@ __global__ void __launch_bounds__(256) k_actor_head(const float* __restrict__ pu
             p[j] = pu[((size_t)a * 8 + j) * umax + u];
             m[j] = j < na ? (float)masks[(t * 29 + mo + j) * n + e] : 0.0f;
         }
-        // entropy and its gradient
-        float ent = 0.0f, g[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const float pe = p[j] + 1e-10f;
-            ent += p[j] * logf(pe);
-            g[j] = -ent_coef * inv_count * -(logf(pe) + p[j] / pe);
-        }
-        ent = -ent;
-        // masked probabilities: p m / sum(p m), or m / sum(m) when nothing valid is left
-        float sr = 0.0f, sm = 0.0f, pm[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) { sr += p[j] * m[j]; sm += m[j]; }
-#pragma unroll
-        for (int j = 0; j < 8; j++) pm[j] = sr > 0.0f ? (p[j] * m[j]) / sr : m[j] / sm;
-        float s2 = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 8; j++) s2 += pm[j];
-        float qa = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 8; j++) qa = j == act ? pm[j] / s2 : qa;
-        const float eps = 1.1920928955078125e-07f;
-        const float qc = fminf(fmaxf(qa, eps), 1.0f - eps);
-        const float logp = logf(qc);
-        // d L / d logp = -adv / count; through clamp (inclusive), q = pm / s2, pm = p m / sr
-        const float gq = (qa >= eps && qa <= 1.0f - eps) ? (-adv * inv_count) / qc : 0.0f;
-        if (sr > 0.0f) {
-            float gpm[8], dot = 0.0f;
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                gpm[j] = (j == act ? gq / s2 : 0.0f) - gq * qa / s2;   // d q_act / d pm_j
-                dot += gpm[j] * (p[j] * m[j]);
+        float g[8], ent, logp, surr = 0.0f, r = 1.0f, dlp = 0.0f;
+        bool clipped = false;
+        head_core(p, m, act, -ent_coef * inv_count, [&](float lp) {
+            if constexpr (PPO) {
+                // the ratio to the behaviour policy and the clipped surrogate
+                const size_t as = (size_t)a * S + s;
+                dlp = logp_old ? lp - logp_old[as] : 0.0f;
+                r = logp_old ? expf(dlp) : 1.0f;
+                if (logp_out) logp_out[as] = lp;
+                const float lo = 1.0f - clip_eps, hi = 1.0f + clip_eps;
+                const float rc = fminf(fmaxf(r, lo), hi);
+                surr = fminf(r * adv, rc * adv);
+                clipped = (adv > 0.0f && r > hi) || (adv < 0.0f && r < lo);
+                return clipped ? 0.0f : (-adv * inv_count) * r;   // -adv r / count unless clipped
+            } else {
+                return -adv * inv_count;
             }
-#pragma unroll
-            for (int j = 0; j < 8; j++) g[j] += m[j] * (gpm[j] / sr - dot / (sr * sr));
-        }
+        }, g, ent, logp);
 #pragma unroll
         for (int j = 0; j < 8; j++)
             if (j < na) grad[(size_t)(mo + j) * S + s] = g[j];   // valid actions only (rows mo..mo+na)
-        sl = (double)(adv * logp);
-        se = (double)ent;
-    }
-    // the workgroup's sums, one partial pair per workgroup (no atomics: ~16 000 workgroups per
-    // agent adding into one address serialise)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        sl += __shfl_xor(sl, off);
-        se += __shfl_xor(se, off);
-    }
-    __shared__ double s_part[4][2];
-    if ((threadIdx.x & 63) == 0) { s_part[threadIdx.x >> 6][0] = sl; s_part[threadIdx.x >> 6][1] = se; }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        const double v = s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x];
-        sums[((size_t)a * gridDim.x + blockIdx.x) * 2 + threadIdx.x] = v;
-    }
-}
-
-// The PPO loss head (ppo_vec.ppo_update; an extension, the reference has A2C only): k_actor_head's
-// pass with one more per-sample operand, the behaviour policy's log-probability, and the clipped
-// surrogate in place of adv_n logp.  p, m, entropy, pm, s2, qa, qc and logp are k_actor_head's,
-// the same operations in the same order.  r = exp(logp - logp_old) (1 in record mode: logp_old
-// NULL), rc = clamp(r, 1 - eps_c, 1 + eps_c), surr = min(r adv, rc adv), L = sum over agents of
-// -(sum surr) / count - c (sum entropy) / count.  d surr / d logp = r adv unless the clip holds
-// the sample (adv > 0 and r > 1 + eps_c, or adv < 0 and r < 1 - eps_c), which is autograd's
-// gradient of min(r adv, clamp(r) adv) (a tie halves, clamp passes at its inclusive bounds).
-//   logp_out[a][s] = logp when given (record mode's output, the later epochs' logp_old);
-//   grad as k_actor_head; sums[a][block] = the workgroup's (surr, entropy, (r - 1) - (logp -
-//   logp_old) = the approximate KL term, clipped count) sums.
-__global__ void __launch_bounds__(256) k_actor_head_ppo(const float* __restrict__ pu, int umax,
-                                                        const int64_t* __restrict__ inv, int T, int n,
-                                                        const int8_t* __restrict__ masks,
-                                                        const uint8_t* __restrict__ actions,
-                                                        const double* __restrict__ advs,
-                                                        const float* __restrict__ adv_mean,
-                                                        const float* __restrict__ adv_std,
-                                                        const float* __restrict__ logp_old,
-                                                        float* __restrict__ logp_out, float clip_eps, float inv_count,
-                                                        float ent_coef, float* __restrict__ grad,
-                                                        double* __restrict__ sums) {
-    const int a = blockIdx.y;
-    const size_t S = (size_t)T * n;
-    const size_t s = (size_t)blockIdx.x * 256 + threadIdx.x;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    if (s < S) {
-        const size_t t = s / (size_t)n, e = s - t * (size_t)n;
-        const size_t u = (size_t)inv[(size_t)a * S + s];
-        const int na = c_nact[a], mo = c_mask_off[a];
-        const size_t ta = (t * NAG + (size_t)a) * (size_t)n + e;
-        const int act = (int)actions[ta];
-        const float adv = adv_std ? ((float)advs[ta] - adv_mean[a]) / (adv_std[a] + 1e-8f) : (float)advs[ta];
-        float p[8], m[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            p[j] = pu[((size_t)a * 8 + j) * umax + u];
-            m[j] = j < na ? (float)masks[(t * 29 + mo + j) * n + e] : 0.0f;
-        }
-        // entropy and its gradient
-        float ent = 0.0f, g[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const float pe = p[j] + 1e-10f;
-            ent += p[j] * logf(pe);
-            g[j] = -ent_coef * inv_count * -(logf(pe) + p[j] / pe);
-        }
-        ent = -ent;
-        // masked probabilities: p m / sum(p m), or m / sum(m) when nothing valid is left
-        float sr = 0.0f, sm = 0.0f, pm[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) { sr += p[j] * m[j]; sm += m[j]; }
-#pragma unroll
-        for (int j = 0; j < 8; j++) pm[j] = sr > 0.0f ? (p[j] * m[j]) / sr : m[j] / sm;
-        float s2 = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 8; j++) s2 += pm[j];
-        float qa = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 8; j++) qa = j == act ? pm[j] / s2 : qa;
-        const float eps = 1.1920928955078125e-07f;
-        const float qc = fminf(fmaxf(qa, eps), 1.0f - eps);
-        const float logp = logf(qc);
-        // the ratio to the behaviour policy and the clipped surrogate
-        const size_t as = (size_t)a * S + s;
-        const float dlp = logp_old ? logp - logp_old[as] : 0.0f;
-        const float r = logp_old ? expf(dlp) : 1.0f;
-        if (logp_out) logp_out[as] = logp;
-        const float lo = 1.0f - clip_eps, hi = 1.0f + clip_eps;
-        const float rc = fminf(fmaxf(r, lo), hi);
-        const float surr = fminf(r * adv, rc * adv);
-        const bool clipped = (adv > 0.0f && r > hi) || (adv < 0.0f && r < lo);
-        // d L / d logp = -adv r / count unless clipped; through clamp (inclusive), q = pm / s2, pm = p m / sr
-        const float gl = clipped ? 0.0f : (-adv * inv_count) * r;
-        const float gq = (qa >= eps && qa <= 1.0f - eps) ? gl / qc : 0.0f;
-        if (sr > 0.0f) {
-            float gpm[8], dot = 0.0f;
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                gpm[j] = (j == act ? gq / s2 : 0.0f) - gq * qa / s2;   // d q_act / d pm_j
-                dot += gpm[j] * (p[j] * m[j]);
-            }
-#pragma unroll
-            for (int j = 0; j < 8; j++) g[j] += m[j] * (gpm[j] / sr - dot / (sr * sr));
-        }
-#pragma unroll
-        for (int j = 0; j < 8; j++)
-            if (j < na) grad[(size_t)(mo + j) * S + s] = g[j];   // valid actions only (rows mo..mo+na)
-        acc[0] = (double)surr;
+        acc[0] = PPO ? (double)surr : (double)(adv * logp);
         acc[1] = (double)ent;
-        acc[2] = (double)((r - 1.0f) - dlp);
-        acc[3] = clipped ? 1.0 : 0.0;
+        if constexpr (PPO) {
+            acc[2] = (double)((r - 1.0f) - dlp);
+            acc[3] = clipped ? 1.0 : 0.0;
+        }
     }
-    // the workgroup's sums, one partial quadruple per workgroup (no atomics, as k_actor_head)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) acc[k] += __shfl_xor(acc[k], off);
-    }
-    __shared__ double s_part[4][4];
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) s_part[threadIdx.x >> 6][k] = acc[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const double v = s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x];
-        sums[((size_t)a * gridDim.x + blockIdx.x) * 4 + threadIdx.x] = v;
-    }
+    block_sums(acc, sums + ((size_t)a * gridDim.x + blockIdx.x) * K);
 }
 
 // The shard learner's actor loss head over an owner's records (shard_learner.owner_losses): a
 // record stands for n samples of one agent with equal (input, mask, action) and carries w = the
 // f64 sum of their normalised advantages; the samples' loss terms and gradients are linear in the
 // advantage and share everything else, so per record: -(w logp) / count - c n entropy / count, and
-// grad[j][r] = dL / dp_j of the record (k_actor_head's formulas with adv -> w and the entropy
-// weighted by n).  pu [8][umax] = the agent's probabilities per distinct input, inv [R] = each
-// record's input group; info [R] = mask bits | action << 8.
+// grad[j][r] = dL / dp_j of the record (head_core with adv -> w and the entropy weighted by n).
+// pu [8][umax] = the agent's probabilities per distinct input, inv [R] = each record's input
+// group; info [R] = mask bits | action << 8; sums[block] = the workgroup's (w logp, n entropy).
 __global__ void __launch_bounds__(256) k_record_head(const float* __restrict__ pu, int umax,
                                                      const int64_t* __restrict__ inv, int R, int na,
                                                      const int32_t* __restrict__ info, const double* __restrict__ wsum,
                                                      const int32_t* __restrict__ cnt, float inv_count, float ent_coef,
                                                      float* __restrict__ grad, double* __restrict__ sums) {
     const int r = blockIdx.x * 256 + threadIdx.x;
-    double sl = 0.0, se = 0.0;
+    double acc[2] = {};
     if (r < R) {
         const size_t u = (size_t)inv[r];
         const uint32_t w0 = (uint32_t)info[r];
@@ -1894,56 +1843,15 @@ __global__ void __launch_bounds__(256) k_record_head(const float* __restrict__ p
             p[j] = pu[(size_t)j * umax + u];
             m[j] = j < na ? (float)((w0 >> j) & 1u) : 0.0f;
         }
-        float ent = 0.0f, g[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const float pe = p[j] + 1e-10f;
-            ent += p[j] * logf(pe);
-            g[j] = -ent_coef * inv_count * nr * -(logf(pe) + p[j] / pe);
-        }
-        ent = -ent;
-        float sr = 0.0f, sm = 0.0f, pm[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) { sr += p[j] * m[j]; sm += m[j]; }
-#pragma unroll
-        for (int j = 0; j < 8; j++) pm[j] = sr > 0.0f ? (p[j] * m[j]) / sr : m[j] / sm;
-        float s2 = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 8; j++) s2 += pm[j];
-        float qa = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 8; j++) qa = j == act ? pm[j] / s2 : qa;
-        const float eps = 1.1920928955078125e-07f;
-        const float qc = fminf(fmaxf(qa, eps), 1.0f - eps);
-        const float logp = logf(qc);
-        const float gq = (qa >= eps && qa <= 1.0f - eps) ? (-adv * inv_count) / qc : 0.0f;
-        if (sr > 0.0f) {
-            float gpm[8], dot = 0.0f;
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                gpm[j] = (j == act ? gq / s2 : 0.0f) - gq * qa / s2;
-                dot += gpm[j] * (p[j] * m[j]);
-            }
-#pragma unroll
-            for (int j = 0; j < 8; j++) g[j] += m[j] * (gpm[j] / sr - dot / (sr * sr));
-        }
+        float g[8], ent, logp;
+        head_core(p, m, act, -ent_coef * inv_count * nr, [&](float) { return -adv * inv_count; }, g, ent, logp);
 #pragma unroll
         for (int j = 0; j < 8; j++)
             if (j < na) grad[(size_t)j * R + r] = g[j];
-        sl = (double)adv * (double)logp;
-        se = (double)nr * (double)ent;
+        acc[0] = (double)adv * (double)logp;
+        acc[1] = (double)nr * (double)ent;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        sl += __shfl_xor(sl, off);
-        se += __shfl_xor(se, off);
-    }
-    __shared__ double s_part[4][2];
-    if ((threadIdx.x & 63) == 0) { s_part[threadIdx.x >> 6][0] = sl; s_part[threadIdx.x >> 6][1] = se; }
-    __syncthreads();
-    if (threadIdx.x < 2)
-        sums[(size_t)blockIdx.x * 2 + threadIdx.x] =
-            s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x];
+    block_sums(acc, sums + (size_t)blockIdx.x * 2);
 }
 
 // The grouping check of the A2C update (a2c_vec.A2CLosses, replaces the torch gather-and-compare
@@ -2090,7 +1998,15 @@ __global__ void __launch_bounds__(256) k_value_head_grad(const float* __restrict
 
 }  // namespace
 
-int fjsp_internal_fail(const char* msg);
+int fjsp_internal_fail(const char* msg);   // fjsp_hip.hip: sets fjsp_last_error()
+
+// Every entry's tail after its launches: 0, or -2 with HIP's message in fjsp_last_error().
+static int launch_error() {
+    const hipError_t err = hipGetLastError();
+    if (err == hipSuccess) return 0;
+    fjsp_internal_fail(hipGetErrorString(err));
+    return -2;
+}
 
 // Library-wide variants of the policy launches, set with fjsp_set_option(NULL or any handle,
 // "policy_xmap" | "policy_dedup" | "policy_split", v) (A/B runs and the bit-identity tests; read
@@ -2156,13 +2072,8 @@ int fjsp_internal_policy_step(const float* feats, const int8_t* masks, int32_t n
         if (staged) hipLaunchKernelGGL((k_policy_step<true, false>), grid, dim3(NTHR), 0, stream, A, St);
         else hipLaunchKernelGGL((k_policy_step<false, false>), grid, dim3(NTHR), 0, stream, A, St);
     }
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        fjsp_internal_fail(hipGetErrorString(err));
-        return -2;
-    }
-    return 0;
-}   // fjsp_hip.hip: sets fjsp_last_error()
+    return launch_error();
+}
 
 extern "C" int fjsp_a2c_actor_head(const float* pu, int32_t umax, const int64_t* inv, int32_t T, int32_t n,
                                    const int8_t* masks, const uint8_t* actions, const double* adv, const float* adv_mean,
@@ -2172,14 +2083,10 @@ extern "C" int fjsp_a2c_actor_head(const float* pu, int32_t umax, const int64_t*
     if (!pu || !inv || !masks || !actions || !adv || !grad || !sums || (!adv_mean != !adv_std))
         return fjsp_internal_fail("fjsp_a2c_actor_head: null buffer");
     const size_t S = (size_t)T * (size_t)n;
-    hipLaunchKernelGGL(k_actor_head, dim3((unsigned)((S + 255) / 256), NAG), dim3(256), 0, (hipStream_t)stream, pu, umax,
-                       inv, T, n, masks, actions, adv, adv_mean, adv_std, inv_count, ent_coef, grad, sums);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        fjsp_internal_fail(hipGetErrorString(err));
-        return -2;
-    }
-    return 0;
+    hipLaunchKernelGGL(k_actor_head<false>, dim3((unsigned)((S + 255) / 256), NAG), dim3(256), 0, (hipStream_t)stream, pu,
+                       umax, inv, T, n, masks, actions, adv, adv_mean, adv_std, (const float*)nullptr, (float*)nullptr, 0.0f,
+                       inv_count, ent_coef, grad, sums);
+    return launch_error();
 }
 
 extern "C" int fjsp_a2c_actor_head_ppo(const float* pu, int32_t umax, const int64_t* inv, int32_t T, int32_t n,
@@ -2193,15 +2100,10 @@ extern "C" int fjsp_a2c_actor_head_ppo(const float* pu, int32_t umax, const int6
     if (!pu || !inv || !masks || !actions || !adv || !grad || !sums || (!adv_mean != !adv_std))
         return fjsp_internal_fail("fjsp_a2c_actor_head_ppo: null buffer");
     const size_t S = (size_t)T * (size_t)n;
-    hipLaunchKernelGGL(k_actor_head_ppo, dim3((unsigned)((S + 255) / 256), NAG), dim3(256), 0, (hipStream_t)stream, pu,
+    hipLaunchKernelGGL(k_actor_head<true>, dim3((unsigned)((S + 255) / 256), NAG), dim3(256), 0, (hipStream_t)stream, pu,
                        umax, inv, T, n, masks, actions, adv, adv_mean, adv_std, logp_old, logp_out, clip_eps, inv_count,
                        ent_coef, grad, sums);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        fjsp_internal_fail(hipGetErrorString(err));
-        return -2;
-    }
-    return 0;
+    return launch_error();
 }
 
 extern "C" int fjsp_a2c_group_keys(const float* feats, int32_t T, int32_t n, uint64_t* keys, float* rows,
@@ -2212,12 +2114,7 @@ extern "C" int fjsp_a2c_group_keys(const float* feats, int32_t T, int32_t n, uin
     if (rows && ((uintptr_t)rows & 15u)) return fjsp_internal_fail("fjsp_a2c_group_keys: rows must be 16-byte aligned");
     hipLaunchKernelGGL(k_group_keys, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, (hipStream_t)stream, feats, T, n,
                        keys, rows);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        fjsp_internal_fail(hipGetErrorString(err));
-        return -2;
-    }
-    return 0;
+    return launch_error();
 }
 
 extern "C" int fjsp_a2c_pack_mfma(const float* W, int32_t B, int32_t R, int32_t K, int32_t transposed, float* out,
@@ -2229,12 +2126,7 @@ extern "C" int fjsp_a2c_pack_mfma(const float* W, int32_t B, int32_t R, int32_t 
     const int64_t total = (int64_t)B * (R / 32) * (K / 16) * 128;
     hipLaunchKernelGGL(k_pack_mfma, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W, B, R, K,
                        transposed, reinterpret_cast<__bf16*>(out));
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        fjsp_internal_fail(hipGetErrorString(err));
-        return -2;
-    }
-    return 0;
+    return launch_error();
 }
 
 extern "C" int fjsp_a2c_record_head(const float* pu, int32_t umax, const int64_t* inv, int32_t R, int32_t nact,
@@ -2245,12 +2137,7 @@ extern "C" int fjsp_a2c_record_head(const float* pu, int32_t umax, const int64_t
     if (!pu || !inv || !info || !wsum || !cnt || !grad || !sums) return fjsp_internal_fail("fjsp_a2c_record_head: null buffer");
     hipLaunchKernelGGL(k_record_head, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pu, umax, inv, R,
                        nact, info, wsum, cnt, inv_count, ent_coef, grad, sums);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        fjsp_internal_fail(hipGetErrorString(err));
-        return -2;
-    }
-    return 0;
+    return launch_error();
 }
 
 extern "C" int fjsp_a2c_shard_keys(const uint64_t* keys, const int8_t* masks, const uint8_t* actions, int32_t T,
@@ -2260,12 +2147,7 @@ extern "C" int fjsp_a2c_shard_keys(const uint64_t* keys, const int8_t* masks, co
     const size_t S = (size_t)T * (size_t)n;
     hipLaunchKernelGGL(k_shard_keys, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, (hipStream_t)stream, keys, masks,
                        actions, T, n, tk, info, bad);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        fjsp_internal_fail(hipGetErrorString(err));
-        return -2;
-    }
-    return 0;
+    return launch_error();
 }
 
 extern "C" int fjsp_a2c_group_verify(const float* rows, int32_t T, int32_t n, const int64_t* rep_a,
@@ -2276,12 +2158,7 @@ extern "C" int fjsp_a2c_group_verify(const float* rows, int32_t T, int32_t n, co
     const size_t S = (size_t)T * (size_t)n;
     hipLaunchKernelGGL(k_group_verify, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rows, T,
                        n, rep_a, rep_c, bad);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        fjsp_internal_fail(hipGetErrorString(err));
-        return -2;
-    }
-    return 0;
+    return launch_error();
 }
 
 extern "C" int fjsp_a2c_relu_bias_grad(const float* gy, const float* y, int64_t rows, int32_t cols, float* g,
@@ -2294,12 +2171,7 @@ extern "C" int fjsp_a2c_relu_bias_grad(const float* gy, const float* y, int64_t 
         hipLaunchKernelGGL(k_relu_bias_grad<256>, grid, dim3(256), 0, (hipStream_t)stream, gy, y, rows, g, part);
     else
         hipLaunchKernelGGL(k_relu_bias_grad<128>, grid, dim3(256), 0, (hipStream_t)stream, gy, y, rows, g, part);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        fjsp_internal_fail(hipGetErrorString(err));
-        return -2;
-    }
-    return 0;
+    return launch_error();
 }
 
 extern "C" int fjsp_a2c_value_head_grad(const float* y, const float* gv, const float* w4, int64_t rows, float* g,
@@ -2308,12 +2180,7 @@ extern "C" int fjsp_a2c_value_head_grad(const float* y, const float* gv, const f
     if (!y || !gv || !w4 || !g || !part) return fjsp_internal_fail("fjsp_a2c_value_head_grad: null buffer");
     hipLaunchKernelGGL(k_value_head_grad, dim3((unsigned)((rows + 127) / 128)), dim3(256), 0, (hipStream_t)stream, y,
                        gv, w4, rows, g, part);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        fjsp_internal_fail(hipGetErrorString(err));
-        return -2;
-    }
-    return 0;
+    return launch_error();
 }
 
 #ifdef FJSP_STAMPS
@@ -2338,12 +2205,7 @@ extern "C" int fjsp_a2c_critic_fused(const float* x, int32_t n, const float* cri
     PolicyArgs A{x, nullptr, n, nullptr, critic_w, nullptr, 0u, 0u, 0, nullptr, values, nullptr, (n + TC - 1) / TC, 0};
     const CriticFused F{coef, w3t, w2t, h1, h2, g3, g2, g1, part, loss, values};
     hipLaunchKernelGGL(k_critic_fused, dim3((unsigned)A.nc), dim3(NTHR), 0, (hipStream_t)stream, A, F);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        fjsp_internal_fail(hipGetErrorString(err));
-        return -2;
-    }
-    return 0;
+    return launch_error();
 }
 
 extern "C" int fjsp_a2c_wgrad(const float* g, int32_t m, int64_t ldg, const float* x, int32_t nx, int64_t ldx, int64_t U,
@@ -2382,12 +2244,7 @@ extern "C" int fjsp_a2c_wgrad(const float* g, int32_t m, int64_t ldg, const floa
     }
     hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((m * nout + 255) / 256)), dim3(256), 0, st, part, P, m, npad, nout,
                        out, ldo);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        fjsp_internal_fail(hipGetErrorString(err));
-        return -2;
-    }
-    return 0;
+    return launch_error();
 }
 
 extern "C" int fjsp_a2c_policy(const float* feats, const int8_t* masks, int32_t n, const float* actor_w,
@@ -2402,10 +2259,5 @@ extern "C" int fjsp_a2c_policy(const float* feats, const int8_t* masks, int32_t 
     PolicyArgs A{feats, masks, n, actor_w, critic_w, seed, env_gid0, step, deterministic, actions, values, probs,
                  values ? (n + TC - 1) / TC : 0, actions ? (n + TA - 1) / TA : 0, 0, policy_xmap(), policy_dedup()};
     hipLaunchKernelGGL(k_policy, dim3((unsigned)(A.nc + NAG * A.na)), dim3(NTHR), 0, (hipStream_t)stream, A);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        fjsp_internal_fail(hipGetErrorString(err));
-        return -2;
-    }
-    return 0;
+    return launch_error();
 }

@@ -14,24 +14,23 @@ gradient clipping and Adam (a2c.py:675-679).
     weights that collected the batch), so the first epoch's ratio is exactly 1 and its gradient is
     A2C's;
   * the grouped update's fixed costs depend on the batch's features alone, so they are paid once
-    per batch (PPOBatch): advantage statistics, key pass, grouping and verification, the groups'
-    representative rows, the critic's loss coefficients.  Every epoch reuses them: forward ->
-    losses -> backward -> clipping -> Adam;
-  * on the GPU with a verified grouping the loss head is one HIP kernel (fjsp_a2c_actor_head_ppo,
-    csrc/fjsp_policy.hip); everywhere else (the CPU, dedup=False, a hash collision) it is the torch
-    ops of ppo_head_terms, the readable specification.
+    per batch (PPOBatch, the A2C update's a2c_vec.UpdateBatch kept over the epochs): advantage
+    statistics, key pass, grouping and verification, the groups' representative rows, the
+    critic's loss coefficients.  Every epoch reuses them: forward -> losses -> backward ->
+    a2c_vec.clip_and_step;
+  * on the GPU with a verified grouping the loss head is one HIP kernel (fjsp_a2c_actor_head_ppo:
+    the A2C head's kernel, k_actor_head in csrc/fjsp_policy.hip, instantiated with the ratio and
+    clip as its dL / dlogp); everywhere else (the CPU, dedup=False, a hash collision) it is the
+    torch ops of ppo_head_terms, the readable specification.
 
 Out of scope: minibatches (a subset of a group's samples would need per-sample weights in the run
 sums), value-loss clipping, graph capture of the update, multi-GPU exchanges.
 """
-import ctypes
-
 import numpy as np
 import torch
 
-from . import _native as nat
 from . import a2c_vec as A
-from .a2c_vec import NA, MASK_DIM, GLOBAL_DIM, GROUP_ROW
+from .a2c_vec import NA
 from .spec import AGENTS
 
 
@@ -58,137 +57,56 @@ def ppo_head_terms(probs, m, acts, adv_n, logp_old, clip_eps):
 
 
 class _ActorHeadPPO(torch.autograd.Function):
-    """a2c_vec._ActorHead's twin for the clipped objective (fjsp_a2c_actor_head_ppo): the per-agent
-    PPO actor losses from the agents' per-group probabilities pu [8, 8, Umax] with their per-sample
-    gradient by one HIP kernel; backward: the same run sums.  Also returns stats f64 [8, 3] = per
-    agent the sums of the entropy, of the KL terms and the number of clipped samples (not
-    differentiable)."""
+    """a2c_vec._ActorHead for the clipped objective, over the same launch helper
+    (a2c_vec.actor_head_forward with the three PPO operands: fjsp_a2c_actor_head_ppo).  Also returns
+    stats f64 [8, 3] = per agent the sums of the entropy, of the KL terms and the number of clipped
+    samples (not differentiable)."""
 
     @staticmethod
     def forward(ctx, pu, g, masks, actions, adv, adv_mean, adv_std, logp_old, logp_out, clip_eps, count, coef):
-        """masks int8 [T, 29, n], actions u8 [T, 8, n], adv f64 [T, 8, n] (the slab's layouts),
-        adv_mean / adv_std f32 [8] or None, logp_old f32 [8, S] or None (record mode), logp_out f32
-        [8, S] or None (written with the current log-probabilities)."""
-        T, _, n = masks.shape
-        S = T * n
-        grad = torch.empty(MASK_DIM, S, dtype=torch.float32, device=pu.device)
-        part = torch.empty(NA, -(-S // 256), 4, dtype=torch.float64, device=pu.device)
-        pu_c = pu.detach().contiguous()
-        for t in (logp_old, logp_out):
-            assert t is None or (t.is_contiguous() and t.shape == (NA, S) and t.dtype == torch.float32)
-        stream = torch.cuda.current_stream(pu.device).cuda_stream
-        V = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        nat.check(nat.lib().fjsp_a2c_actor_head_ppo(V(pu_c), int(pu_c.shape[2]), V(g.inv), T, n, V(masks), V(actions),
-                                                    V(adv), V(adv_mean), V(adv_std), V(logp_old), V(logp_out),
-                                                    float(clip_eps), 1.0 / count, coef, V(grad), V(part),
-                                                    ctypes.c_void_p(stream)))
-        sums = part.sum(1)
-        ctx.g = g
-        ctx.save_for_backward(grad)
+        losses, sums = A.actor_head_forward(ctx, pu, g, masks, actions, adv, adv_mean, adv_std, count, coef,
+                                            (logp_old, logp_out, clip_eps))
         stats = sums[:, 1:].contiguous()
         ctx.mark_non_differentiable(stats)
-        return ((-sums[:, 0] - coef * sums[:, 1]) / count).float(), stats
+        return losses, stats
 
     @staticmethod
     def backward(ctx, gl, _gstats):
-        (grad,) = ctx.saved_tensors
-        return (A.actor_head_group_grads(grad, ctx.g, gl),) + (None,) * 11
+        return A.actor_head_backward(ctx, gl, 12)
 
 
-class PPOBatch:
-    """One collected batch prepared for several epochs: everything of the update that depends on
-    the batch alone, done once (the advantage statistics, the key pass, grouping and verification,
-    the groups' representative rows, the critic's loss coefficients; on the dense path the padded
-    actor inputs, masks, actions and normalised advantages).  losses() is one epoch's forward.
+class PPOBatch(A.UpdateBatch):
+    """a2c_vec.UpdateBatch kept over several epochs, with the batch's own advantage statistics,
+    the behaviour policy's log-probabilities and the clipped loss head.  actor_losses() and
+    critic_loss() are one epoch's forward; the first epoch gathers the groups' representatives,
+    the later ones reuse them.
 
-    feats f32 [T, 38, N], masks int8 [T, 29, N], actions u8 [T, 8, N], ret / adv f64 [T, 8, N] (the
-    rollout slab's layouts; CPU tensors work, as in a2c_vec.update_step).  logp_old f32 [8, T*N]:
-    None until the first losses() call, which runs in record mode and keeps the log-probabilities
-    of its own forward (callers may set it: a batch resumed from a recorded state)."""
+    logp_old f32 [8, T*N]: None until the first actor_losses() call, which runs in record mode and
+    keeps the log-probabilities of its own forward (callers may set it: a batch resumed from a
+    recorded state)."""
 
     def __init__(self, feats, masks, actions, ret, adv, gidx, midx, dedup=True):
         from . import distributed as D
-        f3 = feats.contiguous()
-        self.T, _, self.n = f3.shape
-        T, n = self.T, self.n
-        S = self.S = T * n
-        self.cuda = f3.is_cuda
-        self.count, self.mean, self.std = D.adv_stats_slab(adv)      # of FloatTensor(adv), a2c.py:724-731
-        self.norm = self.count > 1
-        self.r3 = ret
+        count, mean, std = D.adv_stats_slab(adv)                      # of FloatTensor(adv), a2c.py:724-731
+        super().__init__(feats, masks, actions, ret, adv, gidx, midx, dedup, mean, std, count)
         self.logp_old = None
-        ga = gc = rows = x = gt = None
-        if dedup:
-            rows = torch.empty(S, GROUP_ROW, dtype=torch.float32, device=f3.device) if self.cuda else None
-            gr = A.RowGroups(A.group_keys(f3, rows), A.STATION_ROWS)  # 8 actor rows + the critic's
-            ga, gc = gr.rows(0, NA), gr.rows(NA, NA + 1)
-            if not self.cuda:
-                x, gt = A.actor_inputs(f3, gidx), f3.permute(1, 0, 2).reshape(GLOBAL_DIM, S)
-            if not A.group_verify(f3, ga, gc, x, gt, rows):           # a hash collision: dense
-                ga = gc = None
-        self.ga, self.gc = ga, gc
-        self.head_kernel = ga is not None and self.cuda
-        if self.head_kernel:
-            # the kernel reads the slabs in place
-            self.masks, self.actions, self.adv = masks.contiguous(), actions.contiguous(), adv.contiguous()
-            self.reps = A.ActorStack.rep_inputs(None, ga, A.cols_of_rows(rows, gidx))
-            self.logp_buf = torch.empty(NA, S, dtype=torch.float32, device=f3.device)
-        else:
-            if x is None:
-                x = A.actor_inputs(f3, gidx)                          # [8, 13, S]
-            if gt is None:
-                gt = f3.permute(1, 0, 2).reshape(GLOBAL_DIM, S)
-            self.m = A.agent_masks(masks, midx)
-            self.acts = actions.long().permute(1, 0, 2).reshape(NA, S)
-            adv32 = adv.float().permute(1, 0, 2).reshape(NA, S)       # calc_actor_loss: FloatTensor(adv)
-            self.adv_n = (adv32 - self.mean[:, None]) / (self.std[:, None] + 1e-8) if self.norm else adv32
-            if ga is not None:
-                self.reps = A.ActorStack.rep_inputs(x, ga)
-            else:
-                self.x = x
-        # the critic's inputs: the distinct global states (with their loss coefficients on the
-        # grouped GPU path), else every sample's state
-        self.coef = None
-        if gc is not None and self.cuda and gc.gsorted is not None:
-            self.xc = rows.index_select(0, gc.first[0])
-            self.coef = A.critic_coef(gc, ret, self.count)
-        elif gc is not None:
-            self.xc = rows.index_select(0, gc.first[0])[:, :GLOBAL_DIM] if self.cuda else gt[:, gc.first[0]].t()
-        else:
-            self.xc = gt.t()
-        if self.coef is None:
-            self.r32 = ret.float()
-
-    def critic_loss(self, critic):
-        """calc_critic_loss (a2c.py:713-722): the MSE against the fixed returns."""
-        if self.coef is not None:
-            return A.critic_onepass(critic, self.xc, self.coef)
-        v = A.mlp_forward(critic.net, self.xc)
-        if self.gc is not None:
-            v = self.gc.gather(v.reshape(1, 1, -1))
-        return ((v.reshape(self.T, 1, self.n) - self.r32) ** 2).sum() / (NA * self.count)
 
     def actor_losses(self, actors, entropy_coef, clip_eps):
-        """ppo_actor_losses on this batch -> (per-agent losses f32 [8], stats [8, 3] = per agent
-        the sums of the entropy, of the KL terms and the number of clipped samples).  The first
-        call records logp_old."""
+        """Per agent -sum surr / count - entropy_coef sum entropy / count -> (losses f32 [8], stats
+        f64 [8, 3] = per agent the sums of the entropy, of the KL terms and the number of clipped
+        samples): the HIP loss head on the GPU with a verified grouping, the torch ops of
+        ppo_head_terms everywhere else.  The first call records logp_old."""
         record = self.logp_old is None
         count = float(self.count)
+        probs = self.actor_probs(actors)
         if self.head_kernel:
-            pu = actors.forward_reps(*self.reps)
-            losses, stats = _ActorHeadPPO.apply(pu, self.ga, self.masks, self.actions, self.adv,
-                                                self.mean if self.norm else None, self.std if self.norm else None,
-                                                None if record else self.logp_old,
-                                                self.logp_buf if record else None, float(clip_eps), count,
-                                                float(entropy_coef))
+            buf = torch.empty(NA, self.S, dtype=torch.float32, device=probs.device) if record else None
+            losses, stats = _ActorHeadPPO.apply(probs, self.ga, self.masks, self.actions, self.adv, *self.head_stats(),
+                                                self.logp_old, buf, float(clip_eps), count, float(entropy_coef))
             if record:
-                self.logp_old = self.logp_buf
+                self.logp_old = buf
             return losses, stats
-        if self.ga is not None:
-            probs = self.ga.gather(actors.forward_reps(*self.reps))  # [8, 8, S]
-        else:
-            probs = actors(self.x)
-        surr, ent, kl, clipped, logp = ppo_head_terms(probs, self.m, self.acts, self.adv_n, self.logp_old, clip_eps)
+        surr, ent, kl, clipped, logp = ppo_head_terms(probs, *self.dense_operands(), self.logp_old, clip_eps)
         if record:
             self.logp_old = logp.detach().clone()
         losses = -surr.sum(dim=1) / count - entropy_coef * ent.sum(dim=1) / count
@@ -198,28 +116,21 @@ class PPOBatch:
 
 
 def ppo_actor_losses(actors, batch, entropy_coef, clip_eps):
-    """Per agent -sum surr / count - entropy_coef sum entropy / count over the PPOBatch `batch`
-    (and the statistics' sums, PPOBatch.actor_losses): an autograd Function around the HIP loss
-    head on the GPU with a verified grouping, the torch ops of ppo_head_terms everywhere else."""
+    """PPOBatch.actor_losses, as a function of the actors (tests/test_ppo_learner.py calls it)."""
     return batch.actor_losses(actors, entropy_coef, clip_eps)
 
 
 def ppo_epoch(batch, actors, critic, optim_actor, optim_critic, entropy_coef, max_grad_norm, clip_eps,
               grad_probe=None):
-    """One epoch over a PPOBatch: forward -> losses -> backward -> clip_per_agent_ and the critic's
-    clip_grad_norm_ -> both Adam steps.  Returns device tensors (no host synchronisation): actor
-    losses [8], critic loss [1], stats [8, 3] (sums: entropy, KL terms, clipped samples)."""
+    """One epoch over a PPOBatch: forward -> losses -> backward -> a2c_vec.clip_and_step.  Returns
+    device tensors (no host synchronisation): actor losses [8], critic loss [1], stats [8, 3]
+    (sums: entropy, KL terms, clipped samples)."""
     optim_actor.zero_grad(set_to_none=True)
     optim_critic.zero_grad(set_to_none=True)
     critic_loss = batch.critic_loss(critic)   # the critic first, as A2CLosses.compute
     actor_losses, stats = ppo_actor_losses(actors, batch, entropy_coef, clip_eps)
     (actor_losses.sum() + critic_loss).backward()
-    if grad_probe is not None:
-        grad_probe(A.flat_grads(actors, critic).detach().clone())
-    A.clip_per_agent_(actors, max_grad_norm)
-    torch.nn.utils.clip_grad_norm_(critic.parameters(), max_grad_norm)
-    optim_actor.step()
-    optim_critic.step()
+    A.clip_and_step(actors, critic, optim_actor, optim_critic, max_grad_norm, grad_probe)
     return actor_losses.detach(), critic_loss.detach().reshape(1), stats
 
 

@@ -488,11 +488,6 @@ def update_sharded(actors, critic, optim_actor, optim_critic, feats, masks, acti
         al2, cl2 = A.update_core(actors, critic, optim_actor, optim_critic, feats, masks, actions, ret, adv, gidx,
                                  midx, entropy_coef, max_grad_norm, group, dedup, grad_probe)
         return al2.cpu().tolist(), float(cl2.cpu()[0])
-    if grad_probe is not None:
-        grad_probe(A.flat_grads(actors, critic).detach().clone())
-    A.clip_per_agent_(actors, max_grad_norm)
-    torch.nn.utils.clip_grad_norm_(critic.parameters(), max_grad_norm)
-    optim_actor.step()
-    optim_critic.step()
+    A.clip_and_step(actors, critic, optim_actor, optim_critic, max_grad_norm, grad_probe)
     mark("clip_adam")
     return tail[:NA], tail[NA]

@@ -116,9 +116,7 @@ def main(world=8, n=4096, T=256, warm=1, reps=3):
     res["max_rel_grad_error"] = max(e for _, e in errs)
     res["rel_grad_error_per_tensor"] = [[list(s), e] for s, e in errs]
     # clip + Adam (every rank runs it on the reduced gradients)
-    _, t_adam = sync_ms(lambda: (A.clip_per_agent_(L.actors, L.max_grad_norm),
-                                 torch.nn.utils.clip_grad_norm_(L.critic.parameters(), L.max_grad_norm),
-                                 L.optim_actor.step(), L.optim_critic.step()))
+    _, t_adam = sync_ms(lambda: A.clip_and_step(L.actors, L.critic, L.optim_actor, L.optim_critic, L.max_grad_norm))
     res["clip_adam_ms"] = t_adam
     print(json.dumps(res), flush=True)
 

@@ -77,10 +77,7 @@ def run(st):
     mark("backward_critic")
     al.sum().backward()
     mark("backward_actors")
-    A.clip_per_agent_(L.actors, L.max_grad_norm)
-    torch.nn.utils.clip_grad_norm_(L.critic.parameters(), L.max_grad_norm)
-    L.optim_actor.step()
-    L.optim_critic.step()
+    A.clip_and_step(L.actors, L.critic, L.optim_actor, L.optim_critic, L.max_grad_norm)
     mark("clip+adam")
     al.cpu(), cl.cpu()
     L.repack()

@@ -352,6 +352,55 @@ def test_grouped_update_equals_dense_update():
     assert A.group_columns(x, torch.zeros(x.shape[1], dtype=torch.int64)) is None
 
 
+@pytest.mark.parametrize("dedup", [False, True])
+@pytest.mark.parametrize("T", [3, None])
+def test_losses_compute_equals_written_out_loss(T, dedup):
+    """A2CLosses.compute (UpdateBatch: batch preparation, critic loss, actor head) on a T = 3,
+    n = 5 batch and on a single step without the T axis (T None), dense and grouped, against the
+    losses written out from entropy_of, masked_probs and categorical_log_prob on the dense actors
+    and the critic's plain forward: losses and every parameter's gradient
+    (test_grouped_update_equals_dense_update's tolerances)."""
+    n = 5
+    lead = () if T is None else (T,)
+    gen = torch.Generator().manual_seed(21)
+    feats = torch.randint(0, 2, (*lead, A.GLOBAL_DIM, n), generator=gen).float()   # few values: inputs repeat
+    feats[..., 21, :] = torch.rand(*lead, n, generator=gen).round(decimals=1)
+    masks = torch.randint(0, 2, (*lead, 29, n), generator=gen).to(torch.int8)
+    masks[..., A.MASK_OFFS, :] = 1                                                 # IDLE is always valid
+    acts = torch.stack([torch.randint(0, k, (*lead, n), generator=gen) for k in A.N_ACTIONS], -2).to(torch.uint8)
+    ret = torch.randn(*lead, A.NA, n, generator=gen, dtype=torch.float64)
+    adv = torch.randn(*lead, A.NA, n, generator=gen, dtype=torch.float64)
+    gidx, midx = A.gather_index("cpu"), A.mask_index("cpu")
+    S = n * (T or 1)
+    adv32 = adv.float().reshape(-1, A.NA, n).permute(1, 0, 2).reshape(A.NA, S)
+    mean, std = adv32.mean(dim=1), adv32.std(dim=1)
+    actors, critic = A.init_networks(seed=17)
+    params = list(actors.parameters()) + list(critic.parameters())
+
+    def grads(al, cl):
+        for p in params:
+            p.grad = None
+        (al.sum() + cl).backward()
+        return [p.grad.clone() for p in params]
+
+    al, cl = A.A2CLosses.compute(actors, critic, feats, masks, acts, ret, adv, gidx, midx, 0.01, mean, std, S, dedup)
+    got = grads(al, cl)
+    probs = actors(A.actor_inputs(feats, gidx))
+    logp = A.categorical_log_prob(A.masked_probs(probs, A.agent_masks(masks, midx)),
+                                  acts.long().reshape(-1, A.NA, n).permute(1, 0, 2).reshape(A.NA, S))
+    adv_n = (adv32 - mean[:, None]) / (std[:, None] + 1e-8)
+    al_ref = -(adv_n * logp).sum(dim=1) / S - 0.01 * A.entropy_of(probs).sum(dim=1) / S
+    states = feats.reshape(-1, A.GLOBAL_DIM, n).permute(0, 2, 1).reshape(S, A.GLOBAL_DIM)
+    v = critic.net(states).reshape(-1, 1, n)
+    cl_ref = ((v - ret.float().reshape(-1, A.NA, n)) ** 2).sum() / (A.NA * S)
+    want = grads(al_ref, cl_ref)
+    assert al.shape == (A.NA,) and bool(torch.isfinite(al).all())
+    assert torch.allclose(al, al_ref, rtol=1e-5, atol=1e-6)
+    assert torch.allclose(cl, cl_ref, rtol=1e-5, atol=1e-6)
+    for a, b in zip(got, want):
+        assert torch.allclose(a, b, rtol=1e-4, atol=1e-6)
+
+
 def test_policy_weight_packing_planes_and_lane_order():
     """pack_mfma (the fused policy kernel's weight layout, include/fjsp.h): three bf16 planes
     whose sum is the f32 weight within 2^-24 relative, in the 32x32x16 MFMA A-operand lane order

@@ -163,6 +163,49 @@ def test_record_mode_equals_a2c_head(M, T, n):
     assert float((logp_out - logp).abs().max()) <= 1e-6
 
 
+@pytest.mark.parametrize("T,n", [(3, 70), (5, 103)])
+def test_record_head_equals_a2c_head(M, T, n):
+    """fjsp_a2c_record_head on one record per sample (cnt = 1, wsum = the f32 advantage widened to
+    f64, info = mask bits | action << 8) against fjsp_a2c_actor_head on the same f64 values without
+    normalisation, agent by agent: both are head_core, so the gradient rows and (1 * entropy being
+    exact) the workgroups' entropy sums agree bit for bit.  The A2C head rounds each adv * logp to
+    f32 (<= 2^-24 relative) and the record head multiplies in f64, so the workgroups' adv logp sums
+    differ by at most 2^-23 sum |adv logp| over the workgroup's samples (the factor 2 covers the
+    f64 summation)."""
+    A, nat = M["A"], M["nat"]
+    inp = _head_inputs(A, T, n, seed=13 + T)
+    S, pu, g = inp["S"], inp["pu"], inp["g"]
+    B = -(-S // 256)
+    adv = inp["adv"].float().double().contiguous()                              # [T, 8, n]
+    V = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    E = lambda *sh, dt: torch.full(sh, float("nan"), dtype=dt, device="cuda")  # noqa: E731
+    L = nat.lib()
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    g0, s0, s1 = E(29, S, dt=torch.float32), E(8, B, 2, dt=torch.float64), E(8, B, 4, dt=torch.float64)
+    g1, logp = E(29, S, dt=torch.float32), E(8, S, dt=torch.float32)            # logp: the kernels' own
+    nat.check(L.fjsp_a2c_actor_head(V(pu), pu.shape[2], V(g.inv), T, n, V(inp["masks"]), V(inp["actions"]), V(adv),
+                                    None, None, 1.0 / S, 0.01, V(g0), V(s0), st))
+    nat.check(L.fjsp_a2c_actor_head_ppo(V(pu), pu.shape[2], V(g.inv), T, n, V(inp["masks"]), V(inp["actions"]), V(adv),
+                                        None, None, None, V(logp), EPS_CLIP, 1.0 / S, 0.01, V(g1), V(s1), st))
+    bits = (inp["m"].to(torch.int32) << torch.arange(8, device="cuda", dtype=torch.int32)[None, :, None]).sum(1)
+    info = (bits | (inp["acts"].to(torch.int32) << 8)).to(torch.int32).contiguous()    # [8, S]
+    wsum = adv.permute(1, 0, 2).reshape(8, S).contiguous()
+    cnt = torch.ones(S, dtype=torch.int32, device="cuda")
+    terms = torch.nn.functional.pad((wsum * logp.double()).abs(), (0, B * 256 - S)).view(8, B, 256).sum(2)
+    for a, k in enumerate(A.N_ACTIONS):
+        gr, sr = E(k, S, dt=torch.float32), E(B, 2, dt=torch.float64)
+        nat.check(L.fjsp_a2c_record_head(V(pu[a]), pu.shape[2], V(g.inv[a]), S, k, V(info[a]), V(wsum[a]), V(cnt),
+                                         1.0 / S, 0.01, V(gr), V(sr), st))
+        torch.cuda.synchronize()
+        assert not bool(torch.isnan(gr).any()) and not bool(torch.isnan(sr).any())   # every element written
+        o = A.MASK_OFFS[a]
+        assert torch.equal(g0[o:o + k], gr), a
+        assert torch.equal(s0[a, :, 1], sr[:, 1]), a
+        d, bound = (s0[a, :, 0] - sr[:, 0]).abs(), 2.0 ** -23 * terms[a]
+        print("agent", a, "adv logp sums: diff", d.tolist(), "bound", bound.tolist())
+        assert bool((d <= bound).all()), a
+
+
 def _flat_split(params, flat):
     out, o = [], 0
     for p in params:
