@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("FJSP_LIB") or os.path.join(HERE, "libfjsp.so")
 SRC = os.path.join(HERE, "csrc", "fjsp_hip.hip")
 SRCS = [SRC, os.path.join(HERE, "csrc", "fjsp_policy.hip"), os.path.join(HERE, "csrc", "fjsp_group.hip"),
         os.path.join(HERE, "csrc", "fjsp_episode.hip")]
-HEADERS = [os.path.join(HERE, "csrc", h) for h in ("fjsp_env.h", "fjsp_select.h", "fjsp_stepdev.h", "fjsp_stamps.h")] + [
+HEADERS = [os.path.join(HERE, "csrc", h) for h in ("fjsp_env.h", "fjsp_select.h", "fjsp_stepdev.h", "fjsp_predraw.h", "fjsp_stamps.h")] + [
     os.path.join(REPO, "include", "fjsp.h")]
 
 # the drop-in facade's host helper (CPython extension, no GPU code): csrc/fjsp_facade.c

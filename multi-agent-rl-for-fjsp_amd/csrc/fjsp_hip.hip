@@ -506,23 +506,35 @@ constexpr int AG_PB = 4;   // words drawn per env per step in k_step_ag
 // FINAL_MB: the sim side also posts in the final epoch K (k_step_ag resets at the top of an
 // epoch), so a table it consumed or abandoned there must not be stored as ready.
 // ASYNC (k_step_ag): a row loaded in step k is held in registers and stored in step k + 1, and
-// each MT refill is loaded a step ahead: their latency hides behind the barrier instead of
-// the step (plain loads; an LDS DMA would be drained by the barrier's fence).  s_cp unused.
-template <int CR, int PB, bool FINAL_MB = false, bool ASYNC = false>
+// the draw runs in the slices of PreDrawLane (fjsp_predraw.h): the runs of a refill are loaded
+// behind the step's slices and row stores, by the one load site of the loop and into the one
+// register set, and first read in a later step, so their latency hides behind the barrier
+// instead of the step (plain loads; an LDS DMA would be drained by the barrier's fence).  s_cp
+// unused.
+// ALT: a step runs the refill or the consume slice, by its parity (pd_refill_step): half the
+// draw's instructions per step, a table ready in twice the steps; the runs of the next group are
+// loaded in the refill's step and have the consume's step to land.
+template <int CR, int PB, bool FINAL_MB = false, bool ASYNC = false, bool ALT = false>
 __device__ __forceinline__ void predraw_wave(const DevState& S, int K, int lane, int e, bool valid, size_t ebase,
                                              uint32_t (*s_mb)[2][BLOCK], uint4 (*s_cp)[3][BLOCK], uint32_t* s_nxt) {
     const uint32_t n = (uint32_t)S.n;
     // the pre-draw wave: 0 idle, 1 copying the live row, 2 drawing, 3 table ready
-    int ph = 0, nord = 0, pos = 0, g = 0;
+    int ph = 0, nord_ = 0, pos_ = 0, g_ = 0;
     uint32_t src = 0, my = 0x100u;   // live row at the start of the pre-draw; episode it is for
-    OrderDraw d{0, 0, 0, 0, 0u};
+    OrderDraw d_{0, 0, 0, 0, 0u};
+    static_assert(!ASYNC || PB == PD_B, "the sliced lane draws PD_B words per refill");
+    // the table's size, the cursor and the draw: ASYNC in the sliced lane L, else in the plain
+    // variables above (k_step_pipe's code stays as it was)
+    struct NoLane {};
+    std::conditional_t<ASYNC, PreDrawLane, NoLane> L;
+    if constexpr (ASYNC) L.start(0, 0, 0);
+    int& nord = [&]() -> int& { if constexpr (ASYNC) return L.nord; else return nord_; }();
+    int& pos = [&]() -> int& { if constexpr (ASYNC) return L.pos; else return pos_; }();
+    int& g = [&]() -> int& { if constexpr (ASYNC) return L.g; else return g_; }();
+    OrderDraw& d = [&]() -> OrderDraw& { if constexpr (ASYNC) return L.d; else return d_; }();
     int ls_prev[CR];       // ASYNC: lanes whose row DMA is in flight (ph == 4) and their source rows
     uint32_t sl_prev[CR];
     bool inflight = false;
-    // ASYNC: the runs of the next refill, loaded a step ahead (after the draw that precedes it):
-    // the draw waits for loads a step old, not for loads it issues; pf_pa = their refill, -1 none
-    uint4 pfa[(PB + 4) / 4], pfc[(PB + 4) / 4];
-    int pf_pa = -1;
     // ASYNC: the rows in flight, in registers (plain loads are not waited for at the barrier; an
     // LDS DMA is: the barrier's fence drains it)
     // (three scalars, not an array: an array here stays in scratch memory and each load is
@@ -541,7 +553,11 @@ __device__ __forceinline__ void predraw_wave(const DevState& S, int K, int lane,
         }
     }
     FJSP_DIAG(
-    uint64_t pg_busy = 0, pg_act = 0, pg_busy_act = 0, pg_ph[3] = {0, 0, 0};
+    // pg_ph: cycles of the active steps by part (mailbox read, draw, row stores, the refills'
+    // loads, row loads, mailbox post); pg_wall / pg_walln: barrier exit to barrier exit, cycles
+    // and steps, [0] active [1] inactive; pg_last: arrivals the barrier did not hold (AG_BARRIER)
+    uint64_t pg_busy = 0, pg_act = 0, pg_busy_act = 0, pg_ph[6] = {0, 0, 0, 0, 0, 0};
+    uint64_t pg_wall[2] = {0, 0}, pg_walln[2] = {0, 0}, pg_last = 0, pg_exit = 0;
     )
     for (int k = 0; k <= K; k++) {
         FJSP_DIAG(
@@ -553,51 +569,38 @@ __device__ __forceinline__ void predraw_wave(const DevState& S, int K, int lane,
             if ((si & 0xFFu) != my) {   // a new episode: start over from its stream position
                 const uint32_t sw = s_mb[1][k & 1][lane];
                 my = si & 0xFFu;
-                nord = (int)((si >> 8) & 0x7Fu);
-                src = sw >> 31;
-                pos = (int)(sw & 0x3FFu);
-                g = (int)((sw >> 16) & 0x3FFu);
-                d = OrderDraw{0, 0, 0, 0, 0u};
-                pf_pa = -1;
+                if constexpr (ASYNC) {
+                    src = sw >> 31;
+                    L.start((int)((si >> 8) & 0x7Fu), (int)(sw & 0x3FFu), (int)((sw >> 16) & 0x3FFu));
+                } else {
+                    nord = (int)((si >> 8) & 0x7Fu);
+                    src = sw >> 31;
+                    pos = (int)(sw & 0x3FFu);
+                    g = (int)((sw >> 16) & 0x3FFu);
+                    d = OrderDraw{0, 0, 0, 0, 0u};
+                }
                 ph = nord > 0 ? 1 : 3;
             }
         }
         // Copy the live rows of up to CR envs that start a pre-draw (the whole wave, one
         // env at a time: contiguous 1 KB loads): loads first, the per-lane draw in the shadow
         // of their latency, then the stores.  Rows copied in step k are first read in k + 1.
-        // ASYNC: the runs of the next refill from pos (disjoint from the words stored since)
-        auto prefetch = [&](const uint32_t* work) __attribute__((always_inline)) {
-            pf_pa = pos & ~3;
-            mt_load<PB>(work, pf_pa, pfa, pfc);
-        };
         auto draw_step = [&]() __attribute__((always_inline)) {
-            if (valid && ph == 2) {
+            if constexpr (ASYNC) {
+                // this step's slices on runs loaded in an earlier step (the load site is below,
+                // after the row stores)
+                uint32_t* work = S.mt + ((size_t)(src ^ 1u) * n + e) * MT_N;
+                if (pd_refill_step<ALT>(k) && valid && ph == 2 && L.can_refill()) L.refill(work);
+                if (pd_consume_step<ALT>(k) && valid && ph == 2 && L.can_consume())
+                    if (L.consume(s_nxt + lane, BLOCK)) ph = 3;
+            } else if (valid && ph == 2) {
                 uint32_t* work = S.mt + ((size_t)(src ^ 1u) * n + e) * MT_N;
                 uint32_t v[PB];
                 int pa, cnt;
-                if (ASYNC && pf_pa == (pos & ~3)) {
-                    // the refill after this one first (a refill reads no word this one stores),
-                    // then this one on runs loaded a step ago
-                    const int pn = pf_pa + PB >= MT_N ? 0 : pf_pa + PB;
-                    uint4 pna[(PB + 4) / 4], pnc[(PB + 4) / 4];
-                    mt_load<PB>(work, pn, pna, pnc);
-                    mt_batch_loaded<PB>(work, pos, g, v, pa, cnt, pfa, pfc);
-#pragma unroll
-                    for (int q = 0; q < (PB + 4) / 4; q++) { pfa[q] = pna[q]; pfc[q] = pnc[q]; }
-                    pf_pa = pn;
-                    pos += draw_orders<PB>(v, pos - pa, cnt, nord, d, s_nxt + lane, BLOCK);
-                    if (pos == MT_N) { pos = 0; g = 0; }
-                    if (d.o >= nord) { ph = 3; pf_pa = -1; }
-                } else {
-                    mt_batch<PB>(work, pos, g, v, pa, cnt);
-                    pos += draw_orders<PB>(v, pos - pa, cnt, nord, d, s_nxt + lane, BLOCK);
-                    if (pos == MT_N) { pos = 0; g = 0; }
-                    if (d.o >= nord) ph = 3;
-                    if (ASYNC) {
-                        if (ph == 2) prefetch(work);
-                        else pf_pa = -1;
-                    }
-                }
+                mt_batch<PB>(work, pos, g, v, pa, cnt);
+                pos += draw_orders<PB>(v, pos - pa, cnt, nord, d, s_nxt + lane, BLOCK);
+                if (pos == MT_N) { pos = 0; g = 0; }
+                if (d.o >= nord) ph = 3;
             }
         };
         FJSP_DIAG(
@@ -609,9 +612,10 @@ __device__ __forceinline__ void predraw_wave(const DevState& S, int K, int lane,
         pg_active = need != 0 || __ballot(valid && ph == 2) != 0;
         )
         if (ASYNC) {
-            // the draw first (its runs were loaded two steps ago), then last step's rows (loaded
-            // after that step's prefetches), then this step's row loads: each wait is for loads
-            // a step old, never for the ones just issued (vmcnt counts in order)
+            // the draw first (its runs were loaded a step ago or more), then last step's rows
+            // (loaded after that step's runs), then the runs of the lanes that have none and this
+            // step's row loads: each wait is for loads a step old, never for the ones just issued
+            // (vmcnt counts in order)
             draw_step();
             FJSP_DIAG(
             const uint64_t pt2 = __builtin_amdgcn_s_memtime();
@@ -630,12 +634,22 @@ __device__ __forceinline__ void predraw_wave(const DevState& S, int K, int lane,
                 (void)pb;
                 inflight = false;
             }
+            FJSP_DIAG(
+            const uint64_t pt3 = __builtin_amdgcn_s_memtime();
+            if (pg_active) pg_ph[2] += pt3 - pt2;
+            )
 
 #pragma unroll
             for (int r = 0; r < CR; r++)
                 if (promote == 4 && ph == 4 && lane == ls_prev[r]) ph = 2;
-            if (valid && promote == 4 && ph == 2)   // rows stored above: their first refill
-                prefetch(S.mt + ((size_t)(src ^ 1u) * n + e) * MT_N);
+            // the loop's one load site: the next refill of the lanes that consumed theirs, and the
+            // first of the lanes whose rows were stored above
+            if constexpr (ASYNC)
+                if (valid && ph == 2 && L.wants_load()) L.load(S.mt + ((size_t)(src ^ 1u) * n + e) * MT_N);
+            FJSP_DIAG(
+            const uint64_t pt4 = __builtin_amdgcn_s_memtime();
+            if (pg_active) pg_ph[3] += pt4 - pt3;
+            )
             if (need) {
                 const int first = __builtin_ctzll(need);
 #pragma unroll
@@ -652,6 +666,9 @@ __device__ __forceinline__ void predraw_wave(const DevState& S, int K, int lane,
                 }
                 inflight = true;
             }
+            FJSP_DIAG(
+            if (pg_active) pg_ph[4] += __builtin_amdgcn_s_memtime() - pt4;
+            )
         } else if (need) {
             // rows go through LDS by DMA (global_load_lds: no VGPRs held across the draw);
             // slots beyond the envs waiting re-copy the first env's row (identical stores)
@@ -685,20 +702,31 @@ __device__ __forceinline__ void predraw_wave(const DevState& S, int K, int lane,
         } else {
             draw_step();
         }
+        FJSP_DIAG(
+        const uint64_t pt5 = __builtin_amdgcn_s_memtime();
+        )
         if (valid) {
             const uint32_t wrow = nord > 0 ? (src ^ 1u) : src;
             s_mb[2][(k + 1) & 1][lane] = (ph == 3 ? 1u : 0u) | (my << 1) | ((uint32_t)nord << 9);
             s_mb[3][(k + 1) & 1][lane] = (uint32_t)pos | ((uint32_t)g << 16) | (wrow << 31);
         }
         FJSP_DIAG(
+        const uint64_t pb0 = __builtin_amdgcn_s_memtime();
         {
-            const uint64_t dt = __builtin_amdgcn_s_memtime() - pt0;
+            const uint64_t dt = pb0 - pt0;
             pg_busy += dt;
-            if (pg_active) { pg_act += 1; pg_busy_act += dt; }
-            (void)pg_ph;
+            if (pg_active) { pg_act += 1; pg_busy_act += dt; pg_ph[5] += pb0 - pt5; }
         }
         )
         __syncthreads();
+        FJSP_DIAG(
+        {
+            const uint64_t pb1 = __builtin_amdgcn_s_memtime();
+            pg_last += (pb1 - pb0) < 200 ? 1 : 0;
+            if (k > 0) { pg_wall[pg_active ? 0 : 1] += pb1 - pg_exit; pg_walln[pg_active ? 0 : 1] += 1; }
+            pg_exit = pb1;
+        }
+        )
     }
     if (ASYNC) __builtin_amdgcn_s_waitcnt(0x0F70);   // no LDS DMA outlives the workgroup
     FJSP_DIAG(
@@ -707,7 +735,15 @@ __device__ __forceinline__ void predraw_wave(const DevState& S, int K, int lane,
         atomicAdd(&g_pgstamps[1], (unsigned long long)pg_act);
         atomicAdd(&g_pgstamps[2], (unsigned long long)pg_busy_act);
         atomicAdd(&g_pgstamps[3], (unsigned long long)(K + 1));
-        if (ASYNC) { atomicAdd(&g_agstamps[52], (unsigned long long)pg_ph[0]); atomicAdd(&g_agstamps[53], (unsigned long long)pg_ph[1]); }
+        if (ASYNC) {   // k_step_ag (scripts/diag_ag_stamps.py): [52..55], [50], [51] parts, [30] last arrivals, [59..62] walls
+            constexpr int PH_SLOT[6] = {52, 53, 54, 55, 50, 51};
+            for (int i = 0; i < 6; i++) atomicAdd(&g_agstamps[PH_SLOT[i]], (unsigned long long)pg_ph[i]);
+            atomicAdd(&g_agstamps[25 + 5], (unsigned long long)pg_last);
+            for (int i = 0; i < 2; i++) {
+                atomicAdd(&g_agstamps[59 + i], (unsigned long long)pg_wall[i]);
+                atomicAdd(&g_agstamps[61 + i], (unsigned long long)pg_walln[i]);
+            }
+        }
     }
     )
     if (valid) {
@@ -1660,7 +1696,7 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
             AG_BARRIER();
         }
     } else if (wave == AG_PD) {
-        predraw_wave<CR, PB, true, true>(S, K, lane, e, valid, (size_t)blk * EPW, s_mb, s_cp, s_nxt);
+        predraw_wave<CR, PB, true, true, EPW == 16>(S, K, lane, e, valid, (size_t)blk * EPW, s_mb, s_cp, s_nxt);
     } else {
         // E0: step k+2's actions, rewards, the pickup's masks; E1: int32 and float32 fields; E2:
         // int8 fields, term, trunc, status, the AGV's masks; E3: step k+1's pickup

@@ -7,12 +7,11 @@
 #include <stdint.h>
 
 #include "fjsp_env.h"
+#include "fjsp_predraw.h"
 #include "fjsp_stamps.h"
 #include "../../include/fjsp.h"
 
 namespace fjsp {
-
-constexpr int MT_N = 624;
 
 struct DevState {
     uint32_t* words;
@@ -77,107 +76,9 @@ __device__ inline void mt_seed(uint32_t* __restrict__ mt, int e, uint32_t seed) 
     }
 }
 
-// Batched reader of the lazily twisted stream for resets.  A refill of B words starts at the
-// 16-byte aligned word pa = pos & ~3 and loads the words it needs as two runs of B/4 + 1 uint4
-// (words [pa, pa+B+4) and [pa+396, pa+B+400), wrapped into the row; 624 is a multiple of 4
-// so no uint4 straddles the wrap), regenerates the words at or past g, writes the batch back
-// as uint4 (words before g are written back unchanged) and returns the B tempered words in
-// registers; the pos - pa words before pos are skipped by the consumer.  cnt = words of the
-// batch inside the row (a multiple of 4; a batch never crosses the wrap).
-constexpr int MTB = 32;
-
-// the two runs of a refill at pa (mt_batch), as uint4
-template <int B>
-__device__ __forceinline__ void mt_load(const uint32_t* __restrict__ roww, int pa, uint4 (&va)[(B + 4) / 4],
-                                        uint4 (&vc)[(B + 4) / 4]) {
-    const uint4* row = reinterpret_cast<const uint4*>(roww);
-#pragma unroll
-    for (int q = 0; q < (B + 4) / 4; q++) {
-        int ia = pa + 4 * q;
-        ia = ia >= MT_N ? ia - MT_N : ia;
-        int ic = pa + 396 + 4 * q;
-        ic = ic >= MT_N ? ic - MT_N : ic;
-        ic = ic >= MT_N ? ic - MT_N : ic;
-        va[q] = row[ia >> 2];
-        vc[q] = row[ic >> 2];
-    }
-}
-
-// mt_batch on runs already loaded (mt_load at pa = pos & ~3, no store to them since)
-template <int B>
-__device__ __forceinline__ void mt_batch_loaded(uint32_t* __restrict__ roww, int pos, int& g, uint32_t (&v)[B], int& pa,
-                                                int& cnt, const uint4 (&va)[(B + 4) / 4], const uint4 (&vc)[(B + 4) / 4]) {
-    uint4* row = reinterpret_cast<uint4*>(roww);
-    pa = pos & ~3;
-    cnt = (MT_N - pa) < B ? (MT_N - pa) : B;
-    uint32_t a[B + 4], c[B + 4];
-#pragma unroll
-    for (int q = 0; q < (B + 4) / 4; q++) {
-        a[4 * q] = va[q].x; a[4 * q + 1] = va[q].y; a[4 * q + 2] = va[q].z; a[4 * q + 3] = va[q].w;
-        c[4 * q] = vc[q].x; c[4 * q + 1] = vc[q].y; c[4 * q + 2] = vc[q].z; c[4 * q + 3] = vc[q].w;
-    }
-    uint32_t w[B];
-#pragma unroll
-    for (int j = 0; j < B; j++) {
-        const uint32_t y = (a[j] & 0x80000000u) | (a[j + 1] & 0x7fffffffu);   // a[cnt] = word 0 at the wrap
-        const uint32_t regen = c[j + 1] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);   // word pa + j + 397
-        const uint32_t stale = (uint32_t)((pa + j - g) >> 31);   // all ones iff word pa + j < g (already current)
-        w[j] = (regen & ~stale) | (a[j] & stale);   // bitwise: no branch per word
-        uint32_t t = w[j];
-        t ^= t >> 11;
-        t ^= (t << 7) & 0x9d2c5680u;
-        t ^= (t << 15) & 0xefc60000u;
-        t ^= t >> 18;
-        v[j] = t;
-    }
-#pragma unroll
-    for (int q = 0; q < B / 4; q++)
-        if (4 * q < cnt) row[(pa >> 2) + q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-    if (pa + cnt > g) g = pa + cnt;
-}
-
-template <int B>
-__device__ __forceinline__ void mt_batch(uint32_t* __restrict__ roww, int pos, int& g, uint32_t (&v)[B], int& pa,
-                                         int& cnt) {
-    uint4 va[(B + 4) / 4], vc[(B + 4) / 4];
-    mt_load<B>(roww, pos & ~3, va, vc);
-    mt_batch_loaded<B>(roww, pos, g, v, pa, cnt, va, vc);
-}
-
-// generate_order (FJSPSimulation.py:101-131) as a state machine over the stream: per order
-// randint(1, 10) then choice(ProductType) then choice(PackagingColor) (:107,111-112) with
-// numpy's masked rejection: rng 8 / mask 15 for the product count (field k = 0), rng 2 /
-// mask 3 for type and colour (k = 1, 2).
-struct OrderDraw {
-    int o, k, np, ty;
-    uint32_t last;
-};
-
-// Consume words [skip, cnt) of one batch (straight-line selects, no per-draw branch) until
-// `num_orders` orders are complete; returns the words consumed.  The order word is stored
-// every draw, to slot o (overwritten later by order o's own store) or, once the table is
-// complete, as the unchanged last order.
-template <int B>
-__device__ __forceinline__ int draw_orders(const uint32_t (&v)[B], int skip, int cnt, int num_orders, OrderDraw& d,
-                                           uint32_t* orders, int stride) {
-    int used = 0;
-#pragma unroll
-    for (int j = 0; j < B; j++) {
-        const bool act = j >= skip && j < cnt && d.o < num_orders;
-        const uint32_t x = v[j] & (d.k == 0 ? 15u : 3u);
-        const bool acc = act && x <= (d.k == 0 ? 8u : 2u);
-        const bool emit = acc && d.k == 2;
-        d.np = (acc && d.k == 0) ? 1 + (int)x : d.np;
-        d.ty = (acc && d.k == 1) ? 1 + (int)x : d.ty;
-        const uint32_t ow = ow_make(d.np, d.ty, 1 + (int)x);
-        d.last = emit ? ow : d.last;
-        orders[(d.o < num_orders ? d.o : num_orders - 1) * stride] = d.last;
-        d.o += emit ? 1 : 0;
-        d.k = acc ? (d.k == 2 ? 0 : d.k + 1) : d.k;
-        used += act ? 1 : 0;
-    }
-    return used;
-}
+// The batched reader of the stream (mt_load, mt_batch_loaded, mt_batch), the order draw (OrderDraw,
+// draw_orders) and the pre-draw lane's slices are in fjsp_predraw.h, which also compiles for the
+// host.
 
 // MT rows: two per env ([2][N][624]); bit 31 of the cursor word W3 selects the live one (the
 // other is the pre-draw wave's working copy, see k_step_pipe).  W[PGW] = the pre-draw record:
