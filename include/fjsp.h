@@ -580,6 +580,14 @@ int64_t fjsp_snapshot_bytes(const fjsp_handle* h);
  * probabilities f32 [8][8][N] (NULL to skip).  actions == NULL: the critic's values only (masks,
  * actor_w and seed may then be NULL; e.g. the batch-end bootstrap V(s_T), a2c.py:321-332);
  * values == NULL: the actors only (critic_w may be NULL).  Stream-ordered on `stream`.
+ * The masked distribution (a2c.py:204-231) in f32: softmax over the agent's n_a actions, times the
+ * mask, renormalised; if no valid action has probability left, uniform over the k valid actions
+ * (exactly 1.0f / k each).  A padded action (j >= n_a) has probability exactly 0.  The greedy
+ * action is the FIRST maximum (torch.argmax's rule: the lowest valid index under the uniform
+ * fallback); a draw never returns an action of probability 0.  Whether an input whose best logit
+ * exceeds its best VALID logit by about 87 .. 104 falls into the fallback is decided by f32
+ * underflow of expf, as in the reference's f32 softmax; below that gap it never does, above it
+ * always (tests/policy_ref.py, tests/test_gpu_policy_kernel.py).
  * Variants read per launch (fjsp_set_option(NULL, ...); outputs bit-identical under every setting):
  * policy_xmap 0..3 (workgroup -> XCD order; 1-3 also turn the split below off), policy_dedup 0
  * (the station agents' MLP on every env instead of once per distinct input of a 64-env tile),

@@ -114,6 +114,17 @@ __device__ __forceinline__ f32x16 mfma6(const bf16x8 a[NP], const bf16x8 b[NP], 
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc, 0, 0, 0);
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
 }
+// mfma6 with the five small plane products in an accumulator of their own: the full-size sum is
+// then rounded once per 16-deep block, as a plain f32 GEMM's, not six times (the critic's value: its
+// error against float64 drops by about a third, tests/test_gpu_policy_kernel.py)
+__device__ __forceinline__ void mfma6_two(const bf16x8 a[NP], const bf16x8 b[NP], f32x16& acc, f32x16& small) {
+    small = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], small, 0, 0, 0);
+    small = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], small, 0, 0, 0);
+    small = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], small, 0, 0, 0);
+    small = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], small, 0, 0, 0);
+    small = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], small, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
+}
 
 // Weight blocks of one row tile in flight: a register ring of D + 1 blocks x NP planes.
 constexpr int WPD = 1;
@@ -145,12 +156,20 @@ __device__ __forceinline__ void wring_start(WRing<KB>& R, const bf16x8* __restri
 // made the compiler wait for each weight load right after issuing it): weight blocks D ahead,
 // B fragments one MFMA group ahead, each pinned by a scheduling barrier (the scheduler otherwise
 // sinks the loads to their first use).
-template <int KB, int ST, int PL, int NC>
+// TWO: the small plane products in accumulators of their own, added at the end (mfma6_two).
+template <int KB, int ST, int PL, int NC, bool TWO = false>
 __device__ __forceinline__ void mfma_rows(WRing<KB>& R, const bf16x8* __restrict__ a, const __bf16* act, int c0, int lane,
                                           f32x16 acc[NC]) {
     constexpr int D = WRing<KB>::D;
     const __bf16* bq = act + (c0 + (lane & 31)) * ST + 8 * (lane >> 5);
     bf16x8 fb[2][NP];
+    f32x16 small[TWO ? NC : 1];
+    if constexpr (TWO) {
+#pragma unroll
+        for (int c = 0; c < NC; c++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) small[c][r] = 0.0f;
+    }
 #pragma unroll
     for (int p = 0; p < NP; p++) fb[0][p] = *reinterpret_cast<const bf16x8*>(bq + p * PL);
 #pragma unroll
@@ -170,8 +189,15 @@ __device__ __forceinline__ void mfma_rows(WRing<KB>& R, const bf16x8* __restrict
                     fb[(g + 1) & 1][p] = *reinterpret_cast<const bf16x8*>(bq + 32 * cn * ST + 16 * kn + p * PL);
             }
             __builtin_amdgcn_sched_barrier(0);
-            acc[c] = mfma6(R.w[kb % (D + 1)], fb[g & 1], acc[c]);
+            if constexpr (TWO) mfma6_two(R.w[kb % (D + 1)], fb[g & 1], acc[c], small[c]);
+            else acc[c] = mfma6(R.w[kb % (D + 1)], fb[g & 1], acc[c]);
         }
+    }
+    if constexpr (TWO) {
+#pragma unroll
+        for (int c = 0; c < NC; c++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[c][r] += small[c][r];
     }
 }
 
@@ -392,7 +418,8 @@ __device__ __forceinline__ CriticW critic_weights(const float* wb) {
 }
 
 // The critic on a tile of 32 envs: layers 1 and 2 one 32-row tile per wave, layer 3 (128 rows)
-// on waves 0..3, the value head from layer 3's accumulators.
+// on waves 0..3, the value head from layer 3's accumulators.  The layers sum the small plane products
+// in accumulators of their own (mfma_rows<..., true>): one more f32x16 per wave, the same MFMAs.
 __device__ __forceinline__ void critic_tile(const PolicyArgs& A, int tile, unsigned char* s_mem, int tid, int lane,
                                             int wave) {
     __bf16* s_x = reinterpret_cast<__bf16*>(s_mem);              // inputs [NP][TC][XSC]
@@ -410,7 +437,7 @@ __device__ __forceinline__ void critic_tile(const PolicyArgs& A, int tile, unsig
     PST(3, __builtin_amdgcn_s_memtime());
     f32x16 a[1];
     zero_acc<1>(a);
-    mfma_rows<C_DPAD / 16, XSC, XPC, 1>(r1, wblocks<C_DPAD / 16, C_DPAD / 16>(W1, wave, 0, lane), s_x, 0, lane, a);
+    mfma_rows<C_DPAD / 16, XSC, XPC, 1, true>(r1, wblocks<C_DPAD / 16, C_DPAD / 16>(W1, wave, 0, lane), s_x, 0, lane, a);
     PST(4, __builtin_amdgcn_s_memtime());
     WRing<HID / 16> r2;
     wring_start(r2, wblocks<HID / 16, HID / 16>(W2, wave, 0, lane));
@@ -419,7 +446,7 @@ __device__ __forceinline__ void critic_tile(const PolicyArgs& A, int tile, unsig
     __syncthreads();
     PST(5, __builtin_amdgcn_s_memtime());
     zero_acc<1>(a);
-    mfma_rows<HID / 16, HSC, HPC, 1>(r2, wblocks<HID / 16, HID / 16>(W2, wave, 0, lane), s_h, 0, lane, a);
+    mfma_rows<HID / 16, HSC, HPC, 1, true>(r2, wblocks<HID / 16, HID / 16>(W2, wave, 0, lane), s_h, 0, lane, a);
     PST(6, __builtin_amdgcn_s_memtime());
     const int rt3 = wave & 3;
     WRing<HID / 16> r3;
@@ -431,7 +458,7 @@ __device__ __forceinline__ void critic_tile(const PolicyArgs& A, int tile, unsig
     PST(7, __builtin_amdgcn_s_memtime());
     if (wave < 4) {
         zero_acc<1>(a);
-        mfma_rows<HID / 16, HSC, HPC, 1>(r3, wblocks<HID / 16, HID / 16>(W3, rt3, 0, lane), s_h, 0, lane, a);
+        mfma_rows<HID / 16, HSC, HPC, 1, true>(r3, wblocks<HID / 16, HID / 16>(W3, rt3, 0, lane), s_h, 0, lane, a);
         // the value head: this lane's 16 rows of h3, the other half-wave's (lane ^ 32), then the
         // four row tiles through LDS
         float v = 0.0f;
