@@ -227,6 +227,28 @@ int64_t fjsp_state_bytes(const fjsp_handle* h);
 int fjsp_reset(fjsp_handle* h, const uint32_t* seeds, const uint8_t* env_mask, int32_t num_orders,
                const fjsp_out* out);
 
+/* Orders from the caller instead of the MT19937 draw.
+ * orders:   device u32 [K][N] (env fastest), word = n | type << 4 | colour << 6 (the low byte of
+ *           fjsp_env_view.orders); n 1..9, type 1..3, colour 1..3, every other bit 0.  0 <= K <= 64.
+ * counts:   device i32 [N] (env e uses rows 0..counts[e]-1) or NULL = K for every env.
+ * env_mask: device u8 [N] or NULL = all.
+ * append = 0: FJSPSimulation.reset (FJSPSimulation.py:301-320) with these orders in place of the
+ *           generate_order draws.  The env's MT stream is neither reseeded nor advanced.  A
+ *           pre-drawn next table is dropped, as every other reset path does.  counts[e] = 0 is the empty episode.
+ * append = 1: counts[e] calls of generate_order (FJSPSimulation.py:101-131) between two steps with
+ *           these draws: the orders join the running episode's table and the pickup queue with ids
+ *           norders.., and nothing else of the env changes (a pre-drawn next table, a cache of the
+ *           stream drawn for the old order count, is dropped too).  Needs a reset before it.
+ * An env with an invalid word in its rows, counts[e] outside 0..K, or (append) norders + counts[e] > 64
+ * is left exactly as it was and counted in *rejected (device u32, may be NULL; the caller zeroes it).
+ * out (T = 1, may be NULL) receives the observation / masks / feats / status of the envs written.
+ * Stream-ordered like fjsp_reset; a running step server is stopped first and relaunched by its next
+ * request.  The installed table lasts for the episode: after an auto-reset, later episodes are drawn
+ * from the env's MT stream with the env's current order count (appended orders included), as after
+ * any other reset.  An appended order's KPI flow time counts from the episode's start. */
+int fjsp_put_orders(fjsp_handle* h, const uint32_t* orders, int32_t K, const int32_t* counts,
+                    const uint8_t* env_mask, int32_t append, uint32_t* rejected, const fjsp_out* out);
+
 /* One step of every env.  actions: device u8[8][N] (agent-major), 255 = agent absent,
  * other out-of-range values behave as the reference's invalid actions.  agent_order: host
  * u8[8] execution order (the action dict's key order) or NULL = canonical order.

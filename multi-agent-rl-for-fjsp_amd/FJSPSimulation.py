@@ -1,7 +1,7 @@
 """FJSPSimulation drop-in: one reference environment stepped by the HIP kernels (N = 1).
 
 Reference: FJSPSimulation.py (class FJSPSimulation, :27-430).  Same constructor, reset(),
-step(), get_order_progress(), observation_space(), action_space(), get_agent_ids() and the
+step(), generate_order(), get_order_progress(), observation_space(), action_space(), get_agent_ids() and the
 attributes a2c.py reads (current_step, agv.position, agv.carrying_tray).  Observations are the
 reference's dicts of numpy arrays with the exact dtypes; rewards are Python floats (fp64);
 terminations / truncations are Python bools; infos carry the decoded action-result dicts.
@@ -129,6 +129,29 @@ class _AgentView:
         return getattr(ActionSpaces, self.agent_id)()
 
 
+class GeneratedOrder:
+    """What generate_order returns: the reference Order's id and arrival_time and its products'
+    common facts (num_products = len(order.products), the enums' values)."""
+    __slots__ = ("id", "num_products", "product_type", "packaging_color", "arrival_time")
+
+    def __init__(self, id, num_products, product_type, packaging_color, arrival_time):
+        self.id, self.num_products, self.product_type = id, num_products, product_type
+        self.packaging_color, self.arrival_time = packaging_color, arrival_time
+
+    def __repr__(self):
+        return (f"GeneratedOrder(id={self.id}, num_products={self.num_products}, product_type={self.product_type}, "
+                f"packaging_color={self.packaging_color}, arrival_time={self.arrival_time})")
+
+
+class _RecordOut:
+    """The pinned record's observation pointers in the shape FJSPVecEnv's calls take buffers."""
+    def __init__(self, out):
+        self._out = out
+
+    def struct(self):
+        return self._out
+
+
 def _action_code(v):
     """Reference branch semantics by value: 0..max valid, anything else behaves as invalid."""
     try:
@@ -166,6 +189,7 @@ class FJSPSimulation:
         # one launch per step: no per-launch event pair (fjsp_last_kernel_ms), the facade never reads it
         nat.check(self._L.fjsp_set_option(self._h, b"timing", 0))
         self._packed = _Packed()
+        self._record_out = _RecordOut(self._packed.out_obs)
         self._act_host = torch.zeros(8, dtype=torch.uint8).pin_memory()   # read by the kernel in place
         self._act_np = self._act_host.numpy()
         self._act_ptr = ctypes.c_void_p(self._act_host.data_ptr())
@@ -236,10 +260,32 @@ class FJSPSimulation:
         return dict(d)
 
     # ------------------------------------------------------------------ reference API
-    def reset(self, seed=None, num_orders=None):
-        """FJSPSimulation.reset (FJSPSimulation.py:286-323)."""
+    def _put_orders(self, book, append):
+        """fjsp_put_orders for this env with the observation into the pinned record; a running step
+        server is stopped by the library and relaunched by the next step's request."""
+        from . import orders as O
+        words, _ = O.encode([book])
+        self._bind_stream()
+        self._venv.put_orders(words, append=append, buffers=self._record_out)   # synchronises (the rejected count)
+        self._viewcache = None
+        return self._take_obs(self._packed.view)
+
+    def reset(self, seed=None, num_orders=None, orders=None):
+        """FJSPSimulation.reset (FJSPSimulation.py:286-323).  orders: a list of (products, type,
+        colour) (orders.py) that becomes the episode's order table in place of the num_orders
+        generate_order draws; no RNG word is consumed after the optional np.random.seed(seed)."""
         if seed is not None:
             np.random.seed(seed)
+        if orders is not None:
+            book = [tuple(o) for o in orders]
+            if num_orders is not None and int(num_orders) != len(book):
+                raise ValueError(f"num_orders = {num_orders} but {len(book)} orders given")
+            obs = self._put_orders(book, False)
+            self.current_step = 0
+            self.total_products_packaged = 0
+            self.sim_time = 0
+            self._orders_total = len(book)
+            return obs, {a: {} for a in AGENTS}
         n = num_orders if num_orders is not None else 30
         st = np.random.get_state()
         self._bind_stream()
@@ -254,6 +300,30 @@ class FJSPSimulation:
         self._viewcache = None
         obs = self._take_obs(self._packed.view)
         return obs, {a: {} for a in AGENTS}
+
+    def generate_order(self, num_products=None):
+        """FJSPSimulation.generate_order (FJSPSimulation.py:101-131): an order arrives in the running
+        episode, at the back of the pickup queue.  The draws come from numpy's global legacy RNG
+        on the host in the reference's order: randint(1, 10) only when num_products is None, then
+        the two three-way choices.  Returns the order (id, num_products, product_type,
+        packaging_color, arrival_time = sim_time).
+
+        Limits the reference does not have, from the closed form's order table: an episode holds at
+        most FJSP_MAX_ORDERS = 64 orders (RuntimeError on the 65th, before any draw) and an order
+        1..9 products (ValueError, before any draw)."""
+        from . import orders as O
+        if num_products is not None:
+            if isinstance(num_products, bool) or int(num_products) != num_products or not 1 <= int(num_products) <= 9:
+                raise ValueError(f"num_products must be an integer in 1..9, got {num_products!r}")
+        if self._orders_total >= O.MAX_ORDERS:
+            raise RuntimeError(f"the episode already holds FJSP_MAX_ORDERS = {O.MAX_ORDERS} orders")
+        n = int(np.random.randint(1, 10)) if num_products is None else int(num_products)
+        ptype = int(np.random.choice([1, 2, 3]))    # list(ProductType): SMALL, MEDIUM, BIG
+        colour = int(np.random.choice([1, 2, 3]))   # list(PackagingColor): RED, BLUE, GREEN
+        self._put_orders([(n, ptype, colour)], True)
+        order = GeneratedOrder(self._orders_total, n, ptype, colour, self.sim_time)
+        self._orders_total += 1
+        return order
 
     def _make_stepper(self):
         P = self._packed

@@ -17,7 +17,8 @@ LIB_PATH = os.environ.get("FJSP_LIB") or os.path.join(HERE, "libfjsp.so")
 SRC = os.path.join(HERE, "csrc", "fjsp_hip.hip")
 SRCS = [SRC, os.path.join(HERE, "csrc", "fjsp_policy.hip"), os.path.join(HERE, "csrc", "fjsp_group.hip"),
         os.path.join(HERE, "csrc", "fjsp_episode.hip")]
-HEADERS = [os.path.join(HERE, "csrc", h) for h in ("fjsp_env.h", "fjsp_select.h", "fjsp_stepdev.h", "fjsp_predraw.h", "fjsp_stamps.h")] + [
+HEADERS = [os.path.join(HERE, "csrc", h) for h in ("fjsp_env.h", "fjsp_select.h", "fjsp_stepdev.h", "fjsp_predraw.h", "fjsp_stamps.h",
+                                                     "fjsp_orders.h")] + [
     os.path.join(REPO, "include", "fjsp.h")]
 
 # the drop-in facade's host helper (CPython extension, no GPU code): csrc/fjsp_facade.c
@@ -81,7 +82,7 @@ EXPORTS = ["fjsp_abi_version", "fjsp_last_error", "fjsp_default_config", "fjsp_c
            "fjsp_kpi_carry_words", "fjsp_kpi_scan", "fjsp_step_held", "fjsp_actions",
            "fjsp_schedule_carry_words", "fjsp_schedule_temp_bytes", "fjsp_schedule_scan",
            "fjsp_step_sched", "fjsp_packaging_carry_words", "fjsp_packaging_ring_bytes",
-           "fjsp_packaging_temp_bytes", "fjsp_packaging_scan"]
+           "fjsp_packaging_temp_bytes", "fjsp_packaging_scan", "fjsp_put_orders"]
 POLICY_ACTOR_DPAD, POLICY_CRITIC_DPAD = 16, 48
 POLICY_ACTOR_FLOATS = 3 * 256 * 16 // 2 + 256 + 3 * 256 * 256 // 2 + 256 + 8 * 256 + 16
 POLICY_CRITIC_FLOATS = 3 * 256 * 48 // 2 + 256 + 3 * 256 * 256 // 2 + 256 + 3 * 128 * 256 // 2 + 128 + 128 + 16
@@ -174,6 +175,7 @@ def lib():
         "fjsp_state_bytes": (ctypes.c_int64, [P]),
         "fjsp_reset": (I, [P, P, P, I, ctypes.POINTER(fjsp_out)]),
         "fjsp_step": (I, [P, P, P, I, ctypes.POINTER(fjsp_out)]),
+        "fjsp_put_orders": (I, [P, P, I, P, P, I, P, ctypes.POINTER(fjsp_out)]),
         "fjsp_step_many": (I, [P, I, U64, U32, U32, I, I, ctypes.POINTER(fjsp_out)]),
         "fjsp_gae": (I, [P, P, P, P, I, I, I, D, D, P, P, P]),
         "fjsp_gae_f64": (I, [P, P, P, P, I, I, I, D, D, P, P, P]),

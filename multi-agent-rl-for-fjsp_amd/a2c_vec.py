@@ -1814,7 +1814,7 @@ class VecMultiAgentA2C:
 
     @torch.no_grad()
     def evaluate_kpis(self, num_orders=5, steps=500, seeds=None, deterministic=True, env=None, chunk=64,
-                      trace=False, schedule=False, packaging=False):
+                      trace=False, schedule=False, packaging=False, orders=None, counts=None):
         """The learned policy over `steps` vector steps from a reset with auto-reset (an env starts
         its next episode at once), every finished episode accounted twice on the device: returns
         and lengths (episodes.EpisodeLog) and the shop-floor KPIs (kpis.KpiLog: makespan, flow
@@ -1837,7 +1837,10 @@ class VecMultiAgentA2C:
 
         KPIs of the training rollouts themselves come from track_kpis=True (account_kpis /
         pop_kpis, learn()'s training_kpis): the collect then fills the same slabs for the batches
-        the update trains on, and no separate rollout is needed."""
+        the update trains on, and no separate rollout is needed.
+
+        orders / counts: the caller's order books ([K, N] words, orders.encode) for the first
+        episodes in place of the draw, as FJSPVecEnv's evaluation methods take them."""
         from .slablog import LogSet
         if packaging and not schedule:
             raise ValueError("packaging=True needs schedule=True: the pack words come with the held words")
@@ -1867,7 +1870,7 @@ class VecMultiAgentA2C:
             s["held"] = z(C, 3, N, dt=torch.int32)
         if packaging:
             s["pack"] = z(C, 4, N, dt=torch.int32)
-        env.reset(seeds=seeds, num_orders=num_orders)
+        env._open(seeds, num_orders, orders, counts)
         env.pack_a2c(s["feats"][0], s["masks"][0])
         keep = {k: [] for k in s if k not in ("feats", "masks", "status")} if trace else None
         L, h = nat.lib(), env.handle

@@ -9,6 +9,7 @@
 //   mt     u32 [N][624]           per-env MT19937 state (numpy legacy RandomState), env-major
 // Kernels: one lane per env, 64-lane workgroups (one wavefront; 4096 envs -> 64 CUs).
 //   k_reset      FJSPSimulation.reset (FJSPSimulation.py:286-323)
+//   k_put_orders the caller's order tables: a reset without the draw, or arrivals (fjsp_put_orders)
 //   k_step       FJSPSimulation.step  (FJSPSimulation.py:144-242), actions from HBM
 //   k_actions    the built-in policies' actions for the current state (fjsp_actions)
 //   k_step_many  K fused steps with on-device counter-RNG actions
@@ -24,6 +25,7 @@
 #include <type_traits>
 
 #include "fjsp_env.h"
+#include "fjsp_orders.h"
 #include "fjsp_select.h"
 #include "fjsp_stamps.h"
 #include "fjsp_stepdev.h"
@@ -94,6 +96,32 @@ __global__ void __launch_bounds__(BLOCK) k_reset(DevState S, Cfg C, const uint32
     if (seeds) { mt_seed(S.mt, e, seeds[e]); mti = 0; }
     E.set_mti(mti);
     env_reset(E, T, C, S, e, num_orders);
+    StoreSink sink{out.obs_i32, out.obs_i8, out.obs_f32, out.masks, 0u, (uint32_t)S.n, (uint32_t)e, out.feats};
+    observe(E, C, sink);
+    env_store(E, S.words, S.n, e);
+    if (out.status) out.status[e] = E.status();
+}
+
+// fjsp_put_orders: the caller's orders (u32 [K][N], env fastest) as the env's table (a reset without
+// the draw) or appended to it (arrivals between two steps); fjsp_orders.h put_orders_env.  An env it
+// rejects is left as it was and counted (one vector atomic per rejected lane; the rare path).
+__global__ void __launch_bounds__(BLOCK) k_put_orders(DevState S, Cfg C, const uint32_t* __restrict__ orders, int K,
+                                                      const int32_t* __restrict__ counts,
+                                                      const uint8_t* __restrict__ env_mask, int append,
+                                                      uint32_t* __restrict__ rejected, fjsp_out out) {
+    const int e = blockIdx.x * BLOCK + threadIdx.x;
+    if (e >= S.n) return;
+    if (env_mask && !env_mask[e]) return;
+    Tables T = tables_of(S, e);
+    Env E;
+    env_load(E, S.words, S.n, e);
+    const int count = counts ? counts[e] : K;
+    uint32_t pg = 0;
+    if (!put_orders_env(E, T, C, orders + e, S.n, K, count, append, &pg)) {
+        if (rejected) __hip_atomic_fetch_add(rejected, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    S.words[(size_t)PGW * S.n + e] = pg;
     StoreSink sink{out.obs_i32, out.obs_i8, out.obs_f32, out.masks, 0u, (uint32_t)S.n, (uint32_t)e, out.feats};
     observe(E, C, sink);
     env_store(E, S.words, S.n, e);
@@ -2339,6 +2367,24 @@ int fjsp_reset(fjsp_handle* h, const uint32_t* seeds, const uint8_t* env_mask, i
                        out ? *out : kNoOut);
     HIPCHK(hipGetLastError());
     h->has_reset = 1;
+    return 0;
+}
+
+int fjsp_put_orders(fjsp_handle* h, const uint32_t* orders, int32_t K, const int32_t* counts, const uint8_t* env_mask,
+                    int32_t append, uint32_t* rejected, const fjsp_out* out) {
+    if (!h) return fail("null handle");
+    // the arguments are checked before the handle is touched
+    if (K < 0 || K > MAX_ORDERS) return fail("fjsp_put_orders: K must be in 0..64");
+    if (!orders && K > 0) return fail("fjsp_put_orders: null orders with K > 0");
+    if (append != 0 && append != 1) return fail("fjsp_put_orders: append must be 0 or 1");
+    SERVER_QUIESCE(h);
+    if (append && !h->has_reset) return fail("fjsp_put_orders(append) before fjsp_reset");
+    DeviceGuard g(h->device);
+    dim3 grid((h->n + BLOCK - 1) / BLOCK);
+    hipLaunchKernelGGL(k_put_orders, grid, dim3(BLOCK), 0, h->stream, h->S, h->dcfg, orders, K, counts, env_mask, append,
+                       rejected, out ? *out : kNoOut);
+    HIPCHK(hipGetLastError());
+    if (!append) h->has_reset = 1;
     return 0;
 }
 

@@ -227,6 +227,57 @@ def kpi_summary(records, config=None):
                 "idle_with_work": idle}
 
 
+def best_of(records, samples, instances=None, env_id_base=0):
+    """Best-of-K selection over KPI records (a KPI_DTYPE array or KpiLog.pop()'s dict) of a run in
+    which env i * samples + r is replica r of instance i (FJSPVecEnv.solve).  Only each env's first
+    episode counts (end_step == length).  Per instance the terminated replica of least makespan
+    wins, ties going to the lowest env; if no replica terminated the winner is the one with the
+    most orders_completed, then the most packaged, then the lowest env, and the instance is not
+    solved.  instances: their number (None: as many as the records' highest env needs).
+
+    Returns best_env [I] (env index, without env_id_base), solved [I], makespan [I] (NaN where
+    unsolved), all_makespans [I, samples] (NaN where the replica did not terminate), index [I]
+    (the winner's row in `records`, -1 if it finished no episode) and records [I] (the winners'
+    records; zeros where index is -1).  Needs no GPU."""
+    recs = records["records"] if isinstance(records, dict) else np.asarray(records)
+    samples = int(samples)
+    if samples < 1:
+        raise ValueError("samples must be at least 1")
+    first = np.flatnonzero(recs["end_step"] == recs["length"])
+    env = recs["env_gid"][first].astype(np.int64) - int(env_id_base)
+    if instances is None:
+        instances = int(-(-(env.max() + 1) // samples)) if len(env) else 0
+    I = int(instances)
+    if len(env) and (env.min() < 0 or env.max() >= I * samples):
+        raise ValueError("a record's env lies outside instances * samples")
+    if len(np.unique(env)) != len(env):
+        raise ValueError("two first episodes of one env")
+    row = np.full(I * samples, -1, np.int64)
+    row[env] = first
+    have = row >= 0
+    term = np.zeros(I * samples, bool)
+    term[have] = (recs["flags"][row[have]] & FLAG_TERMINATED) != 0
+    span = np.full(I * samples, np.nan)
+    span[term] = recs["makespan"][row[term]]
+    done = np.full(I * samples, -1, np.int64)
+    packed = np.full(I * samples, -1, np.int64)
+    done[have], packed[have] = recs["orders_completed"][row[have]], recs["packaged"][row[have]]
+    span, term, done, packed = (x.reshape(I, samples) for x in (span, term, done, packed))
+    solved = term.any(axis=1)
+    best = np.zeros(I, np.int64)
+    for i in range(I):
+        if solved[i]:
+            best[i] = int(np.argmin(np.where(term[i], span[i], np.inf)))        # the first of equal minima
+        else:
+            best[i] = min(range(samples), key=lambda r: (-done[i, r], -packed[i, r], r))
+    best_env = np.arange(I) * samples + best
+    index = row[best_env] if I else np.zeros(0, np.int64)
+    winners = np.zeros(I, dtype=recs.dtype)
+    winners[index >= 0] = recs[index[index >= 0]]
+    return {"best_env": best_env, "solved": solved, "makespan": np.where(solved, span[np.arange(I), best], np.nan),
+            "all_makespans": span, "index": index, "records": winners}
+
+
 def carry_words():
     return int(nat.lib().fjsp_kpi_carry_words())
 
@@ -276,4 +327,4 @@ class KpiLog(EpisodeSlabLog):
 
 
 __all__ = ["kpi_reference", "kpi_summary", "KpiLog", "KPI_DTYPE", "TIMES_DTYPE", "HEAD_BYTES", "HEAD_FIELDS",
-           "CARRY_WORDS", "records_dict", "result_column", "carry_words"]
+           "CARRY_WORDS", "records_dict", "result_column", "carry_words", "best_of"]

@@ -157,6 +157,95 @@ class FJSPVecEnv:
         nat.check(nat.lib().fjsp_reset(self._h, _ptr(s), _ptr(m), self._num_orders, ctypes.byref(out)))
         return b
 
+    def put_orders(self, orders, counts=None, env_mask=None, append=False, buffers=None, check=True):
+        """Orders from the caller instead of the MT19937 draw (fjsp_put_orders, include/fjsp.h).
+
+        orders: [K, N] words (orders.encode; a tensor or anything np.asarray takes), counts [N] the
+        rows each env uses (None: K).  append=False: a reset with these orders as the episode's
+        table, the env's stream neither reseeded nor advanced; append=True: the orders arrive in
+        the running episode (ids norders.., the back of the pickup queue).  An env whose rows hold
+        an invalid word, whose count is outside 0..K or (append) would pass 64 orders is left as it
+        was and counted.  check=True reads that count (one synchronisation), raises ValueError
+        naming it if it is not 0 and returns the Buffers with the written envs' observation;
+        check=False returns the device counter (int32 [1]) without synchronising."""
+        self._sync_stream()
+        w = orders if isinstance(orders, torch.Tensor) else torch.as_tensor(np.asarray(orders).astype(np.int64))
+        w = w.to(device=self.device, dtype=torch.int64).bitwise_and(0xFFFFFFFF)
+        w = torch.where(w >= 2**31, w - 2**32, w).to(torch.int32).contiguous()
+        if w.dim() != 2 or w.shape[1] != self.num_envs or w.shape[0] > 64:
+            raise ValueError(f"orders must be [K, {self.num_envs}] with K <= 64, got {tuple(w.shape)}")
+        K = int(w.shape[0])
+        c = None
+        if counts is not None:
+            c = torch.as_tensor(counts, device=self.device).to(torch.int32).contiguous()
+            if tuple(c.shape) != (self.num_envs,):
+                raise ValueError(f"counts must be [{self.num_envs}], got {tuple(c.shape)}")
+        m = None
+        if env_mask is not None:
+            m = torch.as_tensor(env_mask, device=self.device).to(torch.uint8).contiguous()
+            if tuple(m.shape) != (self.num_envs,):
+                raise ValueError(f"env_mask must be [{self.num_envs}], got {tuple(m.shape)}")
+        b = buffers or Buffers(1, self.num_envs, self.device, infos=False)
+        out = b.struct()
+        rejected =torch.zeros(1, dtype=torch.int32, device=self.device)
+        nat.check(nat.lib().fjsp_put_orders(self._h, _ptr(w) if K else None, K, _ptr(c), _ptr(m), int(bool(append)),
+                                            _ptr(rejected), ctypes.byref(out)))
+        if not check:
+            return rejected
+        n = int(rejected.item())
+        if n:
+            raise ValueError(f"put_orders: {n} env(s) rejected (an invalid order word, a count outside 0..K or more "
+                             f"than 64 orders); they are unchanged")
+        return b
+
+    def reset_orders(self, orders, counts=None, env_mask=None, buffers=None, check=True):
+        """put_orders(append=False): FJSPSimulation.reset with the caller's orders."""
+        return self.put_orders(orders, counts, env_mask, False, buffers, check)
+
+    def add_orders(self, orders, counts=None, env_mask=None, buffers=None, check=True):
+        """put_orders(append=True): FJSPSimulation.generate_order calls between two steps."""
+        return self.put_orders(orders, counts, env_mask, True, buffers, check)
+
+    def _open(self, seeds, num_orders, orders, counts):
+        """The opening reset of the evaluation methods: reset(seeds, num_orders), or with the caller's
+        orders reset(seeds, num_orders=0) when seeds are given (it seeds the streams and draws
+        nothing) and reset_orders(orders, counts)."""
+        if orders is None:
+            if counts is not None:
+                raise ValueError("counts needs orders")
+            return self.reset(seeds=seeds, num_orders=num_orders)
+        if seeds is not None or self._pending_seeds is not None:
+            self.reset(seeds=seeds, num_orders=0)
+        return self.reset_orders(orders, counts)
+
+    def solve(self, books, samples, policy="masked", steps=None, action_seed=0, packaging=False):
+        """Best-of-`samples` schedules of caller-written order books: env i * samples + r is replica r
+        of books[i] (orders.encode's order tuples), so num_envs must be len(books) * samples.  Every
+        replica runs evaluate_schedule(orders=...) for `steps` vector steps (default
+        max_episode_steps + 1: every first episode ends) under `policy`, whose action stream is keyed
+        by the env id, and kpis.best_of picks each book's winner among the first episodes.  Returns
+        best_of's dict plus "ops" (and "pack_ops" with packaging=True): the winners' first-episode
+        records, as ScheduleLog.pop() / PackagingLog.pop() return them."""
+        from . import kpis as K
+        from . import orders as O
+        from . import schedule as S
+        books, samples = [list(b) for b in books], int(samples)
+        if samples < 1 or self.num_envs != len(books) * samples:
+            raise ValueError(f"solve needs num_envs == len(books) * samples, got {self.num_envs} envs for "
+                             f"{len(books)} books x {samples} samples")
+        words, counts = O.encode([b for b in books for _ in range(samples)])
+        steps = int(self.config.max_episode_steps) + 1 if steps is None else int(steps)
+        r = self.evaluate_schedule(policy=policy, steps=steps, action_seed=action_seed, packaging=packaging,
+                                   orders=words, counts=counts)
+        out = K.best_of(r["kpis"], samples, instances=len(books), env_id_base=self.env_id_base)
+        win = out["best_env"] + self.env_id_base
+        for name, as_dict in (("ops", S.records_dict), ("pack_ops", S.pack_records_dict)):
+            if name in r:
+                recs = r[name]["records"]
+                keep = np.isin(recs["env_gid"], win) & (recs["episode_start"] == 0)
+                out[name] = as_dict(recs[keep], r[name]["dropped"])
+        return out
+
     def actions(self, policy="heuristic", action_seed=0, step=0, out=None):
         """The actions rollout(policy=..., action_seed=..., step0=step) would draw for the current
         state at vector step `step` (fjsp_actions): uint8 [8, N], what step() takes."""
@@ -261,14 +350,17 @@ class FJSPVecEnv:
                                            int(step0), mode, int(bool(autoreset)), ctypes.byref(out)))
         return b
 
-    def evaluate(self, policy="heuristic", num_orders=5, max_steps=500, seeds=None, action_seed=0):
+    def evaluate(self, policy="heuristic", num_orders=5, max_steps=500, seeds=None, action_seed=0, orders=None,
+                 counts=None):
         """MultiAgentA2C.test (a2c.py:539-645) for every env at once: each env runs from a reset
         until its episode ends (term or trunc: the reference's `while env.agents`) or max_steps.
         Returns the reference's test() dict with one entry per env: steps, orders_completed,
         products_packaged, rewards_by_agent [8, N] (each agent's rewards summed in step order,
-        as episode_rewards) and total_reward (their sum in agent order, a2c.py:626)."""
-        import numpy as np
-        self.reset(seeds=seeds, num_orders=num_orders)
+        as episode_rewards) and total_reward (their sum in agent order, a2c.py:626).  orders / counts:
+        the caller's order books in place of the draw (_open; total_orders is then each env's count)."""
+        self._open(seeds, num_orders, orders, counts)
+        if orders is not None:
+            num_orders = np.asarray(torch.as_tensor(counts).cpu()) if counts is not None else int(len(orders))
         b = self.rollout(int(max_steps), action_seed=action_seed, policy=policy, autoreset=False, infos=True)
         done = (b.term | b.trunc).cpu().numpy().astype(bool)                  # [T, N]
         T = done.shape[0]
@@ -283,25 +375,28 @@ class FJSPVecEnv:
                 "products_packaged": pick(b.packaged), "total_orders": num_orders,
                 "rewards_by_agent": by_agent, "total_reward": np.cumsum(by_agent, axis=0)[-1]}
 
-    def evaluate_episodes(self, policy="heuristic", num_orders=5, steps=500, seeds=None, action_seed=0, chunk=256):
+    def evaluate_episodes(self, policy="heuristic", num_orders=5, steps=500, seeds=None, action_seed=0, chunk=256,
+                          orders=None, counts=None):
         """Every finished episode of every env over `steps` vector steps from a reset, with
         auto-reset (an env starts its next episode at once; a2c.py:346-381): rollout(chunk, ...)
         into one reused Buffers, each followed by EpisodeLog.scan on the device.  Returns
         EpisodeLog.pop()'s dict of records (env, length, end_step, total, by_agent [8, n], ...).
         Only the records reach the host; no reward slab is copied."""
-        return self._evaluate_logged(policy, num_orders, steps, seeds, action_seed, chunk, kpis=False)["episodes"]
+        return self._evaluate_logged(policy, num_orders, steps, seeds, action_seed, chunk, kpis=False, orders=orders,
+                                     counts=counts)["episodes"]
 
-    def evaluate_kpis(self, policy="heuristic", num_orders=5, steps=500, seeds=None, action_seed=0, chunk=256):
+    def evaluate_kpis(self, policy="heuristic", num_orders=5, steps=500, seeds=None, action_seed=0, chunk=256,
+                      orders=None, counts=None):
         """evaluate_episodes with the shop-floor KPIs beside the returns: the same loop, each chunk
         scanned into an EpisodeLog and a kpis.KpiLog (fjsp_kpi_scan over the chunk's result words,
         the stations' int8 observations, the infos and sim_time).  Returns {"episodes":
         EpisodeLog.pop(), "kpis": KpiLog.pop()}; record k of each describes the same episode
         (kpis.kpi_summary derives makespan, flow times, utilisation, ... from "kpis").  Only the
         records reach the host."""
-        return self._evaluate_logged(policy, num_orders, steps, seeds, action_seed, chunk)
+        return self._evaluate_logged(policy, num_orders, steps, seeds, action_seed, chunk, orders=orders, counts=counts)
 
     def evaluate_schedule(self, policy="heuristic", num_orders=5, steps=500, seeds=None, action_seed=0, chunk=256,
-                          packaging=False):
+                          packaging=False, orders=None, counts=None):
         """evaluate_kpis with the per-operation schedule beside it: from a reset, per vector step
         the policy's actions (fjsp_actions) and one fjsp_step_held into row k of a chunk slab, each
         chunk scanned into an EpisodeLog, a kpis.KpiLog and a schedule.ScheduleLog.  The states and
@@ -311,16 +406,18 @@ class FJSPVecEnv:
         schedule.PackagingLog with the same rows, and the result has "pack_ops" = its pop() (one
         record per tray run at a packaging station; schedule.check_packaging, schedule.arrivals)."""
         return self._evaluate_logged(policy, num_orders, steps, seeds, action_seed, chunk, schedule=True,
-                                     packaging=bool(packaging))
+                                     packaging=bool(packaging), orders=orders, counts=counts)
 
     def _evaluate_logged(self, policy, num_orders, steps, seeds, action_seed, chunk, kpis=True, schedule=False,
-                         packaging=False):
+                         packaging=False, orders=None, counts=None):
         """The loop behind evaluate_episodes / _kpis / _schedule: from a reset, chunks of rows into one
         reused Buffers, each scanned into a slablog.LogSet; returns its pop().  Two rollout paths,
         which launch different kernels: one fjsp_step_many per chunk, or with schedule per row the
-        policy's actions (fjsp_actions) and one fjsp_step_held / fjsp_step_sched."""
+        policy's actions (fjsp_actions) and one fjsp_step_held / fjsp_step_sched.  orders / counts: the
+        caller's order books for the first episodes in place of the draw (_open); later episodes are
+        drawn from the envs' streams with the envs' order counts."""
         steps, chunk = int(steps), max(1, min(int(chunk), int(steps)))
-        self.reset(seeds=seeds, num_orders=num_orders)
+        self._open(seeds, num_orders, orders, counts)
         logs = LogSet(self, steps, kpis=kpis, schedule=schedule, packaging=packaging)
         b = Buffers(chunk, self.num_envs, self.device, infos=True, held=schedule, pack=packaging)
         slabs = {name: getattr(b, name) for name in LogSet.SLABS}
