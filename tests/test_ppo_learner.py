@@ -3,113 +3,28 @@ formulas restated in float64, epoch 0 against A2C, the grouped path against the 
 epoch loop (target_kl, per-batch work done once) and the new entry's argument checks.
 
 The clipped objective is an extension (the reference has A2C only), so the yardsticks are a
-float64 restatement written out in this file and the A2C losses the project already pins to the
-reference.  The GPU version (the HIP loss head) is tests/test_gpu_ppo.py."""
+float64 restatement written out in tests/backward_ref.py and the A2C losses the project already
+pins to the reference.  The GPU version (the HIP loss head) is tests/test_gpu_ppo.py."""
 import ctypes
-import functools
 import importlib
 
 import numpy as np
 import pytest
 import torch
 
-from oracle import oracle as O
 from tests import gpu_util as G
+from tests.backward_ref import _oracle_batch, _reference_f64
 
 A = importlib.import_module("multi-agent-rl-for-fjsp_amd.a2c_vec")
 PPO = importlib.import_module("multi-agent-rl-for-fjsp_amd.ppo_vec")
-spec = importlib.import_module("multi-agent-rl-for-fjsp_amd.spec")
 
 EPS_CLIP = 0.2
 # every ratio at least 1 % away from a clip bound (0.8, 1.2): f32 rounding cannot flip a sample
 RATIOS = (0.5, 0.79, 0.9, 1.0, 1.1, 1.21, 1.6)
 
 
-@functools.lru_cache(maxsize=None)
-def _oracle_batch(T=24, N=6):
-    """A [T, ., N] batch from N oracle envs under masked-random actions (pre-step features and
-    masks, the actions taken), as test_a2c_learner._replay_obs builds one env's; returns and
-    advantages are random f64 (the update takes them as given)."""
-    idx = spec.a2c_feature_index()
-    feats = np.zeros((T, 38, N), np.float32)
-    masks = np.zeros((T, 29, N), np.int8)
-    acts = np.zeros((T, 8, N), np.uint8)
-    for e in range(N):
-        env = O.OracleEnv()
-        r = env.reset(seed=100 + e, num_orders=25)
-        for t in range(T):
-            flat = np.concatenate([r["obs_i32"], r["obs_i8"], r["obs_f32"]]).astype(np.float32)
-            feats[t, :, e] = flat[idx]
-            masks[t, :, e] = r["masks"]
-            acts[t, :, e] = O.actions(31, e, t, masks[t, :, e])
-            r = env.step(acts[t, :, e])
-            if r["term"] or r["trunc"]:
-                r = env.reset(num_orders=25)
-    gen = torch.Generator().manual_seed(17)
-    ret = torch.randn(T, 8, N, generator=gen, dtype=torch.float64)
-    adv = torch.randn(T, 8, N, generator=gen, dtype=torch.float64)
-    return torch.from_numpy(feats), torch.from_numpy(masks), torch.from_numpy(acts), ret, adv
-
-
 def _params(actors, critic):
     return list(actors.parameters()) + list(critic.parameters())
-
-
-def _reference_f64(actors, critic, feats, masks, acts, ret, adv, mean, std, logp_old, coef, eps_clip):
-    """The PPO losses, statistics and parameter gradients in float64, written out from the
-    definitions (no ppo_vec / a2c_vec loss code): per agent a padded MLP -> softmax over its valid
-    actions, entropy -sum p log(p + 1e-10), mask and renormalise (uniform over the valid actions if
-    nothing is left), log of the taken action's probability clamped to [eps32, 1 - eps32], the
-    clipped surrogate with the gradient cut on the samples the clip holds."""
-    T, _, N = feats.shape
-    S = T * N
-    f = feats.double().permute(1, 0, 2).reshape(38, S)
-    W = {k: v.detach().double().requires_grad_(True) for k, v in actors.named_parameters()}
-    C = [p.detach().double().requires_grad_(True) for p in critic.parameters()]
-    e32 = float(torch.finfo(torch.float32).eps)
-    out = {"loss": [], "ent": [], "kl": [], "clip": []}
-    total = 0.0
-    for a in range(8):
-        d, k, o, mo = A.OBS_DIMS[a], A.N_ACTIONS[a], A.OBS_OFFS[a], A.MASK_OFFS[a]
-        x = f[o:o + d]                                                      # [d, S]
-        h = torch.relu(W["W1"][a][:, :d] @ x + W["b1"][a])
-        h = torch.relu(W["W2"][a] @ h + W["b2"][a])
-        z = W["W3"][a][:k] @ h + W["b3"][a][:k]
-        p = torch.exp(z - z.max(0, keepdim=True).values)
-        p = p / p.sum(0, keepdim=True)                                       # [k, S]
-        ent = -(p * torch.log(p + 1e-10)).sum(0)
-        m = masks[:, mo:mo + k, :].double().permute(1, 0, 2).reshape(k, S)
-        pmk = p * m
-        tot = pmk.sum(0, keepdim=True)
-        q = torch.where(tot > 0, pmk / torch.where(tot > 0, tot, torch.ones_like(tot)), m / m.sum(0, keepdim=True))
-        q = q / q.sum(0, keepdim=True)
-        act = acts[:, a, :].long().reshape(1, S)
-        logp = torch.log(q.gather(0, act)[0].clamp(e32, 1 - e32))
-        adv_n = ((adv[:, a, :].float() - mean[a]) / (std[a] + 1e-8)).double().reshape(S)
-        dl = logp - logp_old[a].double()
-        r = torch.exp(dl)
-        hi_c = (adv_n > 0) & (r > 1 + eps_clip)
-        lo_c = (adv_n < 0) & (r < 1 - eps_clip)
-        surr = torch.where(hi_c, (1 + eps_clip) * adv_n, torch.where(lo_c, (1 - eps_clip) * adv_n, r * adv_n))
-        loss = -surr.sum() / S - coef * ent.sum() / S
-        total = total + loss
-        out["loss"].append(float(loss.detach()))
-        out["ent"].append(float(ent.detach().sum()))
-        out["kl"].append(float(((r - 1) - dl).detach().sum()))
-        out["clip"].append(int((hi_c | lo_c).sum()))
-        out.setdefault("cases", []).append(torch.stack([hi_c, lo_c, (adv_n > 0) & (r < 1 - eps_clip),
-                                                        (adv_n < 0) & (r > 1 + eps_clip),
-                                                        (r >= 1 - eps_clip) & (r <= 1 + eps_clip)]).sum(1))
-    v = f.t()
-    for i in range(0, 8, 2):
-        v = v @ C[i].t() + C[i + 1]
-        if i < 6:
-            v = torch.relu(v)
-    closs = ((v.reshape(T, 1, N) - ret.float().double()) ** 2).sum() / (8 * S)
-    (total + closs).backward()
-    out["critic"] = float(closs.detach())
-    out["grads"] = [W[k].grad for k, _ in actors.named_parameters()] + [c.grad for c in C]
-    return out
 
 
 def _constructed_logp_old(actors, feats, masks, acts, gidx, midx, seed=23):
