@@ -395,6 +395,53 @@ FJSP_DEV uint32_t pickup_execute(Env& E, const Tables& T, const Cfg& C, int acti
     return r;
 }
 
+// The pickup station ahead of the AGV's previous step (k_step_ag's E3 wave): step k+1's pickup
+// runs on the words after step k's pickup, before step k's AGV has acted on them (the
+// speculative pickup); pickup_compose then gives the words the plain order (AGV of step k, then
+// the pickup) ends with.  The AGV changes two of the pickup's words:
+//   * W5's pool, + 1, when it drops an empty tray at the pickup location (AgvPre::pool_add).
+//     pickup_execute reads the pool only as `pool > 0`, and only when a LOAD with an order at
+//     hand finds no tray on the station, so the two orders decide alike unless the pool was
+//     empty there and the AGV refilled it: that lane is `sensitive`, and its pickup is run
+//     again on the words after the AGV (its speculative run took nothing and pushed nothing,
+//     so it left no store behind).  Elsewhere the true pool is the speculative one + 1.
+//   * W7, L_PREADY, when a PICKUP pops its front.  The pickup's one list operation is a push
+//     at the tail, which commutes with a pop at the head: the true word is the push of the
+//     speculative slot onto the AGV's word.  With one tray listed before both, the
+//     speculative push linked the new slot behind that tray, and the plain order (pop, then
+//     push onto an empty list) writes no link: `unlink` says so, and pickup_unlink puts the
+//     byte back to what it held (the tail of a list links to NIL since its own push).
+// The pickup's W0 and W4, its result word and its status bits do not depend on the AGV at all.
+constexpr uint32_t PKS_PUSHED = 1u << 16;    // beside the result word: the speculative pickup pushed a tray,
+constexpr uint32_t PKS_POOL0 = 1u << 17;     //   its decision read an empty pool
+constexpr uint32_t PKS_POOL_ADD = 1u << 8;   // the AGV's delta: AgvPre::pool_add (W5's pool + 1)
+// asked of the words before the speculative pickup
+FJSP_DEV bool pickup_reads_empty_pool(const Env& E, int action) {
+    const bool ok_order = action == 1 && (E.cur_order() >= 0 || E.next_order() < E.norders());
+    return ok_order && !E.tray_valid() && E.pool() == 0;
+}
+struct PickupTrue {
+    uint32_t w5, w7;   // after the pickup in the plain order (not on a sensitive lane)
+    bool sensitive, unlink;
+};
+// sw5, sw7, flags: W5, W7 and PKS_PUSHED / PKS_POOL0 of the speculative pickup; pool_add and
+// w7_agv: the AGV's pool increment and its L_PREADY word (after its pop, if it popped)
+FJSP_DEV PickupTrue pickup_compose(uint32_t sw5, uint32_t sw7, uint32_t flags, uint32_t pool_add, uint32_t w7_agv) {
+    PickupTrue t;
+    t.sensitive = (flags & PKS_POOL0) != 0u && pool_add != 0u;
+    t.w5 = sw5 + pool_add;
+    const bool pushed = (flags & PKS_PUSHED) != 0u;
+    const uint32_t s = (sw7 >> 8) & 0xFFu, n = w7_agv >> 16;
+    t.w7 = pushed ? ((n == 0 ? s : (w7_agv & 0xFFu)) | (s << 8) | ((n + 1u) << 16)) : w7_agv;
+    t.unlink = pushed && n == 0 && (sw7 >> 16) == 2u;
+    return t;
+}
+// the link of the tray the AGV popped (the speculative word's head), on an `unlink` lane
+FJSP_DEV void pickup_unlink(const Tables& T, uint32_t sw7) {
+    const uint32_t h = sw7 & 0xFFu;
+    if (h != (uint32_t)NIL) T.snext[h * T.stride] = (uint8_t)NIL;
+}
+
 // FJSPSimulation.add_tray_to_packaging (FJSPSimulation.py:402-430): first station (dict order
 // blue_1, blue_2, red, green) whose colour matches and whose Resource has capacity; -1 = none
 // (the products are lost).  PackagingColor RED=1 BLUE=2 GREEN=3.

@@ -1093,16 +1093,20 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
 // ---------------------------------------------------------------- agent-group pipeline
 // k_step_ag: K fused steps (uniform-random actions, LDS tables, auto-reset with pre-drawn
 // tables), the env's agents split over the wavefronts of its 64-env workgroup.  Per step the
-// chains that stay sequential are  AGV (k) -> machines' actions (k) -> AGV (k+1)  and
-// AGV (k) -> pickup station (k+1) -> AGV (k+1); everything else hangs off them:
+// chain that stays sequential is  AGV (k) -> machines' actions (k) -> AGV (k+1); the pickup
+// station runs ahead of the AGV's previous step and takes that AGV's result in by a few
+// instructions (pickup_compose, fjsp_env.h); everything else hangs off them:
 //   AM owns every state word but the packaging ones.  At the top of step k it auto-resets the
 //      env once K has counted step k-1's order completions (FJSPSimulation.reset(seed=None)),
 //      applies the pickup and AGV results of step k (computed during step k-1; a lane that just
 //      reset, and the first step of a launch, runs those two agents here), runs the machines'
 //      actions (MachineAgent.py:99-139), posts the pickup / AGV words and the machine lists
 //      (release flag), then the machines' run phase (:151-169) and its half of the snapshot.
-//   E3 runs step k+1's pickup station (PickupStationAgent.py:146-248) on P's AGV result of
-//      step k, and posts it (release flag).
+//   E3 runs, in step k, step k+2's pickup station (PickupStationAgent.py:146-248) on its own
+//      words after step k+1's pickup, ahead of the AGV of step k+1; at the top of step k+1 it
+//      composes P's AGV result into it (a lane AM reset, a launch's first step and a lane whose
+//      pickup found the pool empty while that AGV refilled it run the pickup then, on AM's post /
+//      P's result) and posts it (release flag).
 //   P  runs step k+1's AGV (AGVAgent.py:180-368, a drop at packaging deferred): the half that
 //      needs only the AGV's own words (agv_pre: outcome, prefetch of the list front it would
 //      pop) at the top of the step, the rest (agv_fin) once AM's post and E3's pickup are in.
@@ -1113,7 +1117,7 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
 //      routed (FJSPSimulation.add_tray_to_packaging, with the in-flight counts before the run),
 //      the stations' actions and grants (:91-141) and the order completions
 //      (FJSPSimulation.py:245-258) — it needs only P's AGV result of the previous step.
-//   E0..E3 turn step k-1's snapshot into the outputs; E0 also draws step k+2's actions.
+//   E0..E2 turn step k-1's snapshot into the outputs; E0 also draws step k+3's actions.
 //   PD pre-draws the next order tables (predraw_wave).
 // The order words are shared by AM (processed bits) and K (packaged / complete bits): both OR
 // atomically (order_or); P and E3 read the static fields and the bits of the tray the AGV picks
@@ -1124,12 +1128,12 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
 // Waves w and w + 4 share a SIMD (two waves per SIMD issue VALU at twice one wave's rate): K
 // shares AM's (both busy early in the step; AM has the higher priority), P (the critical path
 // after AM's post, higher priority) shares the lightest emit wave's, PD and E3 pair up.
-// wave of each role: AM, P, E1, E2, K, E0, PD, E3 (waves w and w + 4 share a SIMD): AM+PD, P+E0,
-// E1+K, E2+E3 (0.6 % faster than AM+K, E1+PD; other pairings measured within noise)
-constexpr int AG_LAYOUT[8] = {0, 1, 2, 3, 6, 5, 4, 7};
-constexpr int AG_AM = AG_LAYOUT[0], AG_P = AG_LAYOUT[1], AG_E1 = AG_LAYOUT[2], AG_E2 = AG_LAYOUT[3], AG_K = AG_LAYOUT[4],
-              AG_E0 = AG_LAYOUT[5], AG_PD = AG_LAYOUT[6], AG_E3 = AG_LAYOUT[7];
-static_assert(AG_WAVES == 8, "one wave per role of AG_LAYOUT (AG_WAVES: fjsp_select.h)");
+// wave of each role: AM, P, E1, E2, K, E0, PD, E3 (waves w and w + 4 share a SIMD): AM+K, P+E0,
+// E1+PD, E2+E3.  With E3's pickup on the chain AM+PD, E1+K was 0.6 % faster; with the pickup two
+// steps ahead and the station masks on E0 and E1 it is 2 % slower (1.018 against 0.996 ms per
+// launch; P+K 1.000-1.011, AM+K with P+PD 1.008, E3+K 1.018, E3+PD 1.033: profiles/pickup_ahead/)
+constexpr int AG_AM = 0, AG_P = 1, AG_E1 = 2, AG_E2 = 3, AG_E0 = 5, AG_E3 = 7;   // K and PD: 4 and 6 (AgSplit)
+static_assert(AG_WAVES == 8, "one wave per role (AG_WAVES: fjsp_select.h)");
 // packaging-owned state words (K): W1, W13..W16 (packaging run lists), W20..W29
 constexpr uint32_t K_WORDS = (1u << 1) | (0xFu << 13) | (0x3FFu << 20);
 // masks per emit wave: pickup [0,3) | the AGV's pickup / drop [9,11) | the AGV's moves [3,9),
@@ -1142,12 +1146,29 @@ constexpr uint32_t K_WORDS = (1u << 1) | (0xFu << 13) | (0x3FFu << 20);
 // last wave: E3 and E0 were (87 % / 82 % of the steps), so the AGV's move masks went from E3 to E2
 // and one of E0's two stations back to E3: 1.236 -> 1.215 ms per 1 024-step launch; none of
 // E0's stations, or one / two stations on E1: 1.234 / 1.219 / 1.225-1.255 (profiles/agv_resolve/)
-constexpr int AG_E0ST = 1;
-constexpr uint32_t AG_E0ST_BITS = ((1u << (3 * AG_E0ST)) - 1u) << 11;
-constexpr uint32_t AG_MASKS_E0 = 0x7u | AG_E0ST_BITS, AG_MASKS_E2 = (0x3u << 9) | (0x3Fu << 3),
-                   AG_MASKS_E3 = (0x3FFFFu << 11) & ~AG_E0ST_BITS;
-static_assert((AG_MASKS_E0 | AG_MASKS_E2 | AG_MASKS_E3) == (1u << NMASK) - 1u && !(AG_MASKS_E0 & AG_MASKS_E2) &&
-              !(AG_MASKS_E0 & AG_MASKS_E3) && !(AG_MASKS_E2 & AG_MASKS_E3), "mask split");
+// With the pickup station two steps ahead E3 composes the AGV's result and posts before its
+// pickup, and with its 15 mask fields it was last again (94 % of the steps, busy 2 731 of the
+// step's 2 924 cycles): the machines' masks go to E0 and the packaging stations' (AG_E1ST) to E1,
+// so E3 emits nothing and reads no snapshot.  ms per 1 024-step launch, E0 / E1 / E2 stations,
+// parent 1.023: 2/3/1 1.018, 1/3/2 1.044, 1/2/3 1.092 (E2 shares E3's SIMD); in the AM+K layout
+// below 2/3/1 0.996, 3/3/0 0.998, 3/2/1 0.994, 2/4/0 0.987 (profiles/pickup_ahead/)
+// The split and the SIMD pairing by envs per workgroup (G = BLOCK / EPW lane groups): at 32 and 64
+// envs AM+K was slower than the parent (ag_envs 64: 1.288 against 1.226-1.233 ms) and AM+PD, E1+K
+// with the same masks is level or faster (32: 1.109 against 1.107-1.115; 64: 1.214; 16 384 envs:
+// 1.543 against 1.629-1.646)
+template <bool AMK, int E0ST, int E1ST>
+struct AgSplitOf {
+    static constexpr bool AM_K = AMK;   // K shares AM's SIMD and PD E1's, or the other way round
+    static constexpr uint32_t E0ST_BITS = ((1u << (3 * E0ST)) - 1u) << 11, E1ST_BITS = ((1u << (3 * E1ST)) - 1u) << (11 + 3 * E0ST);
+    static constexpr uint32_t MASKS_E0 = 0x7u | E0ST_BITS, MASKS_E1 = E1ST_BITS, MASKS_E2 = (0x3u << 9) | (0x3Fu << 3),
+                              MASKS_E3 = (0x3FFFFu << 11) & ~(E0ST_BITS | E1ST_BITS);
+    static_assert(E0ST + E1ST <= 6, "two machines and four packaging stations");
+    static_assert((MASKS_E0 | MASKS_E1 | MASKS_E2 | MASKS_E3) == (1u << NMASK) - 1u &&
+                  __builtin_popcount(MASKS_E0) + __builtin_popcount(MASKS_E1) + __builtin_popcount(MASKS_E2) +
+                  __builtin_popcount(MASKS_E3) == NMASK, "mask split");
+};
+template <int G> struct AgSplit : AgSplitOf<false, 2, 4> {};
+template <> struct AgSplit<4> : AgSplitOf<true, 2, 4> {};
 // snapshot slot words (PipeSnap, 32 per lane): AM writes q[0..3], K q[4..7]
 enum : int { SA_W0 = 0, SA_ST, SA_W4, SA_W5, SA_W6, SA_L0, SA_M0 = SA_L0 + 6, SA_M1, SA_R01, SA_R23,
              SK_W1 = 16 };
@@ -1255,16 +1276,16 @@ __device__ __forceinline__ void ag_emit(const uint32_t* v, uint32_t t, uint32_t 
                      g8 + C.lut[reward_index(a, r & 0xFFu, (int)((r >> 8) & 0xFu))]);
             }
         }
-        FieldSink<0u, 0u, 0u, AG_MASKS_E0> ps{sink};
+        FieldSink<0u, 0u, 0u, AgSplit<G>::MASKS_E0> ps{sink};
         observe(E, C, ps);
     } else if (part == 1) {
-        FieldSink<(1u << NI32) - 1u, 0u, (1u << NF32) - 1u, 0u> ps{sink};
+        FieldSink<(1u << NI32) - 1u, 0u, (1u << NF32) - 1u, AgSplit<G>::MASKS_E1> ps{sink};
         observe(E, C, ps);
     } else if (part == 3) {
-        FieldSink<0u, 0u, 0u, AG_MASKS_E3> ps{sink};
+        FieldSink<0u, 0u, 0u, AgSplit<G>::MASKS_E3> ps{sink};
         observe(E, C, ps);
     } else {
-        FieldSink<0u, (1u << NI8) - 1u, 0u, AG_MASKS_E2> ps{sink};
+        FieldSink<0u, (1u << NI8) - 1u, 0u, AgSplit<G>::MASKS_E2> ps{sink};
         observe(E, C, ps);
         const int nord = E.norders();
         const int all_done = E.ncompleted() == nord && nord > 0 && E.next_order() == nord;
@@ -1284,6 +1305,7 @@ template <int EPW, bool STALL = false>
 __global__ void __launch_bounds__(AG_WAVES * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 2)))
 k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step0, int autoreset, fjsp_out out) {
     static_assert(EPW == 64 || EPW == 32 || EPW == 16, "envs per workgroup");
+    constexpr int AG_K = AgSplit<BLOCK / EPW>::AM_K ? 4 : 6, AG_PD = AgSplit<BLOCK / EPW>::AM_K ? 6 : 4;
     FJSP_DIAG(
     const uint64_t t_entry = __builtin_amdgcn_s_memtime();
     )
@@ -1298,7 +1320,7 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
     __shared__ uint8_t s_next[MAX_SLOTS * BLOCK];
     __shared__ uint16_t s_cstep[MAX_SLOTS * BLOCK];
     __shared__ PipeSnap snap[2];
-    __shared__ uint32_t s_act[3][2][BLOCK];   // step k's actions in slot k % 3 (E0 draws two steps ahead)
+    __shared__ uint32_t s_act[4][2][BLOCK];   // step k's actions in slot k & 3 (E0 draws three steps ahead)
     // hand-off slots are lane-major uint4 groups (one 16-byte LDS access per 4 words)
     __shared__ uint4 s_p1[2][2][BLOCK];   // AM post 1 (P1_*), by step parity
     __shared__ uint4 s_p2[BLOCK];         // AM post 2: W9..W12 (machine lists) after the machines' actions
@@ -1322,8 +1344,8 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
     FJSP_DIAG(uint64_t ag_busy = 0, ag_wait = 0;   // per step: busy until the barrier; AM: until post 1, K / P: spinning
               uint64_t amt[6] = {0, 0, 0, 0, 0, 0};   // AM: cycles into the step at its phase marks
               uint64_t ag_last = 0;)                   // steps this wave arrived last at the barrier
-    if (wave == AG_P) {   // the first two steps' actions
-        for (int j = 0; j < 2 && j < K; j++) {
+    if (wave == AG_P) {   // the first three steps' actions
+        for (int j = 0; j < 3 && j < K; j++) {
             int act[NA];
             synth_uniform(seed, gid0 + (uint32_t)e, step0 + (uint32_t)j, act);
             s_act[j][0][lane] = pack_actions(act, 0);
@@ -1333,6 +1355,17 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
     if (threadIdx.x == 0) { s_flag1 = 0; s_uflag = 0; s_abort = 0; s_cap = aux_words(S)[AUX_SPIN_CAP]; }
     auto ag_spin = [&](uint32_t* flag, uint32_t v) __attribute__((always_inline)) {
         spin_until(flag, v, &s_abort, &s_cap);
+    };
+    // two flags expected to be up already: both loads in flight together, one acquire behind them
+    auto ag_spin2 = [&](uint32_t* f1, uint32_t* f2, uint32_t v) __attribute__((always_inline)) {
+        const uint32_t a = __hip_atomic_load(f1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const uint32_t b = __hip_atomic_load(f2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (__builtin_amdgcn_readfirstlane((a ^ v) | (b ^ v)) == 0u) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            return;
+        }
+        spin_until(f1, v, &s_abort, &s_cap);
+        spin_until(f2, v, &s_abort, &s_cap);
     };
     if (valid) {
         // the env's order table, used slot prefix and pre-drawn table live in LDS for the launch
@@ -1445,8 +1478,8 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
             if (valid) {
                 kc = s_kpost[(k - 1) & 1][lane];
                 if (k < K) {
-                    a0 = s_act[k % 3][0][lane];
-                    a1 = s_act[k % 3][1][lane];
+                    a0 = s_act[k & 3][0][lane];
+                    a1 = s_act[k & 3][1][lane];
                     q_get(&s_res[k & 1][0][lane], 4, rs);
                 }
             }
@@ -1580,7 +1613,7 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
                 }
                 if (kvalid) {
                     const int step = E.step();
-                    const uint32_t a1 = s_act[k % 3][1][el];
+                    const uint32_t a1 = s_act[k & 3][1][el];
                     if constexpr (G == 1) {   // one lane per env: the four stations in turn
                         const int tp0 = E.total_packaged();
                         // completions due this step (NORMAL events older than the step's actions)
@@ -1671,7 +1704,7 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
         for (int k = 0; k <= K; k++) {
             AG_T0();
             if (k + 1 < K) {   // step k + 1's AGV: its own half now, the rest on AM's post and E3's pickup
-                const int act1 = (int)((s_act[(k + 1) % 3][0][lane] >> 8) & 0xFFu);
+                const int act1 = (int)((s_act[(k + 1) & 3][0][lane] >> 8) & 0xFFu);
                 AG_MARK(0);
                 const bool fresh = ag_fresh(k, valid, s_p1, s_kpost, lane, C, autoreset);
                 AG_SPIN_T0();
@@ -1696,8 +1729,10 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
                 }
                 ag_pin(pre);   // computed here, in the idle window before the waits
                 AG_MARK(2);
-                if (!wait_first) ag_spin(&s_flag1, (uint32_t)(k + 1));
-                ag_spin(&s_uflag, (uint32_t)(k + 1));
+                // E3 posted step k+1's pickup at the top of this step (composed from the one it ran
+                // ahead in step k-1; behind AM's post on a lane AM reset): long there by now
+                if (wait_first) ag_spin(&s_uflag, (uint32_t)(k + 1));
+                else ag_spin2(&s_flag1, &s_uflag, (uint32_t)(k + 1));
                 AG_SPIN_ACC();
                 AG_MARK(3);
                 if (valid) {
@@ -1714,7 +1749,9 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
                     AG_MARK(4);
 #pragma unroll
                     for (int i = 0; i < 7; i++) sa[i] = Ea.w[6 + i];
-                    const uint32_t rs[16] = {pk.x >> 24, pk.y, Ea.w[5], Ea.w[6], Ea.w[7], Ea.w[8], Ea.w[9],
+                    // RS_NO's word carries the AGV's pool increment (PKS_POOL_ADD) above next_order's
+                    // 8 bits, for E3's compose; AM shifts it out
+                    const uint32_t rs[16] = {(pk.x >> 24) | pre.pool_add, pk.y, Ea.w[5], Ea.w[6], Ea.w[7], Ea.w[8], Ea.w[9],
                                              Ea.w[10], Ea.w[11], Ea.w[12], pr.x, r1, pr.y | Ea.w[2], 0u, 0u, pend};
                     q_put(&s_res[(k + 1) & 1][0][lane], 4, rs);
                 }
@@ -1726,10 +1763,10 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
     } else if (wave == AG_PD) {
         predraw_wave<CR, PB, true, true, EPW == 16>(S, K, lane, e, valid, (size_t)blk * EPW, s_mb, s_cp, s_nxt);
     } else {
-        // E0: step k+2's actions, rewards, the pickup's masks; E1: int32 and float32 fields; E2:
-        // int8 fields, term, trunc, status, the AGV's masks; E3: step k+1's pickup
-        // station (for P), the other masks (balanced by measured cycles: scripts/diag_ag_stamps.py;
-        // E0 shares P's SIMD)
+        // E0: step k+3's actions, rewards, the pickup's and the machines' masks; E1: int32 and
+        // float32 fields, the packaging stations' masks; E2: int8 fields, term, trunc, status, the
+        // AGV's masks; E3: the pickup station (for P), and the masks AgSplit leaves it: none
+        // (balanced by measured cycles: scripts/diag_ag_stamps.py; E0 shares P's SIMD)
         // The role is a compile-time value: four instances of the loop, selected once per wave, so
         // each role reads only the snapshot words and the output pointers it uses.
         auto emit_loop = [&](auto role) __attribute__((always_inline)) {
@@ -1741,42 +1778,77 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
             const uint32_t n = (uint32_t)ea->S.n;
             const uint64_t eseed = ea->seed;
             const uint32_t egid = ea->gid0 + (uint32_t)e, estep = ea->step0;
+            // E3: W0, W4, W5, W7, the result word | PKS_* and the status bits of its latest pickup
+            // (at the top of step k that of step k+1, run in step k-1 ahead of the AGV of step k)
+            uint4 q = make_uint4(0u, 0u, 0u, 0u);
+            uint2 qr = make_uint2(0u, 0u);
             for (int k = 0; k <= K; k++) {
                 AG_T0();
-                if (part == 3 && k + 1 < K) {   // step k+1's pickup station, from P's AGV result of step k
+                if (part == 3 && k + 1 < K) {
+                    // Step k+1's pickup for P: the one run ahead composed with P's AGV result of step
+                    // k (pickup_compose), which costs a few instructions where the pickup itself cost
+                    // P its longest wait.  A lane AM reset (and a launch's first step) and a sensitive
+                    // lane run the pickup here, on AM's post / on P's result.
+                    // this step's inputs, read together (every lane: the slots are BLOCK wide)
+                    uint32_t rs[8];
+                    q_get(&s_res[k & 1][0][lane], 2, rs);   // RS_NO, RS_W4, RS_W5..: W5, W6, W7
+                    const uint32_t a2 = s_act[(k + 2) & 3][0][lane];
                     const bool fresh = ag_fresh(k, valid, s_p1, s_kpost, lane, C, autoreset);
-                    if (__ballot(valid && fresh) != 0) ag_spin(&s_flag1, (uint32_t)(k + 1));
-                    AG_MARK(3);
+                    bool slow = valid && fresh;
+                    if (valid && !fresh) {
+                        const PickupTrue pt = pickup_compose(q.z, q.w, qr.x, rs[RS_NO] & PKS_POOL_ADD, rs[RS_W5 + 2]);
+                        if (pt.unlink) pickup_unlink(TL, q.w);
+                        q.z = pt.w5; q.w = pt.w7;
+                        slow = pt.sensitive;
+                    }
+                    if (__ballot(slow) != 0) {   // rare: a reset, a launch's first step
+                        if (__ballot(valid && fresh) != 0) ag_spin(&s_flag1, (uint32_t)(k + 1));
+                        if (slow) {
+                            Env Ep;
+#pragma unroll
+                            for (int i = 0; i < NSTATE; i++) Ep.w[i] = 0u;
+                            if (fresh) {
+                                uint32_t p1[8];
+                                q_get(&s_p1[k & 1][0][lane], 2, p1);
+                                Ep.w[0] = p1[P1_W0]; Ep.w[4] = p1[P1_W4]; Ep.w[5] = p1[P1_W5]; Ep.w[7] = p1[P1_W7];
+                            } else {
+                                Ep.w[0] = (s_p1[(k - 1) & 1][0][lane].x & 0x00FFFFFFu) | (rs[RS_NO] << 24);
+                                Ep.w[4] = rs[RS_W4]; Ep.w[5] = rs[RS_W5]; Ep.w[7] = rs[RS_W5 + 2];
+                            }
+                            const int act0 = (int)(s_act[(k + 1) & 3][0][lane] & 0xFFu);
+                            const uint32_t r0 = (pickup_execute(Ep, TL, C, act0) & 0xFFu) | ((uint32_t)act0 << 8);
+                            q = make_uint4(Ep.w[0], Ep.w[4], Ep.w[5], Ep.w[7]);
+                            qr = make_uint2(r0, Ep.w[2]);
+                        }
+                    }
                     if (valid) {
+                        s_pk[lane] = q;
+                        s_pkr[lane] = make_uint2(qr.x & 0xFFFFu, qr.y);
+                        __hip_atomic_store(&s_uflag, (uint32_t)(k + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                    AG_MARK(3);
+                    // step k+2's pickup, ahead of the AGV of step k+1 that P resolves in this step
+                    if (valid && k + 2 < K) {
                         Env Ep;
 #pragma unroll
                         for (int i = 0; i < NSTATE; i++) Ep.w[i] = 0u;
-                        if (fresh) {
-                            uint32_t p1[8];
-                            q_get(&s_p1[k & 1][0][lane], 2, p1);
-                            Ep.w[0] = p1[P1_W0]; Ep.w[4] = p1[P1_W4]; Ep.w[5] = p1[P1_W5]; Ep.w[7] = p1[P1_W7];
-                        } else {
-                            uint32_t rs[16];
-                            q_get(&s_res[k & 1][0][lane], 2, rs);   // RS_NO, RS_W4, RS_W5..: W5, W6, W7
-                            Ep.w[0] = (s_p1[(k - 1) & 1][0][lane].x & 0x00FFFFFFu) | (rs[RS_NO] << 24);
-                            Ep.w[4] = rs[RS_W4]; Ep.w[5] = rs[RS_W5]; Ep.w[7] = rs[RS_W5 + 2];
-                        }
-                        const int act0 = (int)(s_act[(k + 1) % 3][0][lane] & 0xFFu);
+                        Ep.w[0] = q.x; Ep.w[4] = q.y; Ep.w[5] = q.z; Ep.w[7] = q.w;
+                        const int act0 = (int)(a2 & 0xFFu);
+                        const uint32_t f0 = pickup_reads_empty_pool(Ep, act0) ? PKS_POOL0 : 0u;
                         const uint32_t r0 = (pickup_execute(Ep, TL, C, act0) & 0xFFu) | ((uint32_t)act0 << 8);
+                        qr = make_uint2(r0 | f0 | (Ep.w[7] != q.w ? PKS_PUSHED : 0u), Ep.w[2]);
+                        q = make_uint4(Ep.w[0], Ep.w[4], Ep.w[5], Ep.w[7]);
                         AG_MARK(4);
-                        s_pk[lane] = make_uint4(Ep.w[0], Ep.w[4], Ep.w[5], Ep.w[7]);
-                        s_pkr[lane] = make_uint2(r0, Ep.w[2]);
-                        __hip_atomic_store(&s_uflag, (uint32_t)(k + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                     }
                 }
                 AG_MARK(0);
-                if (part == 0 && k + 2 < K) {   // E0 draws step k + 2's actions (uniform random)
+                if (part == 0 && k + 3 < K) {   // E0 draws step k + 3's actions (uniform random)
                     int act[NA];
-                    synth_uniform(eseed, egid, estep + (uint32_t)(k + 2), act);
-                    s_act[(k + 2) % 3][0][lane] = pack_actions(act, 0);
-                    s_act[(k + 2) % 3][1][lane] = pack_actions(act, 4);
+                    synth_uniform(eseed, egid, estep + (uint32_t)(k + 3), act);
+                    s_act[(k + 3) & 3][0][lane] = pack_actions(act, 0);
+                    s_act[(k + 3) & 3][1][lane] = pack_actions(act, 4);
                 }
-                if (k > 0 && valid) {
+                if (k > 0 && valid && !(part == 3 && AgSplit<BLOCK / EPW>::MASKS_E3 == 0u)) {   // (E3 with no masks left emits nothing)
                     const uint32_t t = (uint32_t)(k - 1);
                     uint32_t v[SNAP_N];
                     snap_get(snap[(k - 1) & 1], lane, v);
