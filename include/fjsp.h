@@ -453,6 +453,46 @@ int fjsp_step_held(fjsp_handle* h, const uint8_t* actions, const uint8_t* agent_
 int fjsp_actions(fjsp_handle* h, int32_t action_mode, uint64_t action_seed, uint32_t env_gid0, uint32_t step,
                  uint8_t* actions);
 
+/* The perturbed heuristic (a search's base policy; not a fjsp_step_many mode).  With
+ *   h  = fmix64(action_seed ^ fmix64(((uint64)(env_gid0 + e) << 32) | step))     (fjsp_step_many's word)
+ *   h2 = fmix64(h ^ 0x9E3779B97F4A7C15)
+ * agent a of env e takes FJSP_ACTIONS_MASKED's draw from h if ((h2 >> 8a) & 0xFF) < eps8, and
+ * MultiAgentA2C._get_heuristic_actions' action (a2c.py:390-537) otherwise: epsilon = eps8 / 256, eps8 in
+ * 0..256 (anything else is an error); eps8 = 0 is FJSP_ACTIONS_HEURISTIC and eps8 = 256
+ * FJSP_ACTIONS_MASKED byte for byte.  Same contract as fjsp_actions: reads the state only, actions =
+ * device u8 [8][N]. */
+int fjsp_actions_eps(fjsp_handle* h, int32_t eps8, uint64_t action_seed, uint32_t env_gid0, uint32_t step,
+                     uint8_t* actions);
+
+/* End records of fjsp_search_rollout: five device arrays of N entries each, none NULL. */
+typedef struct fjsp_search_end {
+    int32_t* steps;             /* k + 1 at the lane's first step that reported term or trunc; -1: none
+                                   within K, or the lane was inactive */
+    uint8_t* flags;             /* of that step: bit 0 terminated, bit 1 truncated */
+    int32_t* orders_completed;  /* the infos of the lane's last executed step */
+    int32_t* packaged;
+    double* sim_time;
+} fjsp_search_end;
+#define FJSP_SEARCH_TERM 1
+#define FJSP_SEARCH_TRUNC 2
+
+/* One launch that runs every active env from its current state to the end of its episode, the way
+ * MultiAgentA2C.test runs one env (a2c.py:539-645: `while env.agents`, no reset in between), under
+ * a script and then the perturbed heuristic (a2c.py:390-537 with fjsp_actions_eps' coins).  Per
+ * active env e, for k = 0 .. K - 1: the actions are script[k][:, e] while k < script_len[e] (script
+ * = device u8 [L][8][N] or NULL; script_len = device i32 [N], clamped to 0..L, or NULL = L for every
+ * env) and fjsp_actions_eps(eps8, action_seed, env_gid0, step_base + t0 + k) of the env's current
+ * state after that; they are stored to trace[k][:, e] (device u8 [K][8][N]) and one FJSPSimulation.step
+ * without auto-reset follows.  The env stops at its first step that reports terminated or truncated
+ * and is not stepped again; trace rows past its stop are not written.  end: see fjsp_search_end.
+ * active = device u8 [N] or NULL (= all); an inactive env is untouched and gets steps = -1 only.
+ * The env state is left as the env left it.  No observation or reward is produced.  Errors (K <= 0,
+ * eps8 outside 0..256, t0 < 0, a NULL trace or end array, a call before a reset) are found before
+ * anything is launched. */
+int fjsp_search_rollout(fjsp_handle* h, int32_t K, int32_t eps8, uint64_t action_seed, uint32_t env_gid0,
+                        uint32_t step_base, int32_t t0, const uint8_t* script, int32_t L, const int32_t* script_len,
+                        const uint8_t* active, uint8_t* trace, fjsp_search_end* end);
+
 /* One record per operation (32 bytes = 2 x 16).  Steps are 0-based within the episode; an
  * operation lasts (end - start) * step_size. */
 #define FJSP_OP_REC_BYTES 32

@@ -18,7 +18,7 @@ SRC = os.path.join(HERE, "csrc", "fjsp_hip.hip")
 SRCS = [SRC, os.path.join(HERE, "csrc", "fjsp_policy.hip"), os.path.join(HERE, "csrc", "fjsp_group.hip"),
         os.path.join(HERE, "csrc", "fjsp_episode.hip")]
 HEADERS = [os.path.join(HERE, "csrc", h) for h in ("fjsp_env.h", "fjsp_select.h", "fjsp_stepdev.h", "fjsp_predraw.h", "fjsp_stamps.h",
-                                                     "fjsp_orders.h")] + [
+                                                     "fjsp_orders.h", "fjsp_search.h")] + [
     os.path.join(REPO, "include", "fjsp.h")]
 
 # the drop-in facade's host helper (CPython extension, no GPU code): csrc/fjsp_facade.c
@@ -66,6 +66,13 @@ class fjsp_env_view(ctypes.Structure):
         ("status", ctypes.c_uint32), ("orders", ctypes.c_uint32 * 64)]
 
 
+SEARCH_END_FIELDS = ["steps", "flags", "orders_completed", "packaged", "sim_time"]
+
+
+class fjsp_search_end(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in SEARCH_END_FIELDS]
+
+
 # every symbol include/fjsp.h declares (checked by tests/test_abi.py)
 EXPORTS = ["fjsp_abi_version", "fjsp_last_error", "fjsp_default_config", "fjsp_check_config",
            "fjsp_default_reward_weights", "fjsp_set_reward_weights",
@@ -82,7 +89,8 @@ EXPORTS = ["fjsp_abi_version", "fjsp_last_error", "fjsp_default_config", "fjsp_c
            "fjsp_kpi_carry_words", "fjsp_kpi_scan", "fjsp_step_held", "fjsp_actions",
            "fjsp_schedule_carry_words", "fjsp_schedule_temp_bytes", "fjsp_schedule_scan",
            "fjsp_step_sched", "fjsp_packaging_carry_words", "fjsp_packaging_ring_bytes",
-           "fjsp_packaging_temp_bytes", "fjsp_packaging_scan", "fjsp_put_orders"]
+           "fjsp_packaging_temp_bytes", "fjsp_packaging_scan", "fjsp_put_orders", "fjsp_actions_eps",
+           "fjsp_search_rollout"]
 POLICY_ACTOR_DPAD, POLICY_CRITIC_DPAD = 16, 48
 POLICY_ACTOR_FLOATS = 3 * 256 * 16 // 2 + 256 + 3 * 256 * 256 // 2 + 256 + 8 * 256 + 16
 POLICY_CRITIC_FLOATS = 3 * 256 * 48 // 2 + 256 + 3 * 256 * 256 // 2 + 256 + 3 * 128 * 256 // 2 + 128 + 128 + 16
@@ -222,6 +230,8 @@ def lib():
         "fjsp_kpi_scan": (I, [P, P, P, P, P, P, P, I, I, U32, ctypes.c_int64, P, P, ctypes.c_int64, P, P, U64, P]),
         "fjsp_step_held": (I, [P, P, P, I, ctypes.POINTER(fjsp_out), P]),
         "fjsp_actions": (I, [P, I, U64, U32, U32, P]),
+        "fjsp_actions_eps": (I, [P, I, U64, U32, U32, P]),
+        "fjsp_search_rollout": (I, [P, I, I, U64, U32, U32, I, P, I, P, P, P, ctypes.POINTER(fjsp_search_end)]),
         "fjsp_schedule_carry_words": (I, []),
         "fjsp_schedule_temp_bytes": (I, [I, I, ctypes.POINTER(U64)]),
         "fjsp_schedule_scan": (I, [P, P, P, P, I, I, U32, ctypes.c_int64, P, P, ctypes.c_int64, P, P, U64, P]),

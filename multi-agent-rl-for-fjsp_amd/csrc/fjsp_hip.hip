@@ -13,6 +13,8 @@
 //   k_step       FJSPSimulation.step  (FJSPSimulation.py:144-242), actions from HBM
 //   k_actions    the built-in policies' actions for the current state (fjsp_actions)
 //   k_step_many  K fused steps with on-device counter-RNG actions
+//   k_actions_eps / k_search_rollout  the perturbed heuristic's actions; every lane to the end of its
+//                episode in one launch, traces and end records only (fjsp_search.h, search.py)
 //   k_gae        transition_memory.py:83-105 (returns + GAE), one lane per (agent, env) column
 // Compiled with -ffp-contract=off: rewards and GAE follow Python's unfused fp64 op order.
 #include <hip/hip_runtime.h>
@@ -155,19 +157,7 @@ __device__ __forceinline__ void synth_actions(uint64_t seed, uint32_t gid, uint3
         synth_uniform(seed, gid, step, act);
         return;
     }
-    const uint64_t h = fmix64(seed ^ fmix64(((uint64_t)gid << 32) | step));
-    MaskBits mb;
-    compute_masks(E, C, mb);
-#pragma unroll
-    for (int a = 0; a < NA; a++) {
-        const uint32_t bits = mb.bits[a];
-        const int cnt = __popc(bits);
-        int j = (int)((((uint32_t)(h >> (8 * a)) & 0xFFu) * (uint32_t)cnt) >> 8);
-        // j-th set bit
-        uint32_t b = bits;
-        for (int k = 0; k < j; k++) b &= b - 1u;
-        act[a] = __ffs(b) - 1;
-    }
+    masked_actions(action_word(seed, gid, step), E, C, act);
 }
 
 // fjsp_actions: the built-in policies' actions for the current state (no state change)
@@ -180,6 +170,20 @@ __global__ void __launch_bounds__(BLOCK) k_actions(DevState S, Cfg C, int mode, 
     const Tables T = tables_of(S, e);
     int act[NA];
     synth_actions(seed, gid0 + (uint32_t)e, step, mode, E, T, C, act);
+#pragma unroll
+    for (int a = 0; a < NA; a++) actions[(size_t)a * S.n + e] = (uint8_t)act[a];
+}
+
+// fjsp_actions_eps: the perturbed heuristic's actions for the current state (no state change)
+__global__ void __launch_bounds__(BLOCK) k_actions_eps(DevState S, Cfg C, int eps8, uint64_t seed, uint32_t gid0,
+                                                       uint32_t step, uint8_t* __restrict__ actions) {
+    const int e = blockIdx.x * BLOCK + threadIdx.x;
+    if (e >= S.n) return;
+    Env E;
+    env_load(E, S.words, S.n, e);
+    const Tables T = tables_of(S, e);
+    int act[NA];
+    eps_heuristic_actions(seed, gid0 + (uint32_t)e, step, eps8, E, T, C, act);
 #pragma unroll
     for (int a = 0; a < NA; a++) actions[(size_t)a * S.n + e] = (uint8_t)act[a];
 }
@@ -450,6 +454,67 @@ __global__ void __launch_bounds__(BLOCK) k_step_many(DevState S, Cfg C, int K, u
     if (lane == 0)
         for (int i = 0; i < 8; i++) atomicAdd((unsigned long long*)&g_stamps[i], (unsigned long long)E.st_acc[i]);
     )
+}
+
+// fjsp_search_rollout: every active lane from its current state to the end of its episode (or K
+// steps) in one launch, fjsp_search.h search_lane.  One lane per env, 64-env workgroups, the env's
+// tables in LDS as in k_step_many<lds> (97.5 KB: one workgroup per CU); a plain lane loop, so the
+// wave leaves its loop when its last lane has stopped and nothing waits on another wave.  Per step
+// a lane reads nothing (or its 8 script bytes) and writes its 8 action bytes; no observation, no
+// reward, no reward table.
+__global__ void __launch_bounds__(BLOCK) k_search_rollout(DevState S, Cfg C, int K, int eps8, uint64_t seed, uint32_t gid0,
+                                                          uint32_t step0, const uint8_t* __restrict__ script, int L,
+                                                          const int32_t* __restrict__ script_len,
+                                                          const uint8_t* __restrict__ active, uint8_t* __restrict__ trace,
+                                                          fjsp_search_end end) {
+    __shared__ uint32_t s_orders[MAX_ORDERS * BLOCK];
+    __shared__ uint16_t s_code[MAX_SLOTS * BLOCK];
+    __shared__ uint8_t s_next[MAX_SLOTS * BLOCK];
+    __shared__ uint16_t s_cstep[MAX_SLOTS * BLOCK];
+    const int lane = threadIdx.x;
+    const int e = blockIdx.x * BLOCK + lane;
+    if (e >= S.n) return;
+    if (active && !active[e]) {
+        end.steps[e] = -1;
+        return;
+    }
+    Env E;
+    env_load(E, S.words, S.n, e);
+    Tables T;
+    T.orders = s_orders + lane;
+    T.scode = s_code + lane;
+    T.snext = s_next + lane;
+    T.scstep = s_cstep + lane;
+    T.stride = BLOCK;
+    tables_copy_in(S, T, e, E.norders(), E.slot_next());
+    {
+        // A tray slot taken during the launch (at most one per step) gets its code and its link
+        // written at once, its completion step only when it reaches a packaging station: stage what
+        // HBM holds there, so that the copy-out leaves those bytes as the per-step path leaves them.
+        const int s0 = E.slot_next(), s1 = K < MAX_SLOTS - s0 ? s0 + K : MAX_SLOTS;
+        for (int q0 = s0; q0 < s1; q0 += 8) {
+            uint32_t t[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) t[j] = q0 + j < s1 ? S.scstep[(size_t)(q0 + j) * S.n + e] : 0u;
+#pragma unroll
+            for (int j = 0; j < 8; j++)
+                if (q0 + j < s1) T.scstep[(q0 + j) * BLOCK] = (uint16_t)t[j];
+        }
+    }
+    int slen = 0;
+    if (script) {
+        slen = script_len ? script_len[e] : L;
+        slen = slen < 0 ? 0 : slen > L ? L : slen;
+    }
+    const LaneEnd r = search_lane(E, T, C, K, eps8, seed, gid0 + (uint32_t)e, step0, script ? script + e : nullptr, slen,
+                                  trace + e, (size_t)S.n);
+    tables_copy_out(S, T, e, E.norders(), E.slot_next());
+    env_store(E, S.words, S.n, e);
+    end.steps[e] = r.steps;
+    end.flags[e] = (uint8_t)r.flags;
+    end.orders_completed[e] = r.orders_completed;
+    end.packaged[e] = r.packaged;
+    end.sim_time[e] = r.sim_time;
 }
 
 // K fused steps, pipelined over 2 or 3 wavefronts per 64-env workgroup, plus an optional
@@ -2537,6 +2602,52 @@ int fjsp_actions(fjsp_handle* h, int32_t action_mode, uint64_t action_seed, uint
     hipLaunchKernelGGL(k_actions, dim3((h->n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, h->stream, h->S, h->dcfg, action_mode,
                        action_seed, env_gid0, step, actions);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int fjsp_actions_eps(fjsp_handle* h, int32_t eps8, uint64_t action_seed, uint32_t env_gid0, uint32_t step,
+                     uint8_t* actions) {
+    if (!h) return fail("null handle");
+    if (!actions) return fail("fjsp_actions_eps: null actions");
+    if (eps8 < 0 || eps8 > 256) return fail("fjsp_actions_eps: eps8 must be in 0..256");
+    SERVER_QUIESCE(h);
+    if (!h->has_reset) return fail("fjsp_actions_eps before fjsp_reset");
+    DeviceGuard g(h->device);
+    hipLaunchKernelGGL(k_actions_eps, dim3((h->n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, h->stream, h->S, h->dcfg, eps8,
+                       action_seed, env_gid0, step, actions);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int fjsp_search_rollout(fjsp_handle* h, int32_t K, int32_t eps8, uint64_t action_seed, uint32_t env_gid0,
+                        uint32_t step_base, int32_t t0, const uint8_t* script, int32_t L, const int32_t* script_len,
+                        const uint8_t* active, uint8_t* trace, fjsp_search_end* end) {
+    if (!h) return fail("null handle");
+    // the arguments are checked before the handle is touched
+    if (K <= 0) return fail("fjsp_search_rollout: K must be > 0");
+    if (eps8 < 0 || eps8 > 256) return fail("fjsp_search_rollout: eps8 must be in 0..256");
+    if (t0 < 0) return fail("fjsp_search_rollout: t0 must be >= 0");
+    if (!trace) return fail("fjsp_search_rollout: null trace");
+    if (!end || !end->steps || !end->flags || !end->orders_completed || !end->packaged || !end->sim_time)
+        return fail("fjsp_search_rollout: null end record");
+    if ((((uintptr_t)end->steps | (uintptr_t)end->orders_completed | (uintptr_t)end->packaged) & 3u) != 0 ||
+        ((uintptr_t)end->sim_time & 7u) != 0 || ((uintptr_t)script_len & 3u) != 0)
+        return fail("fjsp_search_rollout: misaligned end record or script_len");
+    if (script && L < 0) return fail("fjsp_search_rollout: L must be >= 0");
+    if (!script && script_len) return fail("fjsp_search_rollout: script_len without a script");
+    SERVER_QUIESCE(h);
+    if (!h->has_reset) return fail("fjsp_search_rollout before fjsp_reset");
+    DeviceGuard g(h->device);
+    if (h->timing) HIPCHK(hipEventRecord(h->ev0, h->stream));
+    h->last_kernel = "k_search_rollout";
+    hipLaunchKernelGGL(k_search_rollout, dim3((h->n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, h->stream, h->S, h->dcfg, K, eps8,
+                       action_seed, env_gid0, step_base + (uint32_t)t0, script, script ? L : 0, script_len, active, trace,
+                       *end);
+    HIPCHK(hipGetLastError());
+    if (h->timing) {
+        HIPCHK(hipEventRecord(h->ev1, h->stream));
+        h->timed = 1;
+    }
     return 0;
 }
 

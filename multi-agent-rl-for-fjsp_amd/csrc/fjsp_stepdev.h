@@ -8,6 +8,7 @@
 
 #include "fjsp_env.h"
 #include "fjsp_predraw.h"
+#include "fjsp_search.h"
 #include "fjsp_stamps.h"
 #include "../../include/fjsp.h"
 
@@ -178,13 +179,7 @@ struct StoreSink {
 };
 
 
-// fmix64 counter RNG for synthetic actions (oracle_actions spec)
-__device__ __forceinline__ uint64_t fmix64(uint64_t z) {
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
+// fmix64, the counter RNG of the synthetic actions, is in fjsp_search.h (it compiles for the host too)
 
 // FULL = false: only obs, masks, rewards, term, trunc and status are written (the other
 // fjsp_out pointers are never read, so they take no SGPRs in the hot loop).

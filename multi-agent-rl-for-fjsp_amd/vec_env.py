@@ -15,6 +15,41 @@ from .spec import AGENTS
 
 NI32, NI8, NF32, NMASK, NA, NFEAT = 20, 12, 6, 29, 8, 38
 POLICIES = {"random": 0, "unmasked": 0, "masked": 1, "heuristic": 2}   # FJSP_ACTIONS_*
+# the perturbed heuristic (fjsp_actions_eps): not a fjsp_step_many mode, so actions() / the per-row paths only
+POLICIES["eps_heuristic"] = -1
+
+
+def eps8_of(eps):
+    """epsilon as fjsp_actions_eps takes it: round(eps * 256), an integer in 0..256."""
+    e = int(round(float(eps) * 256))
+    if not 0 <= e <= 256:
+        raise ValueError(f"eps must be in [0, 1], got {eps!r}")
+    return e
+
+
+def _step_many_mode(policy):
+    mode = POLICIES[policy]
+    if mode < 0:
+        raise ValueError(f"policy {policy!r} is not a fjsp_step_many mode: use actions() + step(), "
+                         f"evaluate_schedule, solve or search")
+    return mode
+
+
+class SearchEnd:
+    """End records of fjsp_search_rollout for N envs (device tensors; fjsp_search_end)."""
+
+    def __init__(self, N, device):
+        self.steps = torch.full((N,), -1, dtype=torch.int32, device=device)
+        self.flags = torch.zeros(N, dtype=torch.uint8, device=device)
+        self.orders_completed = torch.zeros(N, dtype=torch.int32, device=device)
+        self.packaged = torch.zeros(N, dtype=torch.int32, device=device)
+        self.sim_time = torch.zeros(N, dtype=torch.float64, device=device)
+
+    def struct(self):
+        return nat.fjsp_search_end(*[getattr(self, k).data_ptr() for k in nat.SEARCH_END_FIELDS])
+
+    def numpy(self):
+        return {k: getattr(self, k).cpu().numpy() for k in nat.SEARCH_END_FIELDS}
 
 
 class Buffers:
@@ -218,14 +253,15 @@ class FJSPVecEnv:
             self.reset(seeds=seeds, num_orders=0)
         return self.reset_orders(orders, counts)
 
-    def solve(self, books, samples, policy="masked", steps=None, action_seed=0, packaging=False):
+    def solve(self, books, samples, policy="masked", steps=None, action_seed=0, packaging=False, eps=0.15):
         """Best-of-`samples` schedules of caller-written order books: env i * samples + r is replica r
         of books[i] (orders.encode's order tuples), so num_envs must be len(books) * samples.  Every
         replica runs evaluate_schedule(orders=...) for `steps` vector steps (default
         max_episode_steps + 1: every first episode ends) under `policy`, whose action stream is keyed
         by the env id, and kpis.best_of picks each book's winner among the first episodes.  Returns
         best_of's dict plus "ops" (and "pack_ops" with packaging=True): the winners' first-episode
-        records, as ScheduleLog.pop() / PackagingLog.pop() return them."""
+        records, as ScheduleLog.pop() / PackagingLog.pop() return them.  eps: policy "eps_heuristic"'s
+        epsilon (actions)."""
         from . import kpis as K
         from . import orders as O
         from . import schedule as S
@@ -236,7 +272,7 @@ class FJSPVecEnv:
         words, counts = O.encode([b for b in books for _ in range(samples)])
         steps = int(self.config.max_episode_steps) + 1 if steps is None else int(steps)
         r = self.evaluate_schedule(policy=policy, steps=steps, action_seed=action_seed, packaging=packaging,
-                                   orders=words, counts=counts)
+                                   orders=words, counts=counts, eps=eps)
         out = K.best_of(r["kpis"], samples, instances=len(books), env_id_base=self.env_id_base)
         win = out["best_env"] + self.env_id_base
         for name, as_dict in (("ops", S.records_dict), ("pack_ops", S.pack_records_dict)):
@@ -246,18 +282,73 @@ class FJSPVecEnv:
                 out[name] = as_dict(recs[keep], r[name]["dropped"])
         return out
 
-    def actions(self, policy="heuristic", action_seed=0, step=0, out=None):
+    def actions(self, policy="heuristic", action_seed=0, step=0, out=None, eps=0.15):
         """The actions rollout(policy=..., action_seed=..., step0=step) would draw for the current
-        state at vector step `step` (fjsp_actions): uint8 [8, N], what step() takes."""
+        state at vector step `step` (fjsp_actions): uint8 [8, N], what step() takes.  policy
+        "eps_heuristic" (fjsp_actions_eps): the heuristic, each agent with probability eps (in steps
+        of 1/256) taking "masked"'s draw of the same (action_seed, env, step) instead."""
         self._sync_stream()
         if out is None:
             out = torch.empty(NA, self.num_envs, dtype=torch.uint8, device=self.device)
         if out.dtype != torch.uint8 or not out.is_contiguous() or out.device != self.device or \
                 tuple(out.shape) != (NA, self.num_envs):
             raise ValueError(f"out must be a contiguous uint8 [8, {self.num_envs}] tensor on the env's device")
+        if POLICIES[policy] < 0:
+            nat.check(nat.lib().fjsp_actions_eps(self._h, eps8_of(eps), int(action_seed) & (2**64 - 1), self.env_id_base,
+                                                 int(step), _ptr(out)))
+            return out
         nat.check(nat.lib().fjsp_actions(self._h, POLICIES[policy], int(action_seed) & (2**64 - 1), self.env_id_base,
                                          int(step), _ptr(out)))
         return out
+
+    def search_rollout(self, K, eps=0.15, action_seed=0, step_base=0, t0=0, script=None, script_len=None, active=None,
+                       trace=None, end=None):
+        """fjsp_search_rollout: one launch that runs every active env from its current state until its
+        episode ends (or K steps), without auto-reset.  Step k of env e takes script[k, :, e] while
+        k < script_len[e] (script uint8 [L, 8, N]; script_len int32 [N], None: L) and after that the
+        "eps_heuristic" actions of vector step step_base + t0 + k; the actions go to trace[k, :, e]
+        (uint8 [K, 8, N]; rows past an env's stop are not written).  active: uint8 [N] (None: all);
+        an inactive env is untouched.  Returns (trace, end): end a SearchEnd with steps (k + 1 at the
+        stop, -1: not within K or inactive), flags (bit 0 terminated, bit 1 truncated) and the
+        orders_completed / packaged / sim_time infos of the env's last executed step."""
+        self._sync_stream()
+        K, N = int(K), self.num_envs
+        if trace is None:
+            trace = torch.zeros(max(K, 0), NA, N, dtype=torch.uint8, device=self.device)
+        elif trace.dtype != torch.uint8 or not trace.is_contiguous() or trace.device != self.device or \
+                trace.dim() != 3 or trace.shape[0] < K or tuple(trace.shape[1:]) != (NA, N):
+            raise ValueError(f"trace must be a contiguous uint8 [>= {K}, 8, {N}] tensor on the env's device")
+        L = 0
+        if script is not None:
+            if script.dtype != torch.uint8 or not script.is_contiguous() or script.device != self.device or \
+                    script.dim() != 3 or tuple(script.shape[1:]) != (NA, N):
+                raise ValueError(f"script must be a contiguous uint8 [L, 8, {N}] tensor on the env's device")
+            L = int(script.shape[0])
+        elif script_len is not None:
+            raise ValueError("script_len needs a script")
+        if script_len is not None:
+            script_len = torch.as_tensor(script_len, device=self.device).to(torch.int32).contiguous()
+            if tuple(script_len.shape) != (N,):
+                raise ValueError(f"script_len must be [{N}], got {tuple(script_len.shape)}")
+        if active is not None:
+            active = torch.as_tensor(active, device=self.device).to(torch.uint8).contiguous()
+            if tuple(active.shape) != (N,):
+                raise ValueError(f"active must be [{N}], got {tuple(active.shape)}")
+        end = end or SearchEnd(N, self.device)
+        es = end.struct()
+        nat.check(nat.lib().fjsp_search_rollout(self._h, K, eps8_of(eps), int(action_seed) & (2**64 - 1), self.env_id_base,
+                                                int(step_base), int(t0), _ptr(script), L, _ptr(script_len), _ptr(active),
+                                                _ptr(trace), ctypes.byref(es)))
+        return trace, end
+
+    def search(self, books, width, stride=8, eps=0.15, action_seed=0, max_passes=None, packaging=False):
+        """Rollout search over caller-written order books (search.search): a best-of-`width` first
+        pass under the perturbed heuristic, then passes that commit the incumbent's next `stride`
+        steps and run `width` lanes from there to the episode's end, keeping a strictly better run.
+        num_envs must be len(books) * width; env i * width + r is replica r of books[i]."""
+        from . import search as SR
+        return SR.search(self, books, width, stride=stride, eps=eps, action_seed=action_seed, max_passes=max_passes,
+                         packaging=packaging)
 
     def step(self, actions, agent_order=None, autoreset=True, buffers=None, held=None, pack=None):
         """One FJSPSimulation.step per env (FJSPSimulation.py:144-242).
@@ -343,7 +434,7 @@ class FJSPVecEnv:
         policy: "random" (uniform, action_space.sample()), "masked" (uniform over valid
         actions) or "heuristic" (MultiAgentA2C._get_heuristic_actions, a2c.py:390-537)."""
         self._sync_stream()
-        mode = POLICIES[policy] if policy is not None else (1 if masked else 0)
+        mode = _step_many_mode(policy) if policy is not None else (1 if masked else 0)
         b = buffers or Buffers(K, self.num_envs, self.device, infos=infos)
         out = b.struct()
         nat.check(nat.lib().fjsp_step_many(self._h, int(K), int(action_seed) & (2**64 - 1), self.env_id_base,
@@ -358,6 +449,7 @@ class FJSPVecEnv:
         products_packaged, rewards_by_agent [8, N] (each agent's rewards summed in step order,
         as episode_rewards) and total_reward (their sum in agent order, a2c.py:626).  orders / counts:
         the caller's order books in place of the draw (_open; total_orders is then each env's count)."""
+        _step_many_mode(policy)
         self._open(seeds, num_orders, orders, counts)
         if orders is not None:
             num_orders = np.asarray(torch.as_tensor(counts).cpu()) if counts is not None else int(len(orders))
@@ -396,7 +488,7 @@ class FJSPVecEnv:
         return self._evaluate_logged(policy, num_orders, steps, seeds, action_seed, chunk, orders=orders, counts=counts)
 
     def evaluate_schedule(self, policy="heuristic", num_orders=5, steps=500, seeds=None, action_seed=0, chunk=256,
-                          packaging=False, orders=None, counts=None):
+                          packaging=False, orders=None, counts=None, eps=0.15):
         """evaluate_kpis with the per-operation schedule beside it: from a reset, per vector step
         the policy's actions (fjsp_actions) and one fjsp_step_held into row k of a chunk slab, each
         chunk scanned into an EpisodeLog, a kpis.KpiLog and a schedule.ScheduleLog.  The states and
@@ -404,18 +496,36 @@ class FJSPVecEnv:
         (env, episode_start) is an episode record's (env, end_step - length).  Only the records
         reach the host.  packaging=True: the steps go through fjsp_step_sched, whose pack words feed a
         schedule.PackagingLog with the same rows, and the result has "pack_ops" = its pop() (one
-        record per tray run at a packaging station; schedule.check_packaging, schedule.arrivals)."""
+        record per tray run at a packaging station; schedule.check_packaging, schedule.arrivals).  eps:
+        policy "eps_heuristic"'s epsilon (actions)."""
         return self._evaluate_logged(policy, num_orders, steps, seeds, action_seed, chunk, schedule=True,
-                                     packaging=bool(packaging), orders=orders, counts=counts)
+                                     packaging=bool(packaging), orders=orders, counts=counts, eps=eps)
+
+    def evaluate_script(self, actions, orders, counts=None, packaging=False, seeds=None, chunk=256):
+        """evaluate_schedule with each row's actions taken from the caller's uint8 [T, 8, N] tensor
+        instead of a policy: T vector steps from reset_orders(orders, counts) through fjsp_step_held
+        (fjsp_step_sched with packaging=True), with auto-reset.  Returns {"episodes", "kpis", "ops"}
+        (and "pack_ops")."""
+        a = torch.as_tensor(actions)
+        if a.dim() != 3 or tuple(a.shape[1:]) != (NA, self.num_envs):
+            raise ValueError(f"actions must be [T, 8, {self.num_envs}], got {tuple(a.shape)}")
+        a = a.to(device=self.device, dtype=torch.uint8).contiguous()
+        if orders is None:
+            raise ValueError("evaluate_script needs orders")
+        return self._evaluate_logged(None, 0, int(a.shape[0]), seeds, 0, chunk, schedule=True, packaging=bool(packaging),
+                                     orders=orders, counts=counts, script=a)
 
     def _evaluate_logged(self, policy, num_orders, steps, seeds, action_seed, chunk, kpis=True, schedule=False,
-                         packaging=False, orders=None, counts=None):
+                         packaging=False, orders=None, counts=None, eps=0.15, script=None):
         """The loop behind evaluate_episodes / _kpis / _schedule: from a reset, chunks of rows into one
         reused Buffers, each scanned into a slablog.LogSet; returns its pop().  Two rollout paths,
         which launch different kernels: one fjsp_step_many per chunk, or with schedule per row the
         policy's actions (fjsp_actions) and one fjsp_step_held / fjsp_step_sched.  orders / counts: the
         caller's order books for the first episodes in place of the draw (_open); later episodes are
-        drawn from the envs' streams with the envs' order counts."""
+        drawn from the envs' streams with the envs' order counts.  script (schedule only): uint8
+        [steps, 8, N] on the device, row k's actions in place of the policy's."""
+        if not schedule:
+            _step_many_mode(policy)
         steps, chunk = int(steps), max(1, min(int(chunk), int(steps)))
         self._open(seeds, num_orders, orders, counts)
         logs = LogSet(self, steps, kpis=kpis, schedule=schedule, packaging=packaging)
@@ -429,7 +539,10 @@ class FJSPVecEnv:
             k = min(chunk, steps - done)
             if schedule:
                 for j in range(k):
-                    self.actions(policy, action_seed=action_seed, step=done + j, out=act)
+                    if script is not None:
+                        act = script[done + j]
+                    else:
+                        self.actions(policy, action_seed=action_seed, step=done + j, out=act, eps=eps)
                     self.step(act, autoreset=True, buffers=rows[j], held=b.held[j], pack=b.pack[j] if packaging else None)
             else:
                 self.rollout(k, action_seed=action_seed, step0=done, policy=policy, autoreset=True, buffers=b)
@@ -571,4 +684,4 @@ def gae_shared(rewards, values, done, gamma, lamb, out_ret=None, out_adv=None):
     return ret, adv
 
 
-__all__ = ["FJSPVecEnv", "Buffers", "RowBuffers", "gae", "gae_shared", "AGENTS"]
+__all__ = ["FJSPVecEnv", "Buffers", "RowBuffers", "SearchEnd", "gae", "gae_shared", "AGENTS"]

@@ -1,0 +1,262 @@
+"""CPU checks of the rollout search: fjsp_search.h (the perturbed heuristic and the lane loop of
+k_search_rollout) compiled for the host through tests/hostsim/search_shim.cpp (TEST-ONLY) against
+the oracle, and search.py's selection rule and incumbent bookkeeping (pure numpy).
+
+The policy must equal, step by step, the composition of OracleEnv.heuristic(), oracle.actions() on
+the oracle's masks and the coin computed in Python (tests/search_ref.py); the lane loop must match
+the same loop driven through OracleEnv.step in trace, stop step, flags, infos and sim_time.  The
+same shim is built once more with a stand-alone main under -fsanitize=address,undefined and run."""
+import ctypes
+import importlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import search_ref as R
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SHIM = os.path.join(HERE, "hostsim", "search_shim.cpp")
+SAN_MAIN = os.path.join(HERE, "hostsim", "search_san_main.cpp")
+GXX = ["g++", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function"]
+P, I32, U32, U64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64
+SEED = 0x5EED5EED12345
+CASES = [(3, 2), (7, 5), (11, 30), (5, 64), (0, 2), (9, 5), (2, 30), (4, 9)]    # (seed, num_orders) per env
+
+
+@pytest.fixture(scope="module")
+def shim(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("search") / "libsearch.so")
+    subprocess.run(GXX + ["-O2", "-fPIC", "-shared", "-o", so, SHIM], check=True)
+    lib = ctypes.CDLL(so)
+    lib.search_world_bytes.restype = ctypes.c_int
+    lib.search_world_reset.restype = ctypes.c_int
+    lib.search_world_reset.argtypes = [P, P, ctypes.c_int]
+    lib.search_eps_actions.restype = None
+    lib.search_eps_actions.argtypes = [P, U64, U32, U32, ctypes.c_int, P]
+    lib.search_heuristic.restype = None
+    lib.search_heuristic.argtypes = [P, P]
+    lib.search_masked.restype = None
+    lib.search_masked.argtypes = [P, U64, U32, U32, P]
+    lib.search_step.restype = ctypes.c_double
+    lib.search_step.argtypes = [P, P, P]
+    lib.search_rollout_host.restype = None
+    lib.search_rollout_host.argtypes = [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, U64, U32, U32, ctypes.c_int,
+                                        P, ctypes.c_int, P, P, P, P, P, P, P, P]
+    lib.search_world_status.restype = U32
+    lib.search_world_status.argtypes = [P]
+    return lib
+
+
+class Worlds:
+    """n host worlds side by side, world e reset with the book OracleEnv (seed, num_orders) draws."""
+
+    def __init__(self, shim, cases):
+        self.shim, self.n = shim, len(cases)
+        self.nb = shim.search_world_bytes()
+        self.buf = np.zeros(self.n * self.nb, np.uint8)
+        for e, (s, k) in enumerate(cases):
+            words = R.Lane(s, k).book_words()
+            assert len(words) == k
+            assert shim.search_world_reset(self.ptr(e), words.ctypes.data, k) == 1
+
+    def ptr(self, e):
+        return self.buf.ctypes.data + e * self.nb
+
+    def bytes_of(self, e):
+        return self.buf[e * self.nb:(e + 1) * self.nb].tobytes()
+
+    def rollout(self, K, eps8, seed, gid0, step_base, t0, script=None, script_len=None, active=None):
+        n = self.n
+        trace = np.full((K, 8, n), 0xEE, np.uint8)
+        end = {"steps": np.full(n, -7, np.int32), "flags": np.full(n, 0xEE, np.uint8),
+               "orders_completed": np.full(n, -7, np.int32), "packaged": np.full(n, -7, np.int32),
+               "sim_time": np.full(n, -7.0)}
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        self.shim.search_rollout_host(self.buf.ctypes.data, n, K, eps8, seed, gid0, step_base, t0, ptr(script),
+                                      0 if script is None else len(script), ptr(script_len), ptr(active),
+                                      trace.ctypes.data, *[end[k].ctypes.data for k in
+                                                           ("steps", "flags", "orders_completed", "packaged", "sim_time")])
+        return trace, end
+
+
+# ---------------------------------------------------------------- the policy
+@pytest.mark.parametrize("eps8", [0, 38, 128, 256])
+def test_policy_equals_the_oracle_composition(shim, eps8):
+    """8 envs x 120 steps: each step's bytes, and the stepped state's infos, against the oracle."""
+    W = Worlds(shim, CASES)
+    took_masked = took_heur = 0
+    for e, (s, k) in enumerate(CASES):
+        lane = R.Lane(s, k)
+        gid = 1000 + e
+        for t in range(120):
+            want = R.eps_actions(lane.ref, lane.rec["masks"], SEED, gid, t, eps8)
+            got, h, m = np.zeros(8, np.uint8), np.zeros(8, np.uint8), np.zeros(8, np.uint8)
+            shim.search_eps_actions(W.ptr(e), SEED, gid, t, eps8, got.ctypes.data)
+            assert got.tolist() == want.tolist(), (eps8, e, t)
+            # the endpoints: eps8 = 0 is the heuristic, eps8 = 256 the masked stream
+            shim.search_heuristic(W.ptr(e), h.ctypes.data)
+            shim.search_masked(W.ptr(e), SEED, gid, t, m.ctypes.data)
+            assert h.tolist() == lane.ref.heuristic().tolist(), (e, t)
+            assert m.tolist() == R.OR.actions(SEED, gid, t, lane.rec["masks"]).tolist(), (e, t)
+            if eps8 == 0:
+                assert got.tolist() == h.tolist()
+            if eps8 == 256:
+                assert got.tolist() == m.tolist()
+            coin = R.coins(SEED, gid, t) < eps8
+            took_masked += int((coin & (m != h)).sum())
+            took_heur += int((~coin & (m != h)).sum())
+            lane.rec = r = lane.ref.step(got)
+            info = np.zeros(4, np.int32)
+            st = shim.search_step(W.ptr(e), got.ctypes.data, info.ctypes.data)
+            assert info.tolist() == [r["term"], r["trunc"], r["orders_completed"], r["packaged"]], (e, t)
+            assert st == r["sim_time"] and shim.search_world_status(W.ptr(e)) == r["status"], (e, t)
+    if 0 < eps8 < 256:      # both branches decided some byte
+        assert took_masked > 50 and took_heur > 50, (took_masked, took_heur)
+
+
+def test_coin_is_the_specified_hash():
+    """The coin's formula, spelled out once more against tests/search_ref.py."""
+    h = R.fmix64(7 ^ R.fmix64((5 << 32) | 9))
+    h2 = R.fmix64(h ^ 0x9E3779B97F4A7C15)
+    assert R.coins(7, 5, 9).tolist() == [(h2 >> (8 * a)) & 0xFF for a in range(8)]
+    assert R.fmix64(0) == 0
+
+
+# ---------------------------------------------------------------- the lane loop
+LANE_CASES = [(0, 2), (0, 2), (11, 2), (3, 3), (7, 5), (0, 2)]
+
+
+def _heuristic_run(case):
+    return R.Lane(*case).run(201, 0, 0, 0, 0)
+
+
+def test_lane_loop_equals_the_oracle_loop(shim):
+    """Lanes: 0 a script shorter than its run, 1 a script longer than its run (the heuristic's whole
+    run and rows after it), 2 no script, 3 inactive, 4 a five-order book the policy does not finish
+    (truncation), 5 script_len 0 with rows present."""
+    n, K, eps8, gid0, base, t0 = len(LANE_CASES), 201, 38, 40, 3 << 12, 16
+    full, full_end = _heuristic_run(LANE_CASES[1])
+    assert full_end["flags"] == 1 and len(full) < 100
+    L = len(full) + 7
+    script = np.full((L, 8, n), 0, np.uint8)
+    script[:10, :, 0] = full[:10]
+    script[:len(full), :, 1] = full
+    script[:, :, 5] = 0x11                                    # never read: script_len 0
+    slen = np.array([10, L, 0, 5, 0, 0], np.int32)
+    active = np.array([1, 1, 1, 0, 1, 1], np.uint8)
+    W = Worlds(shim, LANE_CASES)
+    before = W.bytes_of(3)
+    trace, end = W.rollout(K, eps8, SEED, gid0, base, t0, script, slen, active)
+    assert W.bytes_of(3) == before and end["steps"][3] == -1
+    assert (trace[:, :, 3] == 0xEE).all() and end["flags"][3] == 0xEE and end["sim_time"][3] == -7.0
+    for e in (0, 1, 2, 4, 5):
+        sc = script[:slen[e], :, e]
+        tr, want = R.Lane(*LANE_CASES[e]).run(K, eps8, SEED, gid0 + e, base + t0, sc)
+        assert want["steps"] > 0
+        for k in want:
+            assert end[k][e] == want[k], (e, k, end[k][e], want[k])
+        assert trace[:len(tr), :, e].tolist() == tr.tolist(), e
+        assert (trace[len(tr):, :, e] == 0xEE).all(), "rows past the stop were written"
+    assert end["steps"][1] == len(full) and end["flags"][1] == 1      # stopped inside its script
+    assert end["flags"][4] == 2 and end["steps"][4] == 201            # truncated
+    assert end["steps"][0] > 10
+
+
+def test_a_k_that_ends_before_the_episode(shim):
+    n, K = len(LANE_CASES), 30
+    W = Worlds(shim, LANE_CASES)
+    trace, end = W.rollout(K, 64, SEED, 0, 0, 0)
+    for e in range(n):
+        lane = R.Lane(*LANE_CASES[e])
+        tr, want = lane.run(K, 64, SEED, e, 0)
+        assert want["steps"] == -1 and want["flags"] == 0 and len(tr) == K
+        assert end["steps"][e] == -1 and end["flags"][e] == 0
+        for k in ("orders_completed", "packaged", "sim_time"):
+            assert end[k][e] == want[k], (e, k)
+        assert end["sim_time"][e] == 10.0 * K
+        assert trace[:, :, e].tolist() == tr.tolist()
+    # the lanes go on from where they stopped: a second launch finishes what one launch would have
+    trace2, end2 = W.rollout(201 - K, 64, SEED, 0, 0, K)
+    for e in range(n):
+        tr, want = R.Lane(*LANE_CASES[e]).run(201, 64, SEED, e, 0)
+        assert end2["steps"][e] == want["steps"] - K and end2["flags"][e] == want["flags"]
+        assert end2["sim_time"][e] == want["sim_time"]
+        assert np.concatenate([trace[:, :, e], trace2[:end2["steps"][e], :, e]]).tolist() == tr.tolist()
+
+
+def test_sanitized_standalone_run(tmp_path):
+    exe = str(tmp_path / "search_san")
+    subprocess.run(GXX + ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, SAN_MAIN],
+                   check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert r.stdout.strip().endswith("OK")
+
+
+# ---------------------------------------------------------------- selection rule and incumbents
+@pytest.fixture(scope="module")
+def SR():
+    return importlib.import_module("multi-agent-rl-for-fjsp_amd.search")
+
+
+def test_select_follows_best_of(SR):
+    f = np.array
+    # terminated lanes: the least sim_time, ties to the lowest lane; a terminated lane beats any other
+    assert SR.select(f([2, 1, 1, 1]), f([2010., 900., 800., 800.]), f([9, 2, 2, 2]), f([9, 5, 5, 5])) == 2
+    assert SR.select(f([3, 1]), f([2010., 2010.]), f([2, 2]), f([5, 5])) == 0           # term | trunc counts as term
+    # none terminated: the most orders, then the most packaged, then the lowest lane; sim_time is not read
+    assert SR.select(f([2, 2, 2, 2]), f([1., 2., 3., 4.]), f([1, 3, 3, 3]), f([9, 4, 6, 6])) == 2
+    assert SR.select(f([2, 2]), f([5., 1.]), f([0, 0]), f([0, 0])) == 0
+    assert SR.run_key(1, 500.0, 0, 0) < SR.run_key(0, 10.0, 64, 999)
+
+
+def test_incumbent_takes_strict_improvements_only(SR):
+    a = np.arange(40, dtype=np.uint8).reshape(5, 8)
+    inc = SR.Incumbent(a, 2, 2010.0, 1, 7)
+    assert not inc.solved and np.isnan(inc.makespan) and len(inc) == 5
+    assert not inc.offer(2, a[:1], 2, 2010.0, 1, 7)                   # equal: kept
+    assert not inc.offer(2, a[:1], 2, 100.0, 1, 6)                    # fewer packaged
+    assert inc.offer(2, a[:1] + 100, 2, 2010.0, 1, 8) and len(inc) == 3
+    assert inc.actions.tolist() == a[:2].tolist() + (a[:1] + 100).tolist()
+    assert inc.offer(3, a[3:], 1, 900.0, 2, 9) and inc.solved and inc.makespan == 900.0 and len(inc) == 5
+    assert not inc.offer(1, a[:2], 1, 900.0, 2, 9)                    # an equal makespan does not replace
+    assert not inc.offer(1, a[:2], 2, 10.0, 64, 99)                   # nor does any unsolved run
+    assert not inc.offer(1, a[:2], 1, 910.0, 2, 9)
+    before = inc.actions.copy()
+    assert inc.offer(4, a[:3], 1, 890.0, 2, 9) and len(inc) == 7 and inc.actions[:4].tolist() == before[:4].tolist()
+
+
+def test_book_activity_and_history(SR):
+    inc = SR.Incumbent(np.zeros((41, 8), np.uint8), 1, 410.0, 2, 6)
+    assert [SR.book_active(inc, p, 8) for p in range(1, 7)] == [True] * 5 + [False]
+    assert not SR.book_active(SR.Incumbent(np.zeros((8, 8), np.uint8), 1, 80.0, 1, 1), 1, 8)
+    nan = np.nan
+    assert SR.history_monotone([[nan, 800.0], [nan, 800.0], [1940.0, 740.0], [1880.0, 740.0]])
+    assert not SR.history_monotone([[800.0], [810.0]])
+    assert not SR.history_monotone([[800.0], [nan]])
+    # a hand-made sequence of offers yields a monotone history
+    inc, hist = SR.Incumbent(np.zeros((20, 8), np.uint8), 2, 2010.0, 0, 3), []
+    for off in [(2, 2010.0, 0, 2), (2, 2010.0, 1, 0), (1, 1500.0, 2, 6), (1, 1600.0, 2, 6), (2, 0.0, 2, 6), (1, 1490.0, 2, 6)]:
+        inc.offer(4, np.zeros((3, 8), np.uint8), *off)
+        hist.append([inc.makespan])
+    assert SR.history_monotone(hist) and hist[-1] == [1490.0] and np.isnan(hist[0][0])
+
+
+def test_search_rejects_what_it_cannot_run(SR):
+    """The argument checks come before anything touches the env: a stand-in without a GPU will do."""
+    from types import SimpleNamespace as NS
+    book = [(1, 1, 1)]
+    env = NS(num_envs=4, config=NS(max_episode_steps=4095))
+    with pytest.raises(ValueError, match="4095"):           # the pass number is packed above 12 bits of the step
+        SR.search(env, [book, book], 2)
+    env = NS(num_envs=4, config=NS(max_episode_steps=200))
+    with pytest.raises(ValueError, match="num_envs"):
+        SR.search(env, [book], 2)
+    with pytest.raises(ValueError, match="stride"):
+        SR.search(env, [book, book], 2, stride=0)
+    with pytest.raises(ValueError, match="max_passes"):
+        SR.search(env, [book, book], 2, max_passes=0)
+    with pytest.raises(ValueError, match="eps"):
+        SR.search(env, [book, book], 2, eps=-0.1)
