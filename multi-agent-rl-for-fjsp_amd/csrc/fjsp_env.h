@@ -1025,6 +1025,58 @@ FJSP_DEV uint32_t pack_lane_counts(const Env& E, int g, int half) {
     return v;
 }
 
+// ---- k_step_ag's AM wave on lane groups.  With G = 64 / EPW >= 2 lanes per env, lane group
+// g < 2 holds machine g in machine slot 0 of its own Env: its queue and ready list in W9 / W10,
+// its machine word in W17, its next completion in the low half of W19 (machine 1's state words
+// are W11 / W12 / W18 and W19's high half).  machine_execute<0> runs unchanged on both groups and
+// mach_lane_run is machines_run for the one machine; the two machines touch disjoint state words
+// and OR the shared order words atomically, so the groups run side by side.  Group 0 keeps every
+// other word AM owns; group 1 keeps a copy of W0 (the step counter, and num_orders / next_order
+// for the reset decision it takes itself) and its own status bits (W2), which are ORed into the
+// env's where the status is emitted and stored.
+// word(i) reads state word i of the lane's env.
+template <class W>
+FJSP_DEV void mach_lane_load(Env& E, int g, W&& word) {
+    E.w[7 + L_M0Q] = word(7 + L_M0Q + 2 * g);
+    E.w[7 + L_M0R] = word(7 + L_M0R + 2 * g);
+    E.w[17] = word(17 + g);
+    E.w[19] = (word(19) >> (16 * g)) & 0xFFFFu;
+}
+// env_clear of a machine's words (and the lane's copies of W0 and the status; the caller sets
+// num_orders)
+FJSP_DEV void mach_lane_clear(Env& E) {
+    E.w[0] = 0u; E.w[2] = 0u;
+    E.w[7 + L_M0Q] = (uint32_t)NIL | ((uint32_t)NIL << 8);
+    E.w[7 + L_M0R] = (uint32_t)NIL | ((uint32_t)NIL << 8);
+    E.w[17] = (uint32_t)NIL << 1;
+    E.w[19] = 0u;
+}
+// machines_run for the lane's machine (slot 0): ptk = its processing time per product
+template <bool AT = false>
+FJSP_DEV void mach_lane_run(Env& E, const Tables& T, int ptk, int s0) {
+    const int step = E.step();
+    const bool due0 = E.m_busy(0) && E.m_next(0) == step;
+    const int c0 = E.m_code(0);
+    const int o0 = tc_order(c0);
+    const int g0 = T.scode[(s0 >= 0 ? s0 : 0) * T.stride];
+    const uint32_t b0 = 1u << (tc_start(c0) + E.m_k(0));
+    if (due0) {   // product.is_processed = True, then machine_done
+        if constexpr (AT) order_or(&T.orders[o0 * T.stride], b0);
+        else T.orders[o0 * T.stride] |= b0;
+        const int k = E.m_k(0);
+        E.set_m_k(0, k + 1);
+        if (k + 1 >= tc_count(c0)) { E.set_m_busy(0, 0); E.set_m_prog(0, 1); }
+        else E.set_m_next(0, step + ptk);
+    }
+    if (s0 >= 0) {   // machine_grant
+        if (E.m_cur(0) != NIL) E.flag(ST_OVERWRITE);
+        const int busy = tc_count(g0) > 0;
+        E.set_m_grant(0, s0, g0, busy);
+        if (busy) E.set_m_next(0, step + ptk);
+        else E.set_m_prog(0, 1);
+    }
+}
+
 // ---------------------------------------------------------------- observations
 // Observations and masks are emitted field by field into a Sink (store-as-you-go keeps the
 // 67 output values out of the register file).  Sink API:

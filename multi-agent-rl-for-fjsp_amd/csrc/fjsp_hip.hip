@@ -1167,6 +1167,8 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
 //      reset, and the first step of a launch, runs those two agents here), runs the machines'
 //      actions (MachineAgent.py:99-139), posts the pickup / AGV words and the machine lists
 //      (release flag), then the machines' run phase (:151-169) and its half of the snapshot.
+//      With 16 / 32 envs per workgroup the two machines run side by side on its lane groups 0
+//      and 1 (mach_lane_*, fjsp_env.h).
 //   E3 runs, in step k, step k+2's pickup station (PickupStationAgent.py:146-248) on its own
 //      words after step k+1's pickup, ahead of the AGV of step k+1; at the top of step k+1 it
 //      composes P's AGV result into it (a lane AM reset, a launch's first step and a lane whose
@@ -1235,8 +1237,18 @@ struct AgSplitOf {
 template <int G> struct AgSplit : AgSplitOf<false, 2, 4> {};
 template <> struct AgSplit<4> : AgSplitOf<true, 2, 4> {};
 // snapshot slot words (PipeSnap, 32 per lane): AM writes q[0..3], K q[4..7]
-enum : int { SA_W0 = 0, SA_ST, SA_W4, SA_W5, SA_W6, SA_L0, SA_M0 = SA_L0 + 6, SA_M1, SA_R01, SA_R23,
-             SK_W1 = 16 };
+enum : int { SA_W0 = 0, SA_ST, SA_W4, SA_W5, SA_W6, SK_W1 = 16 };
+// AM's other words by the wave's number of lane groups G: with one lane per env the order AM has
+// always stored them in (W7..W12, W17, W18, r0 | r1 << 16, r2 | r3 << 16); with lane groups
+// (machine g on group g < 2, fjsp_env.h mach_lane_*) whole 16-byte groups per lane group: group 0
+// writes words 0..11 (machine 0's lists, word and result among them), group 1 words 12..15:
+// machine 1's lists, its word, and r3 | its status bits << 16 (X)
+template <int G>
+struct SnapA {
+    static constexpr int L(int l) { return G == 1 ? 5 + l : l < 2 ? 5 + l : l < 4 ? 6 + l : 8 + l; }
+    static constexpr int M0 = G == 1 ? 11 : 10, M1 = G == 1 ? 12 : 14, R01 = G == 1 ? 13 : 7, R23 = G == 1 ? 14 : 11, X = 15;
+    static_assert(G == 1 || (L(0) == 5 && L(1) == 6 && L(2) == 8 && L(3) == 9 && L(4) == 12 && L(5) == 13), "AM's snapshot words");
+};
 // K's words by the wave's number of lane groups G: with one lane per env the order K has always
 // stored them in; with lane groups, whole 16-byte groups per kind of word, so that group 0 writes
 // the words that are one per env and every group its station's words at their places
@@ -1248,7 +1260,6 @@ struct SnapK {
                   "K's snapshot words");
     static_assert(R67 < 32, "snapshot slot");
 };
-static_assert(SA_R23 < 16, "snapshot slot");
 // P's results for a step (s_res): next_order, W4, W5..W12, pickup result, AGV result, status, drop
 enum : int { RS_NO = 0, RS_W4, RS_W5, RS_R0 = RS_W5 + 8, RS_R1, RS_ST, RS_PEND = 15, RS_N };
 static_assert(RS_N <= 16, "s_res slot");
@@ -1320,11 +1331,13 @@ __device__ __forceinline__ void ag_emit(const uint32_t* v, uint32_t t, uint32_t 
     Env E;
 #pragma unroll
     for (int i = 0; i < NSTATE; i++) E.w[i] = 0u;
+    using SA = SnapA<G>;
     E.w[0] = v[SA_W0]; E.w[2] = v[SA_ST] | v[SK::ST]; E.w[4] = v[SA_W4]; E.w[5] = v[SA_W5];
+    if constexpr (G > 1) E.w[2] |= v[SA::X] >> 16;   // machine 1's lane group keeps its own status bits
     E.w[6] = v[SA_W6];
 #pragma unroll
-    for (int l = 0; l < 6; l++) E.w[7 + l] = v[SA_L0 + l];
-    E.w[17] = v[SA_M0]; E.w[18] = v[SA_M1];
+    for (int l = 0; l < 6; l++) E.w[7 + l] = v[SA::L(l)];
+    E.w[17] = v[SA::M0]; E.w[18] = v[SA::M1];
     E.w[1] = v[SK_W1];
 #pragma unroll
     for (int s = 0; s < 4; s++) { E.w[20 + s] = v[SK::P0 + s]; E.w[26 + s] = v[SK::N0 + s]; }
@@ -1333,7 +1346,7 @@ __device__ __forceinline__ void ag_emit(const uint32_t* v, uint32_t t, uint32_t 
         if (out.rewards) {
             const uint32_t gs = v[SK::GS];
             const double g8 = global_reward8(C, (int)(gs & 0xFFFFu), (int)(gs >> 16));
-            const uint32_t rw[4] = {v[SA_R01], v[SA_R23], v[SK::R45], v[SK::R67]};
+            const uint32_t rw[4] = {v[SA::R01], G > 1 ? v[SA::R23] | (v[SA::X] << 16) : v[SA::R23], v[SK::R45], v[SK::R67]};
 #pragma unroll
             for (int a = 0; a < NA; a++) {
                 const uint32_t r = (rw[a >> 1] >> (16 * (a & 1))) & 0xFFFFu;
@@ -1509,7 +1522,175 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
     if constexpr (STALL) {
         if (wave == AG_AM && blockIdx.x == 0) stall_for_test(S);
     }
-    if (wave == AG_AM) {
+    if (BLOCK / EPW > 1 && wave == AG_AM) {
+        // The two machines on the wave's lane groups 0 and 1 (fjsp_env.h, mach_lane_*): lane
+        // g * EPW + el holds machine g of env el, so machine_execute<0> and the machine's run phase
+        // are one instruction stream for both.  Group 0 is AM as it is below, less machine 1;
+        // group 1 reads the same inputs with the same instructions (of P's result it keeps W0's
+        // next_order and its two list words), takes the reset decision itself from its copy of
+        // W0, posts its half of s_p2 and writes its 16 bytes of the snapshot.  A lane AM reset, and
+        // the first step of a launch, run the pickup and the AGV on group 0, which hands W0 and
+        // machine 1's lists to group 1 inside the wave.
+        if constexpr (BLOCK / EPW > 1) {
+        using SA = SnapA<BLOCK / EPW>;
+        Cfg C = cfg_at(ag_args(), s_lut);
+        asm volatile("" : "+v"(C.max_steps), "+v"(C.tray_cap), "+v"(C.storage_cap), "+v"(C.pool0), "+v"(C.ptk_small),
+                          "+v"(C.ptk_big));   // see the one-lane form below
+        __builtin_amdgcn_s_setprio(3);   // the machines -> AGV chain is the critical path
+        const int g = lane / EPW, el = lane % EPW;
+        const int em = blk * EPW + el;
+        const bool mval = g < 2 && em < S.n, v1 = mval && g == 1;   // `valid`: group 0's lanes
+        const Tables TM{s_orders + el, s_code + el, s_next + el, s_cstep + el, BLOCK};
+        const int ptk = g ? C.ptk_big : C.ptk_small;
+        Env E;
+#pragma unroll
+        for (int i = 0; i < NSTATE; i++) E.w[i] = 0u;
+        if (valid) env_load(E, S.words, S.n, e);
+        if (v1) {
+            mach_lane_load(E, 1, [&](int i) { return S.words[(size_t)i * n + em]; });
+            E.w[0] = S.words[em];   // its copy of W0: the step counter and the reset decision
+        }
+        int epi = 0;
+        bool fresh = true, trunc_prev = false;
+        FJSP_DIAG(
+        const uint64_t loop_t0 = __builtin_amdgcn_s_memtime();
+        )
+        for (int k = 0; k <= K; k++) {
+            AG_T0();
+            AG_MARK(0);
+            // the lane's machine queue front's successor as P's AGV of step k saw the queue
+            int pl = 0, pn = NIL;
+            if (mval && k < K) {
+                pl = E.ll(L_M0Q);
+                if (pl >= 2) pn = TM.snext[E.lh(L_M0Q) * BLOCK];
+            }
+            // this step's inputs, read together: K's completion count, the actions, P's results
+            uint32_t kc = 0, a0 = 0, rs[16];
+            if (mval) {
+                kc = s_kpost[(k - 1) & 1][el];
+                if (k < K) {
+                    a0 = s_act[k & 3][0][el];
+                    q_get(&s_res[k & 1][0][el], 4, rs);
+                }
+            }
+            if (mval && k > 0) {   // end of step k - 1: auto-reset once K has counted the completions
+                const int nord = E.norders();
+                const int all_done = (int)(kc & 0xFFu) == nord && nord > 0 && E.next_order() == nord;
+                if (autoreset && (all_done || trunc_prev)) {
+                    fresh = true;
+                    if (g == 0) {
+                        const uint32_t pr = s_mb[2][k & 1][lane];
+                        if ((pr & 1u) && ((pr >> 1) & 0xFFu) == (uint32_t)epi && (int)((pr >> 9) & 0x7Fu) == nord)
+                            env_reset_predrawn(E, TL, C, nord, s_mb[3][k & 1][lane], s_nxt + lane);
+                        else
+                            E = env_reset_cold(E, TL, C, S, e, nord, false);
+                        epi = (epi + 1) & 0xFF;
+                    } else {
+                        mach_lane_clear(E);
+                        E.set_norders(nord);
+                    }
+                }
+            }
+            AG_MARK(1);
+            if (k < K) {
+                uint32_t r0 = 0, r1 = 0, pend = 0;
+                if (mval && !fresh) {   // step k's pickup and AGV ran on P during step k - 1
+                    // (group 1 keeps next_order and its machine's lists in slot 0; the rest is unused there)
+                    E.w[0] = (E.w[0] & 0x00FFFFFFu) | (rs[RS_NO] << 24);
+                    E.w[4] = rs[RS_W4];
+#pragma unroll
+                    for (int i = 0; i < 8; i++) E.w[5 + i] = rs[RS_W5 + i];
+                    E.w[7 + L_M0Q] = g ? rs[RS_W5 + 2 + L_M1Q] : rs[RS_W5 + 2 + L_M0Q];
+                    E.w[7 + L_M0R] = g ? rs[RS_W5 + 2 + L_M1R] : rs[RS_W5 + 2 + L_M0R];
+                    r0 = rs[RS_R0];
+                    r1 = rs[RS_R1];
+                    E.w[2] |= g ? 0u : rs[RS_ST];
+                }
+                if (__ballot(mval && fresh) != 0) {   // rare: a reset, a launch's first step
+                    if (valid && fresh) {
+                        const int act0 = (int)(a0 & 0xFFu), act1 = (int)((a0 >> 8) & 0xFFu);
+                        r0 = (pickup_execute(E, TL, C, act0) & 0xFFu) | ((uint32_t)act0 << 8);
+                        int mv = 0;
+                        r1 = (agv_execute<true>(E, TL, C, act1, &mv, &pend) & 0xFFu) | ((uint32_t)act1 << 8);
+                        if (mv) E.set_loc(mv);   // the move always lands inside the run
+                    }
+                    // W0 after that pickup and machine 1's lists after that AGV, from group 0's lane
+                    // of the env to group 1's
+                    const uint32_t h0 = (uint32_t)__shfl((int)E.w[0], el);
+                    const uint32_t hq = (uint32_t)__shfl((int)E.w[7 + L_M1Q], el), hr = (uint32_t)__shfl((int)E.w[7 + L_M1R], el);
+                    if (v1 && fresh) {
+                        E.w[0] = h0;
+                        E.w[7 + L_M0Q] = hq;
+                        E.w[7 + L_M0R] = hr;
+                    }
+                }
+                AG_MARK(2);
+                if (mval) {
+                    const int actm = (int)((a0 >> (16 + 8 * g)) & 0xFFu);
+                    int s0 = -1;
+                    const int nk = fresh ? -1 : pl >= 2 ? pn : E.lt(L_M0Q);
+                    const uint32_t rm2 = (machine_execute<0>(E, TM, actm, &s0, nk) & 0xFFu) | ((uint32_t)actm << 8);
+                    AG_MARK(3);
+                    // the post: pickup / AGV words (P1_*) by group 0, each group its machine's lists
+                    if (g == 0) {
+                        const uint32_t p1[8] = {E.w[0], E.w[4], E.w[5], E.w[6], E.w[7], E.w[8], pend, 0u};
+                        q_put(&s_p1[k & 1][0][lane], 2, p1);
+                    }
+                    reinterpret_cast<uint2*>(&s_p2[el])[g] = make_uint2(E.w[7 + L_M0Q], E.w[7 + L_M0R]);
+                    // stored by the lanes that posted, after their post in the same instruction
+                    // stream (a store by the other lanes could be scheduled first); every workgroup
+                    // has a valid lane
+                    __hip_atomic_store(&s_flag1, (uint32_t)(k + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    AG_ACC(ag_wait);
+                    AG_MARK(4);
+                    mach_lane_run<true>(E, TM, ptk, s0);
+                    AG_MARK(5);
+                    if (E.ll(L_M0Q) > 127) E.flag(ST_OBS_OVERFLOW | ST_DIVERGED);
+                    if (g == 0) {
+                        const uint32_t v[12] = {E.w[0], E.w[2], E.w[4], E.w[5], E.w[6], E.w[7], E.w[8], r0 | (r1 << 16),
+                                                E.w[9], E.w[10], E.w[17], rm2};
+                        static_assert(SA::R01 == 7 && SA::L(2) == 8 && SA::M0 == 10 && SA::R23 == 11, "group 0's snapshot words");
+#pragma unroll
+                        for (int q = 0; q < 3; q++) snap[k & 1].q[q][lane] = make_uint4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+                    } else {
+                        static_assert(SA::L(4) == 12 && SA::M1 == 14 && SA::X == 15, "group 1's snapshot words");
+                        snap[k & 1].q[3][el] = make_uint4(E.w[7 + L_M0Q], E.w[7 + L_M0R], E.w[17], rm2 | (E.w[2] << 16));
+                    }
+                    trunc_prev = E.step() >= C.max_steps;
+                    E.set_step(E.step() + 1);
+                    fresh = false;
+                }
+            }
+            if (valid) {   // PD's mailbox for the next step (off the way to the post: its release waits for them)
+                s_mb[0][(k + 1) & 1][lane] = (uint32_t)epi | ((uint32_t)E.norders() << 8);
+                s_mb[1][(k + 1) & 1][lane] = E.w[3];
+            }
+            AG_ACC(ag_busy);
+            AG_BARRIER();
+        }
+        FJSP_DIAG(
+        if (lane == 0) atomicAdd(&g_agstamps[24], (unsigned long long)(__builtin_amdgcn_s_memtime() - loop_t0));
+        )
+        // machine 1's next completion and its lane group's status bits, back to group 0's lane
+        const uint32_t n1 = (uint32_t)__shfl((int)E.w[19], EPW + el), st1 = (uint32_t)__shfl((int)E.w[2], EPW + el);
+        if (v1) {
+            S.words[(size_t)(7 + L_M1Q) * n + em] = E.w[7 + L_M0Q];
+            S.words[(size_t)(7 + L_M1R) * n + em] = E.w[7 + L_M0R];
+            S.words[(size_t)18 * n + em] = E.w[17];
+        }
+        if (valid) {
+            s_act[0][0][lane] = (uint32_t)E.norders();   // for the copy-out by all waves below
+            s_act[0][1][lane] = (uint32_t)E.slot_next();
+            E.w[2] |= s_kpost[2][lane] | st1;
+            E.w[19] = (E.w[19] & 0xFFFFu) | (n1 << 16);
+            // every wait happened before the last barrier: a give-up is visible here
+            if (s_abort) E.w[2] |= ST_SPIN_TIMEOUT | ST_DIVERGED;
+#pragma unroll
+            for (int i = 0; i < NSTATE; i++)
+                if (!((K_WORDS >> i) & 1u) && i != 7 + L_M1Q && i != 7 + L_M1R && i != 18) S.words[i * n + e] = E.w[i];
+        }
+        }
+    } else if (wave == AG_AM) {   // one lane per env (64 envs per workgroup)
         Cfg C = cfg_at(ag_args(), s_lut);
         // AM's loop has no SGPRs to spare: with its six config scalars there, four of them and a
         // loop-invariant condition were spilled to VGPR lanes and read back by v_readlane at each
