@@ -2,31 +2,9 @@
 // (multi-agent-rl-for-fjsp_amd/csrc/fjsp_env.h: agv_pre + agv_fin, k_step_ag's P wave) for
 // tests/test_agv_split_host.py: a constructed sweep and a replay in P's schedule, both against
 // agv_execute<true> / the plain step.
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-#define FJSP_DEV inline
-#include "../../multi-agent-rl-for-fjsp_amd/csrc/fjsp_env.h"
-using namespace fjsp;
+#include "replay.h"
 
 namespace {
-
-struct World {   // one env with its tables (stride 1)
-    Env E;
-    uint32_t orders[MAX_ORDERS];
-    uint16_t scode[MAX_SLOTS];
-    uint8_t snext[MAX_SLOTS];
-    uint16_t scstep[MAX_SLOTS];
-    Tables tabs() { return Tables{orders, scode, snext, scstep, 1}; }
-};
-
-Cfg make_cfg(int storage_cap, const double* lut) {
-    Cfg C;
-    C.step_size = 10; C.max_steps = 200; C.tray_cap = 5; C.mask_tray_cap = 5; C.storage_cap = storage_cap;
-    C.pool0 = 1000; C.pkg_cap = 20; C.ptk_small = 6; C.ptk_big = 12; C.ptk_pack = 3;
-    C.lut = lut;
-    return C;
-}
 
 void fill(World& W, int lid, int len, int* slot_order) {   // `len` trays of distinct orders on list lid
     Tables T = W.tabs();
@@ -48,25 +26,57 @@ void others(World& W, int change, int src, int dst) {
     if ((change & 2) && (dst == L_M0Q || dst == L_M1Q) && (W.E.w[7 + dst] >> 16) != 0) list_pop_dyn<0x3Fu>(W.E, T, dst);
 }
 
-bool same(const World& A, const World& B) {
-    return memcmp(A.E.w, B.E.w, sizeof(A.E.w)) == 0 && memcmp(A.orders, B.orders, sizeof(A.orders)) == 0 &&
-           memcmp(A.scode, B.scode, sizeof(A.scode)) == 0 && memcmp(A.snext, B.snext, sizeof(A.snext)) == 0 &&
-           memcmp(A.scstep, B.scstep, sizeof(A.scstep)) == 0;
-}
+// S's step in P's schedule: AGV of step k -> agv_pre of k+1 -> the rest of step k -> pickup of
+// k+1 -> agv_fin
+struct PSchedule {
+    static constexpr int AHEAD = 1;
+    const Cfg& C;
+    int64_t* rare;   // [2]: agv_fin's rare path 0 (front new), rare path 1 (successor new)
+    bool fresh;
+    uint32_t r0, r1, pend;
+    int mv;
+    AgvPre pre;
 
-struct Lcg {
-    uint64_t s;
-    uint32_t next(uint32_t n) { s = s * 6364136223846793005ull + 1442695040888963407ull; return (uint32_t)(s >> 33) % n; }
-};
+    void begin(World&) { fresh = true; r0 = r1 = pend = 0; mv = 0; }
 
-void reset_world(World& W, const Cfg& C, int num_orders, Lcg& g) {
-    env_clear(W.E, C);
-    W.E.set_norders(num_orders);
-    for (int o = 0; o < num_orders; o++) {
-        const int n = 1 + (int)g.next(9), ty = 1 + (int)g.next(3), co = 1 + (int)g.next(3);
-        W.orders[o] = ow_make(n, ty, co);
+    bool step(Step& st, World& S) {
+        Tables TS = S.tabs();
+        if (fresh) {   // the launch's first step, and the step after a reset: both agents in place
+            r0 = pickup_execute(S.E, TS, C, st.act[0]);
+            mv = 0; pend = 0;
+            r1 = agv_execute<true>(S.E, TS, C, st.act[1], &mv, &pend) | ((uint32_t)st.act[1] << 8);
+            if (mv) S.E.set_loc(mv);
+            fresh = false;
+        }
+        pre = agv_pre(S.E, TS, C, st.nxt[1]);   // step k + 1's AGV, its own half
+        if (pend) agv_pack_drop(S.E, TS, C, pend);
+        // the rest of step k: the move lands inside the run (machine_execute does not read the
+        // location), the pickup station and the AGV have acted (255 = no action)
+        if (mv) S.E.set_loc(mv);
+        int rest[NA];
+        uint32_t res[NA];
+        for (int a = 0; a < NA; a++) rest[a] = a < 2 ? 255 : st.act[a];
+        env_advance<true>(S.E, TS, C, rest, nullptr, res);
+        res[0] = r0; res[1] = r1;
+        bool ok = true;
+        for (int a = 0; a < NA; a++)
+            ok = ok && (a == 1 ? (st.res_ref[1] | ((uint32_t)st.act[1] << 8)) == res[1] : st.res_ref[a] == res[a]);
+        return ok;
     }
-}
+
+    void end_step(const Step& st, World& S, bool done, Mismatch&) {
+        if (done) { fresh = true; return; }
+        Tables TS = S.tabs();
+        r0 = pickup_execute(S.E, TS, C, st.nxt[0]);
+        if (!pre.force && pre.thr != ~0u) {   // which rare path agv_fin takes: the source list's final length
+            uint32_t len = 0;
+            for (int i = 0; i < 6; i++) len = pre.m[i] ? S.E.w[7 + i] >> 16 : len;
+            if (len > pre.thr) rare[pre.thr]++;
+        }
+        mv = 0; pend = 0;
+        r1 = agv_fin(S.E, TS, pre, &mv, &pend);
+    }
+};
 
 }  // namespace
 
@@ -76,9 +86,8 @@ extern "C" {
 // the other agents.  out: cases, mismatches, cases with pre_len == 0 -> len > 0, with pre_len == 1 ->
 // len >= 2, pickups, drops that push.  msg: the first mismatch.
 void agv_sweep(int64_t* out, char* msg, int msg_len) {
-    static double lut[RLUT_SIZE];
     for (int i = 0; i < 6; i++) out[i] = 0;
-    msg[0] = 0;
+    Mismatch bad(out + 1, msg, msg_len);
     // carried tray: none, an empty one, and one of each type unprocessed / processed / packaged
     struct Hand { int has, count, type, processed, packaged; };
     Hand hands[11];
@@ -99,12 +108,11 @@ void agv_sweep(int64_t* out, char* msg, int msg_len) {
         const int dst = nib(nibs(0xF, 0xF, L_M1Q, L_M0Q, L_STORAGE, 0xF), loc) == 0xF ? -1
                         : nib(nibs(0xF, 0xF, L_M1Q, L_M0Q, L_STORAGE, 0xF), loc);
         World W;
-        memset(&W, 0, sizeof(W));
-        memset(W.snext, 0x77, sizeof(W.snext));     // stale links: a missing store shows
-        memset(W.scstep, 0x55, sizeof(W.scstep));
+        poison_world(W);
         // storage at its cap (capmode 0) or below it
         const int storage_len = src == L_STORAGE ? slen : 0;
-        const Cfg C = make_cfg(capmode == 0 ? storage_len : storage_len + 1, lut);
+        Cfg C = default_cfg();
+        C.storage_cap = capmode == 0 ? storage_len : storage_len + 1;
         env_clear(W.E, C);
         W.E.set_norders(10);
         // orders 0..7 for list trays (types, colours and processed / packaged states vary), 8 carried
@@ -147,94 +155,23 @@ void agv_sweep(int64_t* out, char* msg, int msg_len) {
         if (rb & 8u) out[4]++;
         if ((rb & 16u) && dst >= 0 && !(dst == L_STORAGE && capmode == 0)) out[5]++;
         out[0]++;
-        if (!(same(A, B) && ra == rb && mva == mvb && pa == pb)) {
-            if (!out[1]++)
-                snprintf(msg, (size_t)msg_len, "action %d loc %d hand %d slen %d dlen %d capmode %d change %d: r %x/%x mv %d/%d "
-                         "pend %x/%x w6 %x/%x state %d", action, loc, h, slen, dlen, capmode, change, ra, rb, mva, mvb, pa, pb,
-                         A.E.w[6], B.E.w[6], (int)same(A, B));
-        }
+        bad.check(same_world(A, B) && ra == rb && mva == mvb && pa == pb,
+                  "action %d loc %d hand %d slen %d dlen %d capmode %d change %d: r %x/%x mv %d/%d pend %x/%x w6 %x/%x state %d",
+                  action, loc, h, slen, dlen, capmode, change, ra, rb, mva, mvb, pa, pb, A.E.w[6], B.E.w[6], (int)same_world(A, B));
     }
 }
 
 // (b) `envs` envs x `steps` steps of uniform-random actions with auto-reset: the plain step against
-// the step in P's schedule (AGV of step k -> agv_pre of k+1 -> the rest of step k -> pickup of
-// k+1 -> agv_fin).  out: env-steps compared, mismatches, rare path 0 (front new), rare path 1
-// (successor new), resets.
+// the step in P's schedule.  out: env-steps compared, mismatches, rare path 0 (front new), rare
+// path 1 (successor new), resets.
 void agv_replay(int envs, int steps, int num_orders, uint64_t seed, int64_t* out, char* msg, int msg_len) {
-    static double lut[RLUT_SIZE];
-    const double w[NW] = {100.0, 10.0, -0.1, 1.0, 5.0, -1.0, 2.0, -0.1, 10.0, -5.0, 5.0, 1.0, -2.0, 20.0, 2.0, -1.0};
-    build_reward_lut(w, 10, lut);
-    const Cfg C = make_cfg(100, lut);
     for (int i = 0; i < 5; i++) out[i] = 0;
-    msg[0] = 0;
-    const int nact[NA] = {3, 8, 3, 3, 3, 3, 3, 3};
-    for (int e = 0; e < envs; e++) {
-        Lcg ga{seed * 1000003ull + (uint64_t)e}, gr_ref{seed + 77ull * (uint64_t)e}, gr_split = gr_ref;
-        World R, S;
-        memset(&R, 0, sizeof(R));
-        memset(&S, 0, sizeof(S));
-        reset_world(R, C, num_orders, gr_ref);
-        reset_world(S, C, num_orders, gr_split);
-        Tables TR = R.tabs(), TS = S.tabs();
-        int act[NA], nxt[NA];
-        for (int a = 0; a < NA; a++) nxt[a] = (int)ga.next((uint32_t)nact[a]);
-        bool fresh = true;
-        uint32_t r0 = 0, r1 = 0, pend = 0;
-        int mv = 0;
-        for (int k = 0; k < steps; k++) {
-            for (int a = 0; a < NA; a++) { act[a] = nxt[a]; nxt[a] = (int)ga.next((uint32_t)nact[a]); }
-            // plain step
-            uint32_t res_ref[NA], res[NA];
-            double rew[NA];
-            env_step<true>(R.E, TR, C, act, nullptr, res_ref, rew);
-            // P's schedule
-            if (fresh) {   // the launch's first step, and the step after a reset: both agents in place
-                r0 = pickup_execute(S.E, TS, C, act[0]);
-                mv = 0; pend = 0;
-                r1 = agv_execute<true>(S.E, TS, C, act[1], &mv, &pend) | ((uint32_t)act[1] << 8);
-                if (mv) S.E.set_loc(mv);
-                fresh = false;
-            }
-            const AgvPre pre = agv_pre(S.E, TS, C, nxt[1]);   // step k + 1's AGV, its own half
-            if (pend) agv_pack_drop(S.E, TS, C, pend);
-            // the rest of step k: the move lands inside the run (machine_execute does not read the
-            // location), the pickup station and the AGV have acted (255 = no action)
-            if (mv) S.E.set_loc(mv);
-            int rest[NA];
-            for (int a = 0; a < NA; a++) rest[a] = a < 2 ? 255 : act[a];
-            env_advance<true>(S.E, TS, C, rest, nullptr, res);
-            res[0] = r0; res[1] = r1;
-            // compare: state words, results, the live tables.  The carried slot's link is dead (no
-            // list holds it; every push rewrites it) and agv_pre may already have cleared it.
-            bool ok = memcmp(R.E.w, S.E.w, sizeof(R.E.w)) == 0;
-            for (int a = 0; a < NA; a++) ok = ok && (a == 1 ? (res_ref[1] | ((uint32_t)act[1] << 8)) == res[1] : res_ref[a] == res[a]);
-            const int nslot = R.E.slot_next(), carry = R.E.carry();
-            ok = ok && memcmp(R.orders, S.orders, 4u * (size_t)num_orders) == 0 && memcmp(R.scode, S.scode, 2u * (size_t)nslot) == 0;
-            for (int s = 0; s < nslot; s++) ok = ok && (s == carry || R.snext[s] == S.snext[s]) && R.scstep[s] == S.scstep[s];
-            out[0]++;
-            if (!ok && !out[1]++) snprintf(msg, (size_t)msg_len, "env %d step %d (orders %d): split differs from the plain step", e, k, num_orders);
-            // end of step: auto-reset (the next table continues each side's own stream)
-            const int nord = R.E.norders();
-            const bool done = (R.E.ncompleted() == nord && nord > 0 && R.E.next_order() == nord) || R.E.step() >= C.max_steps;
-            R.E.set_step(R.E.step() + 1);
-            S.E.set_step(S.E.step() + 1);
-            if (done) {
-                reset_world(R, C, nord, gr_ref);
-                reset_world(S, C, nord, gr_split);
-                fresh = true;
-                out[4]++;
-            } else {
-                r0 = pickup_execute(S.E, TS, C, nxt[0]);
-                if (!pre.force && pre.thr != ~0u) {   // which rare path agv_fin takes: the source list's final length
-                    uint32_t len = 0;
-                    for (int i = 0; i < 6; i++) len = pre.m[i] ? S.E.w[7 + i] >> 16 : len;
-                    if (len > pre.thr) out[2 + pre.thr]++;
-                }
-                mv = 0; pend = 0;
-                r1 = agv_fin(S.E, TS, pre, &mv, &pend);
-            }
-        }
-    }
+    Mismatch bad(out + 1, msg, msg_len);
+    const Cfg C = default_cfg();
+    PSchedule m{C, out + 2};
+    const Replayed n = replay(C, envs, steps, num_orders, seed, m, bad, "split differs from the plain step");
+    out[0] = n.compared;
+    out[4] = n.resets;
 }
 
 }  // extern "C"

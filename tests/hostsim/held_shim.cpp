@@ -1,37 +1,9 @@
 // held_shim.cpp — TEST-ONLY host build of fjsp_env.h's held_words (the held-tray words of
 // fjsp_step_held) for tests/test_held_host.py: replays of the reference's recorded runs (actions and
 // order tables from the fixtures) and constructed states with stale code bits.
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-#define FJSP_DEV inline
-#include "../../multi-agent-rl-for-fjsp_amd/csrc/fjsp_env.h"
-using namespace fjsp;
+#include "world.h"
 
 namespace {
-
-struct World {   // one env with its tables (stride 1)
-    Env E;
-    uint32_t orders[MAX_ORDERS];
-    uint16_t scode[MAX_SLOTS];
-    uint8_t snext[MAX_SLOTS];
-    uint16_t scstep[MAX_SLOTS];
-    Tables tabs() { return Tables{orders, scode, snext, scstep, 1}; }
-};
-
-Cfg make_cfg(const double* lut) {   // the default config
-    Cfg C;
-    C.step_size = 10; C.max_steps = 200; C.tray_cap = 5; C.mask_tray_cap = 5; C.storage_cap = 100;
-    C.pool0 = 1000; C.pkg_cap = 20; C.ptk_small = 6; C.ptk_big = 12; C.ptk_pack = 3;
-    C.lut = lut;
-    return C;
-}
-
-void reset_world(World& W, const Cfg& C, int num_orders, const uint8_t* table) {   // table [num_orders][3]
-    env_clear(W.E, C);
-    W.E.set_norders(num_orders);
-    for (int o = 0; o < num_orders; o++) W.orders[o] = ow_make(table[3 * o], table[3 * o + 1], table[3 * o + 2]);
-}
 
 // held_words on the state itself, which must stay as it is (status included)
 bool held_pure(const Env& E, uint32_t* v) {
@@ -51,10 +23,7 @@ extern "C" {
 // held_words changed, [4] status bits ORed over the run.
 void held_replay(const uint8_t* actions, const uint32_t* results, const uint8_t* term, const uint8_t* trunc,
                  const uint8_t* orders, int episodes, int num_orders, int T, uint32_t* held, int64_t* out) {
-    static double lut[RLUT_SIZE];
-    const double w[NW] = {100.0, 10.0, -0.1, 1.0, 5.0, -1.0, 2.0, -0.1, 10.0, -5.0, 5.0, 1.0, -2.0, 20.0, 2.0, -1.0};
-    build_reward_lut(w, 10, lut);
-    const Cfg C = make_cfg(lut);
+    const Cfg C = default_cfg();
     for (int i = 0; i < 5; i++) out[i] = 0;
     World W;
     memset(&W, 0, sizeof(W));
@@ -73,8 +42,7 @@ void held_replay(const uint8_t* actions, const uint32_t* results, const uint8_t*
         out[3] += !held_pure(W.E, held + 3 * t);
         out[4] |= W.E.status();
         const int nord = W.E.norders();
-        const bool te = W.E.ncompleted() == nord && nord > 0 && W.E.next_order() == nord;
-        const bool tr = W.E.step() >= C.max_steps;
+        const bool te = all_done(W.E), tr = W.E.step() >= C.max_steps;
         out[1] += (te != (term[t] != 0)) || (tr != (trunc[t] != 0));
         W.E.set_step(W.E.step() + 1);
         if (te || tr) {
@@ -92,8 +60,7 @@ void held_replay(const uint8_t* actions, const uint32_t* results, const uint8_t*
 //   2 the AGV carrying `code` at the small machine            3 after its DROP there
 //   4 both holding an empty tray of the same order / start    5 a fresh env
 void held_cases(int code, uint32_t* v, uint32_t* raw, int* ok) {
-    static double lut[RLUT_SIZE];
-    const Cfg C = make_cfg(lut);
+    const Cfg C = default_cfg();
     World W;
     memset(&W, 0, sizeof(W));
     const uint8_t table[3] = {9, 1, 1};   // one SMALL order of 9 products

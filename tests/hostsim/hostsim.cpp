@@ -2,12 +2,9 @@
 // (multi-agent-rl-for-fjsp_amd/csrc/fjsp_env.h) so its closed-form logic can be checked
 // against the oracle on CPU in the build container (no GPU there).  The product library
 // (libfjsp.so) never contains or loads this; the GPU parity tests are the real proof.
-#include <stdint.h>
-#include <string.h>
 #include <stdlib.h>
-#define FJSP_DEV inline
-#include "../../multi-agent-rl-for-fjsp_amd/csrc/fjsp_env.h"
-using namespace fjsp;
+
+#include "world.h"
 
 struct HS {
     int n; Cfg C;
@@ -39,9 +36,8 @@ void* hs_create(const int32_t* c, int n) {
     h->C.step_size = c[4]; h->C.max_steps = c[5]; h->C.tray_cap = c[1]; h->C.mask_tray_cap = c[2];
     h->C.storage_cap = c[3]; h->C.pool0 = c[0] < 1000 ? c[0] : 1000; h->C.pkg_cap = c[10];
     h->C.ptk_small = c[7] / c[4]; h->C.ptk_big = c[8] / c[4]; h->C.ptk_pack = c[9] / c[4];
-    const double w[NW] = {100.0, 10.0, -0.1, 1.0, 5.0, -1.0, 2.0, -0.1, 10.0, -5.0, 5.0, 1.0, -2.0, 20.0, 2.0, -1.0};
     double* lut = (double*)calloc(RLUT_SIZE, sizeof(double));
-    build_reward_lut(w, c[4], lut);
+    default_lut(lut, c[4]);
     h->C.lut = lut;
     h->E = (Env*)calloc(n, sizeof(Env));
     h->orders = (uint32_t*)calloc((size_t)MAX_ORDERS * n, 4);
@@ -101,12 +97,10 @@ void hs_step(void* p, const uint8_t* actions, int autoreset, int32_t* i32, int8_
         int act[8]; for (int a = 0; a < 8; a++) act[a] = actions[8 * e + a];
         env_step<true>(E, T, h->C, act, nullptr, res + 8 * e, rew + 8 * e);
         obs_out(h, e, i32, i8, f32, mk);
-        const int nord = E.norders();
-        int all_done = E.ncompleted() == nord && nord > 0 && E.next_order() == nord;
-        int tr = E.step() >= h->C.max_steps;
-        term[e] = (uint8_t)all_done; trunc[e] = (uint8_t)tr; status[e] = E.status();
+        const bool te = all_done(E), tr = E.step() >= h->C.max_steps;
+        term[e] = (uint8_t)te; trunc[e] = (uint8_t)tr; status[e] = E.status();
         E.set_step(E.step() + 1);
-        if (autoreset && (all_done || tr)) reset_one(h, e, nord);
+        if (autoreset && (te || tr)) reset_one(h, e, E.norders());
         obs_out(h, e, ri32, ri8, rf32, rmk);
     }
 }

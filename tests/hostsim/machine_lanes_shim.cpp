@@ -4,50 +4,9 @@
 // is the sequence AM ran before on one Env: machine_execute<0>, machine_execute<1>,
 // machines_run<true>.  groups 4 and 2: machine g on lane group g < 2 (the other groups idle);
 // groups 1: the sequence itself with the queue fronts' successors known ahead (next_known).
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-#define FJSP_DEV inline
-#include "../../multi-agent-rl-for-fjsp_amd/csrc/fjsp_env.h"
-using namespace fjsp;
+#include "replay.h"
 
 namespace {
-
-struct World {   // one env with its tables (stride 1)
-    Env E;
-    uint32_t orders[MAX_ORDERS];
-    uint16_t scode[MAX_SLOTS];
-    uint8_t snext[MAX_SLOTS];
-    uint16_t scstep[MAX_SLOTS];
-    Tables tabs() { return Tables{orders, scode, snext, scstep, 1}; }
-};
-
-Cfg make_cfg(const double* lut) {
-    Cfg C;
-    C.step_size = 10; C.max_steps = 200; C.tray_cap = 5; C.mask_tray_cap = 5; C.storage_cap = 100;
-    C.pool0 = 1000; C.pkg_cap = 20; C.ptk_small = 6; C.ptk_big = 12; C.ptk_pack = 3;
-    C.lut = lut;
-    return C;
-}
-
-struct Lcg {
-    uint64_t s;
-    uint32_t next(uint32_t n) { s = s * 6364136223846793005ull + 1442695040888963407ull; return (uint32_t)(s >> 33) % n; }
-};
-
-void reset_world(World& W, const Cfg& C, int num_orders, Lcg& g) {
-    env_clear(W.E, C);
-    W.E.set_norders(num_orders);
-    for (int o = 0; o < num_orders; o++) {
-        const int n = 1 + (int)g.next(9), ty = 1 + (int)g.next(3), co = 1 + (int)g.next(3);
-        W.orders[o] = ow_make(n, ty, co);
-    }
-}
-
-bool same_tables(const World& A, const World& B) {
-    return memcmp(A.orders, B.orders, sizeof(A.orders)) == 0 && memcmp(A.scode, B.scode, sizeof(A.scode)) == 0 &&
-           memcmp(A.snext, B.snext, sizeof(A.snext)) == 0 && memcmp(A.scstep, B.scstep, sizeof(A.scstep)) == 0;
-}
 
 // what the inputs contain, counted on the sequence alone
 struct Events {
@@ -180,7 +139,7 @@ bool both(const World& W, const Cfg& C, int groups, int act2, int act3, int drop
         rb = lanes.machines(B, C, act2, act3, known(false, a0, B.E, L_M0Q), known(false, a1, lanes.M1, L_M0Q));
         B.E = lanes.merged(B.E);
     }
-    return memcmp(A.E.w, B.E.w, sizeof(A.E.w)) == 0 && same_tables(A, B) && memcmp(&ra, &rb, sizeof(ra)) == 0;
+    return same_world(A, B) && memcmp(&ra, &rb, sizeof(ra)) == 0;
 }
 
 // constructed state of one machine: 0 empty; 1 one tray queued; 2 three queued; 3 busy, its last
@@ -204,6 +163,121 @@ void build_machine(World& W, int m, int state, int step, int order) {
     }
 }
 
+// S's step in AM's schedule, the machines on the lanes, in launches of `launch` steps.  Between two
+// steps S.E is group 0's own Env (machine 1's words poisoned); for the comparison with the plain
+// step it holds the words the launch epilogue would store.
+struct AMSchedule {
+    static constexpr int AHEAD = 0;
+    const Cfg& C;
+    const int groups, launch;
+    Events& ev;
+    int64_t& fresh_steps;
+    Lanes lanes;
+    Env G0;   // group 0's Env while S.E holds the merged words
+    bool fresh;
+
+    void begin(World&) { fresh = true; memset(&lanes, 0, sizeof(lanes)); }
+
+    bool step(Step& st, World& S) {
+        Tables TS = S.tabs();
+        const int* act = st.act;
+        if (st.k % launch == 0) {   // a launch starts: both groups load their words
+            if (st.k > 0 && groups > 1) S.E = lanes.merged(S.E);
+            if (groups > 1) {
+                Env full = S.E;
+                lanes.load(S.E);
+                S.E.w[7 + L_M1Q] = full.w[7 + L_M1Q];   // group 0 loads the whole env: its AGV of
+                S.E.w[7 + L_M1R] = full.w[7 + L_M1R];   // this step needs machine 1's lists
+            }
+            fresh = true;
+        }
+        // the events, on the plain sequence: the machines of a copy of R after its pickup and AGV
+        {
+            World Q = st.R0;
+            Tables TQ = Q.tabs();
+            int mv = 0;
+            pickup_execute(Q.E, TQ, C, act[0]);
+            agv_execute(Q.E, TQ, C, act[1], &mv);
+            machines_ref(Q, C, act[2], act[3], -1, -1, &ev);
+        }
+        // S: the top of the step, then the pickup and the AGV (fresh: on group 0 itself, with the
+        // hand-over; else P's, on AM's post), the machines, the packaging stations
+        Env& E0 = S.E;
+        const Ahead a0 = ahead(E0, TS, L_M0Q);
+        const Ahead a1 = groups > 1 ? ahead(lanes.M1, TS, L_M0Q) : ahead(E0, TS, L_M1Q);
+        uint32_t pend = 0;
+        int mv = 0;
+        if (groups > 1 && !fresh) {
+            World Q = S;
+            Q.E = lanes.merged(S.E);
+            Tables TQ = Q.tabs();   // Q's own copy of the tables
+            pickup_execute(Q.E, TQ, C, act[0]);
+            agv_execute<true>(Q.E, TQ, C, act[1], &mv, &pend);
+            if (mv) Q.E.set_loc(mv);
+            if (pend) agv_pack_drop(Q.E, TQ, C, pend);
+            const uint32_t w17 = S.E.w[17], w19 = S.E.w[19];
+            memcpy(S.orders, Q.orders, sizeof(S.orders)); memcpy(S.scode, Q.scode, sizeof(S.scode));
+            memcpy(S.snext, Q.snext, sizeof(S.snext)); memcpy(S.scstep, Q.scstep, sizeof(S.scstep));
+            Q.E.w[2] &= ~lanes.M1.w[2] | S.E.w[2];   // group 1's status bits stay its own
+            lanes.apply(S.E, Q.E);
+            S.E.w[17] = w17; S.E.w[19] = w19;
+        } else {
+            pickup_execute(E0, TS, C, act[0]);
+            agv_execute<true>(E0, TS, C, act[1], &mv, &pend);
+            if (mv) E0.set_loc(mv);
+            if (pend) agv_pack_drop(E0, TS, C, pend);
+            if (groups > 1) {
+                ev.handover_changed += lanes.handover(E0);
+                fresh_steps++;
+            }
+        }
+        MOut rm;
+        if (groups > 1)
+            rm = lanes.machines(S, C, act[2], act[3], known(fresh, a0, E0, L_M0Q), known(fresh, a1, lanes.M1, L_M0Q));
+        else
+            rm = machines_ref(S, C, act[2], act[3], known(fresh, a0, E0, L_M0Q), known(fresh, a1, E0, L_M1Q), nullptr);
+        {   // the packaging stations, as the plain step runs them
+            int sp[4] = {0, 0, 0, 0}, orders_done = 0;
+            pack_execute<0>(E0, act[4], &sp[0]); pack_execute<1>(E0, act[5], &sp[1]);
+            pack_execute<2>(E0, act[6], &sp[2]); pack_execute<3>(E0, act[7], &sp[3]);
+            const int step = E0.step();
+            const bool d0 = pack_due<0>(E0, TS, step), d1 = pack_due<1>(E0, TS, step);
+            const bool d2 = pack_due<2>(E0, TS, step), d3 = pack_due<3>(E0, TS, step);
+            pack_run<0>(E0, TS, C, sp[0], d0, &orders_done); pack_run<1>(E0, TS, C, sp[1], d1, &orders_done);
+            pack_run<2>(E0, TS, C, sp[2], d2, &orders_done); pack_run<3>(E0, TS, C, sp[3], d3, &orders_done);
+            E0.set_ncompleted(E0.ncompleted() + orders_done);
+        }
+        bool ok = groups == 1 || lanes.M1.w[0] == S.E.w[0];
+        ok = ok && rm.r[0] == ((st.res_ref[2] & 0xFFu) | ((uint32_t)act[2] << 8)) &&
+             rm.r[1] == ((st.res_ref[3] & 0xFFu) | ((uint32_t)act[3] << 8));
+        fresh = false;
+        if (groups > 1) {   // same_live reads the merged words
+            G0 = S.E;
+            S.E = lanes.merged(G0);
+        }
+        return ok;
+    }
+
+    void end_step(const Step& st, World& S, bool done, Mismatch& bad) {
+        lanes.M1.set_step(lanes.M1.step() + 1);
+        if (done) {
+            fresh = true;
+            if (groups == 1) return;
+            // group 1's own reset of its lane against a fresh load
+            Env full = S.E;
+            Lanes fresh_lanes;
+            fresh_lanes.load(full);
+            mach_lane_clear(lanes.M1);
+            lanes.M1.set_norders(S.E.norders());
+            bad.check(memcmp(lanes.M1.w, fresh_lanes.M1.w, sizeof(lanes.M1.w)) == 0, "groups %d env %d step %d: reset of lane group 1",
+                      groups, st.env, st.k);
+        } else if (groups > 1) {
+            G0.set_step(G0.step() + 1);
+            S.E = G0;
+        }
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -212,12 +286,11 @@ extern "C" {
 // the trays on the machines of one order or of two.  out: cases, mismatches, then the events
 // [both_start, start_signal, both_signal, both_done, done_same_order, overwrite].
 void mlanes_sweep(int groups, int64_t* out, char* msg, int msg_len) {
-    static double lut[RLUT_SIZE];
     for (int i = 0; i < 8; i++) out[i] = 0;
-    msg[0] = 0;
+    Mismatch bad(out + 1, msg, msg_len);
     Events ev;
     memset(&ev, 0, sizeof(ev));
-    const Cfg C = make_cfg(lut);
+    const Cfg C = default_cfg();
     const int step = 17;
     for (int st0 = 0; st0 < NSTATES; st0++)
     for (int st1 = 0; st1 < NSTATES; st1++)
@@ -225,9 +298,7 @@ void mlanes_sweep(int groups, int64_t* out, char* msg, int msg_len) {
     for (int drop = 0; drop < 3; drop++)
     for (int same = 0; same < 2; same++) {
         World W;
-        memset(&W, 0, sizeof(W));
-        memset(W.snext, 0x77, sizeof(W.snext));     // stale links: a missing store shows
-        memset(W.scstep, 0x55, sizeof(W.scstep));
+        poison_world(W);
         env_clear(W.E, C);
         W.E.set_norders(10);
         W.E.set_step(step);
@@ -235,9 +306,9 @@ void mlanes_sweep(int groups, int64_t* out, char* msg, int msg_len) {
         build_machine(W, 0, st0, step, 0);
         build_machine(W, 1, st1, step, same ? 0 : 1);
         out[0]++;
-        if (!both(W, C, groups, acts % 3, acts / 3, drop, ev) && !out[1]++)
-            snprintf(msg, (size_t)msg_len, "groups %d machines %d / %d actions %d / %d drop %d same order %d: the lanes differ from "
-                     "the sequence", groups, st0, st1, acts % 3, acts / 3, drop, same);
+        bad.check(both(W, C, groups, acts % 3, acts / 3, drop, ev),
+                  "groups %d machines %d / %d actions %d / %d drop %d same order %d: the lanes differ from the sequence",
+                  groups, st0, st1, acts % 3, acts / 3, drop, same);
     }
     out[2] = ev.both_start; out[3] = ev.start_signal; out[4] = ev.both_signal; out[5] = ev.both_done;
     out[6] = ev.done_same_order; out[7] = ev.overwrite;
@@ -250,134 +321,21 @@ void mlanes_sweep(int groups, int64_t* out, char* msg, int msg_len) {
 // handover_changed, starts, signals, products done].
 void mlanes_replay(int groups, int envs, int steps, int launch, int num_orders, uint64_t seed, int64_t* out, char* msg,
                    int msg_len) {
-    static double lut[RLUT_SIZE];
     for (int i = 0; i < 14; i++) out[i] = 0;
-    msg[0] = 0;
+    Mismatch bad(out + 1, msg, msg_len);
     Events ev;
     memset(&ev, 0, sizeof(ev));
-    const double w[NW] = {100.0, 10.0, -0.1, 1.0, 5.0, -1.0, 2.0, -0.1, 10.0, -5.0, 5.0, 1.0, -2.0, 20.0, 2.0, -1.0};
-    build_reward_lut(w, 10, lut);
-    const Cfg C = make_cfg(lut);
-    const int nact[NA] = {3, 8, 3, 3, 3, 3, 3, 3};
-    for (int e = 0; e < envs; e++) {
-        Lcg ga{seed * 1000003ull + (uint64_t)e}, gr_ref{seed + 77ull * (uint64_t)e}, gr_s = gr_ref;
-        // R: the plain step.  S: the step in AM's schedule, the machines on the lanes.
-        World R, S;
-        memset(&R, 0, sizeof(R));
-        memset(&S, 0, sizeof(S));
-        reset_world(R, C, num_orders, gr_ref);
-        reset_world(S, C, num_orders, gr_s);
-        Tables TR = R.tabs(), TS = S.tabs();
-        Lanes lanes;
-        bool fresh = true;
-        for (int k = 0; k < steps; k++) {
-            int act[NA];
-            for (int a = 0; a < NA; a++) act[a] = (int)ga.next((uint32_t)nact[a]);
-            if (k % launch == 0) {   // a launch starts: both groups load their words
-                if (k > 0 && groups > 1) S.E = lanes.merged(S.E);
-                if (groups > 1) {
-                    Env full = S.E;
-                    lanes.load(S.E);
-                    S.E.w[7 + L_M1Q] = full.w[7 + L_M1Q];   // group 0 loads the whole env: its AGV of
-                    S.E.w[7 + L_M1R] = full.w[7 + L_M1R];   // this step needs machine 1's lists
-                }
-                fresh = true;
-            }
-            uint32_t res_ref[NA];
-            double rew[NA];
-            // the events, on the plain sequence: the machines of a copy of R after its pickup and AGV
-            {
-                World Q = R;
-                Tables TQ = Q.tabs();
-                int mv = 0;
-                pickup_execute(Q.E, TQ, C, act[0]);
-                agv_execute(Q.E, TQ, C, act[1], &mv);
-                machines_ref(Q, C, act[2], act[3], -1, -1, &ev);
-            }
-            env_step<true>(R.E, TR, C, act, nullptr, res_ref, rew);
-            // S: the top of the step, then the pickup and the AGV (fresh: on group 0 itself, with the
-            // hand-over; else P's, on AM's post), the machines, the packaging stations
-            Env& G0 = S.E;
-            const Ahead a0 = ahead(G0, TS, L_M0Q);
-            const Ahead a1 = groups > 1 ? ahead(lanes.M1, TS, L_M0Q) : ahead(G0, TS, L_M1Q);
-            uint32_t pend = 0;
-            int mv = 0;
-            if (groups > 1 && !fresh) {
-                World Q = S;
-                Q.E = lanes.merged(S.E);
-                Tables TQ = Q.tabs();   // Q's own copy of the tables
-                pickup_execute(Q.E, TQ, C, act[0]);
-                agv_execute<true>(Q.E, TQ, C, act[1], &mv, &pend);
-                if (mv) Q.E.set_loc(mv);
-                if (pend) agv_pack_drop(Q.E, TQ, C, pend);
-                const uint32_t w17 = S.E.w[17], w19 = S.E.w[19];
-                memcpy(S.orders, Q.orders, sizeof(S.orders)); memcpy(S.scode, Q.scode, sizeof(S.scode));
-                memcpy(S.snext, Q.snext, sizeof(S.snext)); memcpy(S.scstep, Q.scstep, sizeof(S.scstep));
-                Q.E.w[2] &= ~lanes.M1.w[2] | S.E.w[2];   // group 1's status bits stay its own
-                lanes.apply(S.E, Q.E);
-                S.E.w[17] = w17; S.E.w[19] = w19;
-            } else {
-                pickup_execute(G0, TS, C, act[0]);
-                agv_execute<true>(G0, TS, C, act[1], &mv, &pend);
-                if (mv) G0.set_loc(mv);
-                if (pend) agv_pack_drop(G0, TS, C, pend);
-                if (groups > 1) {
-                    ev.handover_changed += lanes.handover(G0);
-                    out[3]++;
-                }
-            }
-            MOut rm;
-            if (groups > 1)
-                rm = lanes.machines(S, C, act[2], act[3], known(fresh, a0, G0, L_M0Q), known(fresh, a1, lanes.M1, L_M0Q));
-            else
-                rm = machines_ref(S, C, act[2], act[3], known(fresh, a0, G0, L_M0Q), known(fresh, a1, G0, L_M1Q), nullptr);
-            {   // the packaging stations, as the plain step runs them
-                int st[4] = {0, 0, 0, 0}, orders_done = 0;
-                pack_execute<0>(G0, act[4], &st[0]); pack_execute<1>(G0, act[5], &st[1]);
-                pack_execute<2>(G0, act[6], &st[2]); pack_execute<3>(G0, act[7], &st[3]);
-                const int step = G0.step();
-                const bool d0 = pack_due<0>(G0, TS, step), d1 = pack_due<1>(G0, TS, step);
-                const bool d2 = pack_due<2>(G0, TS, step), d3 = pack_due<3>(G0, TS, step);
-                pack_run<0>(G0, TS, C, st[0], d0, &orders_done); pack_run<1>(G0, TS, C, st[1], d1, &orders_done);
-                pack_run<2>(G0, TS, C, st[2], d2, &orders_done); pack_run<3>(G0, TS, C, st[3], d3, &orders_done);
-                G0.set_ncompleted(G0.ncompleted() + orders_done);
-            }
-            const Env M = groups > 1 ? lanes.merged(S.E) : S.E;
-            bool ok = memcmp(R.E.w, M.w, sizeof(M.w)) == 0 && (groups == 1 || lanes.M1.w[0] == S.E.w[0]);
-            ok = ok && rm.r[0] == ((res_ref[2] & 0xFFu) | ((uint32_t)act[2] << 8)) && rm.r[1] == ((res_ref[3] & 0xFFu) | ((uint32_t)act[3] << 8));
-            const int nslot = R.E.slot_next(), carry = R.E.carry();
-            ok = ok && memcmp(R.orders, S.orders, 4u * (size_t)num_orders) == 0 && memcmp(R.scode, S.scode, 2u * (size_t)nslot) == 0;
-            for (int s = 0; s < nslot; s++) ok = ok && (s == carry || R.snext[s] == S.snext[s]) && R.scstep[s] == S.scstep[s];
-            out[0]++;
-            if (!ok && !out[1]++)
-                snprintf(msg, (size_t)msg_len, "groups %d env %d step %d (orders %d, fresh %d): the lanes differ from the plain step",
-                         groups, e, k, num_orders, (int)fresh);
-            fresh = false;
-            const int nord = R.E.norders();
-            const bool done = (R.E.ncompleted() == nord && nord > 0 && R.E.next_order() == nord) || R.E.step() >= C.max_steps;
-            R.E.set_step(R.E.step() + 1);
-            S.E.set_step(S.E.step() + 1);
-            lanes.M1.set_step(lanes.M1.step() + 1);
-            if (done) {
-                reset_world(R, C, nord, gr_ref);
-                reset_world(S, C, nord, gr_s);
-                if (groups > 1) {   // group 1's own reset of its lane against a fresh load
-                    Env full = S.E;
-                    Lanes fresh_lanes;
-                    fresh_lanes.load(full);
-                    mach_lane_clear(lanes.M1);
-                    lanes.M1.set_norders(nord);
-                    if (memcmp(lanes.M1.w, fresh_lanes.M1.w, sizeof(lanes.M1.w)) != 0 && !out[1]++)
-                        snprintf(msg, (size_t)msg_len, "groups %d env %d step %d: reset of lane group 1", groups, e, k);
-                }
-                fresh = true;
-                out[2]++;
-            }
-        }
-    }
+    const Cfg C = default_cfg();
+    AMSchedule m{C, groups, launch, ev, out[3]};
+    char what[64];
+    snprintf(what, sizeof(what), "the lanes differ from the plain step (groups %d)", groups);
+    const Replayed n = replay(C, envs, steps, num_orders, seed, m, bad, what);
+    out[0] = n.compared;
+    out[2] = n.resets;
     out[4] = ev.both_start; out[5] = ev.start_signal; out[6] = ev.both_signal; out[7] = ev.both_done;
     out[8] = ev.done_same_order; out[9] = ev.overwrite; out[10] = ev.handover_changed;
     out[11] = ev.starts; out[12] = ev.signals; out[13] = ev.dones;
 }
 
 }  // extern "C"
+

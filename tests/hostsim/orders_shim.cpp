@@ -2,44 +2,11 @@
 // fjsp_put_orders) with the state machine of fjsp_env.h, for tests/test_orders_host.py: replays of
 // the reference's recorded runs on caller-chosen order books and with orders arriving during the
 // episode (tests/golden/orders.npz), and single calls on a caller-held world (rejections, appends).
-#include <stddef.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-#define FJSP_DEV inline
+#include "world.h"
+
 #include "../../multi-agent-rl-for-fjsp_amd/csrc/fjsp_orders.h"
-using namespace fjsp;
 
 namespace {
-
-struct World {   // one env with its tables (stride 1) and its pre-draw record
-    Env E;
-    uint32_t pgw;
-    uint32_t orders[MAX_ORDERS];
-    uint16_t scode[MAX_SLOTS];
-    uint8_t snext[MAX_SLOTS];
-    uint16_t scstep[MAX_SLOTS];
-    Tables tabs() { return Tables{orders, scode, snext, scstep, 1}; }
-};
-
-const double* reward_lut() {   // the default weights
-    static double lut[RLUT_SIZE];
-    static bool built = false;
-    if (!built) {
-        const double w[NW] = {100.0, 10.0, -0.1, 1.0, 5.0, -1.0, 2.0, -0.1, 10.0, -5.0, 5.0, 1.0, -2.0, 20.0, 2.0, -1.0};
-        build_reward_lut(w, 10, lut);
-        built = true;
-    }
-    return lut;
-}
-
-Cfg make_cfg() {   // the default config
-    Cfg C;
-    C.step_size = 10; C.max_steps = 200; C.tray_cap = 5; C.mask_tray_cap = 5; C.storage_cap = 100;
-    C.pool0 = 1000; C.pkg_cap = 20; C.ptk_small = 6; C.ptk_big = 12; C.ptk_pack = 3;
-    C.lut = reward_lut();
-    return C;
-}
 
 void put_obs(Env& E, const Cfg& C, int32_t* i32, int8_t* i8, float* f32, int8_t* mk) {
     Obs o;
@@ -74,8 +41,8 @@ struct OrdersRun {
 // One recorded run: the book through put_orders_env(append = 0) on a dirty world, the arrivals
 // through put_orders_env(append = 1) before their steps, the recorded actions through env_step.
 void orders_replay(OrdersRun* r) {
-    const Cfg C = make_cfg();
-    World W;
+    const Cfg C = default_cfg();
+    BookWorld W;
     memset(&W, 0xA5, sizeof(W));   // a reset must not depend on what the env held
     W.E.w[3] = 0x12345u;
     W.pgw = 1u;
@@ -98,8 +65,7 @@ void orders_replay(OrdersRun* r) {
         for (int k = 0; k < NA; k++) act[k] = r->actions[t * NA + k];
         env_step<true>(W.E, Tb, C, act, nullptr, r->res + NA * t, r->rew + NA * t);
         put_obs(W.E, C, r->i32 + NI32 * t, r->i8 + NI8 * t, r->f32 + NF32 * t, r->mk + NMASK * t);
-        const int nord = W.E.norders();
-        r->term[t] = W.E.ncompleted() == nord && nord > 0 && W.E.next_order() == nord;
+        r->term[t] = all_done(W.E);
         r->trunc[t] = W.E.step() >= C.max_steps;
         r->oc[t] = W.E.ncompleted();
         r->pk[t] = W.E.total_packaged();
@@ -110,26 +76,28 @@ void orders_replay(OrdersRun* r) {
 }
 
 // ---- single calls on a world the caller holds as bytes
-int orders_world_bytes(void) { return (int)sizeof(World); }
+int orders_world_bytes(void) { return (int)sizeof(BookWorld); }
 // byte offsets of the state words, the pre-draw record and the order table; their counts
 void orders_world_layout(int32_t* out) {
-    out[0] = (int32_t)offsetof(World, E) + (int32_t)offsetof(Env, w);
+    BookWorld W;
+    const char* base = (const char*)&W;
+    out[0] = (int32_t)((const char*)W.E.w - base);
     out[1] = NSTATE;
-    out[2] = (int32_t)offsetof(World, pgw);
-    out[3] = (int32_t)offsetof(World, orders);
+    out[2] = (int32_t)((const char*)&W.pgw - base);
+    out[3] = (int32_t)((const char*)W.orders - base);
     out[4] = MAX_ORDERS;
 }
 // put_orders_env on the world: the env's column of a [K][sstride] table starts at src
 int orders_put(void* world, const uint32_t* src, int sstride, int K, int count, int append) {
-    World& W = *(World*)world;
-    const Cfg C = make_cfg();
+    BookWorld& W = *(BookWorld*)world;
+    const Cfg C = default_cfg();
     Tables Tb = W.tabs();
     return put_orders_env(W.E, Tb, C, src, sstride, K, count, append, &W.pgw) ? 1 : 0;
 }
 // n steps of the built-in heuristic (a state in the middle of an episode); returns the status word
 uint32_t orders_world_run(void* world, int n) {
-    World& W = *(World*)world;
-    const Cfg C = make_cfg();
+    BookWorld& W = *(BookWorld*)world;
+    const Cfg C = default_cfg();
     Tables Tb = W.tabs();
     for (int t = 0; t < n; t++) {
         int act[NA];

@@ -1,40 +1,7 @@
 // pack_shim.cpp — TEST-ONLY host build of fjsp_env.h's pack_words (the pack words of
 // fjsp_step_sched) for tests/test_pack_host.py: replays of the reference's recorded runs (actions,
 // order tables and configs from tests/golden/packaging.npz).
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-#define FJSP_DEV inline
-#include "../../multi-agent-rl-for-fjsp_amd/csrc/fjsp_env.h"
-using namespace fjsp;
-
-namespace {
-
-struct World {   // one env with its tables (stride 1)
-    Env E;
-    uint32_t orders[MAX_ORDERS];
-    uint16_t scode[MAX_SLOTS];
-    uint8_t snext[MAX_SLOTS];
-    uint16_t scstep[MAX_SLOTS];
-    Tables tabs() { return Tables{orders, scode, snext, scstep, 1}; }
-};
-
-// the default config but for the packaging time (in steps), the step limit and the stations' capacity
-Cfg make_cfg(const double* lut, int ptk_pack, int max_steps, int pkg_cap) {
-    Cfg C;
-    C.step_size = 10; C.max_steps = max_steps; C.tray_cap = 5; C.mask_tray_cap = 5; C.storage_cap = 100;
-    C.pool0 = 1000; C.pkg_cap = pkg_cap; C.ptk_small = 6; C.ptk_big = 12; C.ptk_pack = ptk_pack;
-    C.lut = lut;
-    return C;
-}
-
-void reset_world(World& W, const Cfg& C, int num_orders, const uint8_t* table) {   // table [num_orders][3]
-    env_clear(W.E, C);
-    W.E.set_norders(num_orders);
-    for (int o = 0; o < num_orders; o++) W.orders[o] = ow_make(table[3 * o], table[3 * o + 1], table[3 * o + 2]);
-}
-
-}  // namespace
+#include "world.h"
 
 extern "C" {
 
@@ -47,10 +14,8 @@ extern "C" {
 void pack_replay(const uint8_t* actions, const uint32_t* results, const uint8_t* term, const uint8_t* trunc,
                  const uint8_t* orders, int episodes, int num_orders, int T, const int32_t* cfg, uint32_t* pack,
                  int32_t* packaged, int64_t* out) {
-    static double lut[RLUT_SIZE];
-    const double w[NW] = {100.0, 10.0, -0.1, 1.0, 5.0, -1.0, 2.0, -0.1, 10.0, -5.0, 5.0, 1.0, -2.0, 20.0, 2.0, -1.0};
-    build_reward_lut(w, 10, lut);
-    const Cfg C = make_cfg(lut, cfg[0] / 10, cfg[1], cfg[2]);
+    Cfg C = default_cfg();
+    C.ptk_pack = cfg[0] / 10; C.max_steps = cfg[1]; C.pkg_cap = cfg[2];
     for (int i = 0; i < 5; i++) out[i] = 0;
     World W;
     memset(&W, 0, sizeof(W));
@@ -72,8 +37,7 @@ void pack_replay(const uint8_t* actions, const uint32_t* results, const uint8_t*
         packaged[t] = W.E.total_packaged();
         out[4] |= W.E.status();
         const int nord = W.E.norders();
-        const bool te = W.E.ncompleted() == nord && nord > 0 && W.E.next_order() == nord;
-        const bool tr = W.E.step() >= C.max_steps;
+        const bool te = all_done(W.E), tr = W.E.step() >= C.max_steps;
         out[1] += (te != (term[t] != 0)) || (tr != (trunc[t] != 0));
         W.E.set_step(W.E.step() + 1);
         if (te || tr) {

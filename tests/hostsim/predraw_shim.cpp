@@ -3,8 +3,8 @@
 // The sliced lane is driven by the schedule the kernel's step loop gives it (pd_refill_step /
 // pd_consume_step by the step's parity, the load after them) and compared with the one-shot draw
 // of a reset (env_reset's loop, restated here on the same mt_batch / draw_orders) and with the
-// sequential generator of hostsim.cpp (mt_next_, bounded).  With PREDRAW_SHIM_MAIN it is a
-// stand-alone program that runs the sweep (the sanitizer build).
+// sequential generator of hostsim.cpp (mt_next_, bounded).  predraw_san_main.cpp runs the sweep
+// as a stand-alone program (the sanitizer build).
 #include "hostsim.cpp"
 
 #include <stdio.h>
@@ -200,26 +200,3 @@ void pd_sweep(const uint32_t* key, int pos, int g, int num_orders, int alternate
 }
 
 }  // extern "C"
-
-#ifdef PREDRAW_SHIM_MAIN
-int main() {
-    static const int NORD[] = {0, 1, 2, 5, 30, 64};
-    static const int CUR[][2] = {{0, 0}, {1, 4}, {3, 624}, {226, 228}, {227, 624}, {228, 232}, {396, 400}, {397, 400},
-                                 {620, 624}, {623, 624}, {600, 604}, {100, 624}};
-    uint32_t key[MT_N];
-    uint32_t x = 20240u;
-    for (int i = 0; i < MT_N; i++) { x = 1812433253u * (x ^ (x >> 30)) + (uint32_t)i; key[i] = x; }
-    advance(key, 0, MT_N);
-    long fails = 0, points = 0;
-    for (int no : NORD)
-        for (auto& cu : CUR)
-            for (int alt = 0; alt < 2; alt++) {
-                int64_t out[4];
-                pd_sweep(key, cu[0], cu[1], no, alt, 1, out);
-                fails += out[0];
-                points += out[3];
-            }
-    printf("predraw sweep: %ld failed checks, %ld interruption points\n", fails, points);
-    return fails != 0;
-}
-#endif

@@ -1,46 +1,11 @@
 // station_i8_shim.cpp — TEST-ONLY host build of fjsp_env.h's station_i8 (the stations' is_busy /
 // queue_length of a state, k_policy_step's KPI output obs_i8) for tests/test_station_i8_host.py:
 // random rollouts with auto-reset and a constructed state, both against what observe() hands its
-// sink's i8().
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-#define FJSP_DEV inline
-#include "../../multi-agent-rl-for-fjsp_amd/csrc/fjsp_env.h"
-using namespace fjsp;
+// sink's i8().  Its rollout is written out here and not replay.h's: there is one world, no second
+// schedule of the step, and the state is compared once more after every reset.
+#include "world.h"
 
 namespace {
-
-struct World {   // one env with its tables (stride 1)
-    Env E;
-    uint32_t orders[MAX_ORDERS];
-    uint16_t scode[MAX_SLOTS];
-    uint8_t snext[MAX_SLOTS];
-    uint16_t scstep[MAX_SLOTS];
-    Tables tabs() { return Tables{orders, scode, snext, scstep, 1}; }
-};
-
-Cfg make_cfg(const double* lut) {
-    Cfg C;
-    C.step_size = 10; C.max_steps = 200; C.tray_cap = 5; C.mask_tray_cap = 5; C.storage_cap = 100;
-    C.pool0 = 1000; C.pkg_cap = 20; C.ptk_small = 6; C.ptk_big = 12; C.ptk_pack = 3;
-    C.lut = lut;
-    return C;
-}
-
-struct Lcg {
-    uint64_t s;
-    uint32_t next(uint32_t n) { s = s * 6364136223846793005ull + 1442695040888963407ull; return (uint32_t)(s >> 33) % n; }
-};
-
-void reset_world(World& W, const Cfg& C, int num_orders, Lcg& g) {
-    env_clear(W.E, C);
-    W.E.set_norders(num_orders);
-    for (int o = 0; o < num_orders; o++) {
-        const int n = 1 + (int)g.next(9), ty = 1 + (int)g.next(3), co = 1 + (int)g.next(3);
-        W.orders[o] = ow_make(n, ty, co);
-    }
-}
 
 // what observe() hands i8(), as the sinks store it: (int8_t)v
 struct I8Sink {
@@ -79,13 +44,9 @@ extern "C" {
 // the reset, as the step kernels emit obs_i8) and after every reset.  out: states compared,
 // states with a difference, resets, then per field the states where it was non-zero.
 void station_i8_replay(int envs, int steps, int num_orders, uint64_t seed, int64_t* out) {
-    static double lut[RLUT_SIZE];
-    const double w[NW] = {100.0, 10.0, -0.1, 1.0, 5.0, -1.0, 2.0, -0.1, 10.0, -5.0, 5.0, 1.0, -2.0, 20.0, 2.0, -1.0};
-    build_reward_lut(w, 10, lut);
-    const Cfg C = make_cfg(lut);
+    const Cfg C = default_cfg();
     for (int i = 0; i < 3 + NI8; i++) out[i] = 0;
     int nonzero[NI8] = {0};
-    const int nact[NA] = {3, 8, 3, 3, 3, 3, 3, 3};
     for (int e = 0; e < envs; e++) {
         Lcg ga{seed * 1000003ull + (uint64_t)e}, gr{seed + 77ull * (uint64_t)e};
         World W;
@@ -94,17 +55,16 @@ void station_i8_replay(int envs, int steps, int num_orders, uint64_t seed, int64
         Tables T = W.tabs();
         for (int k = 0; k < steps; k++) {
             int act[NA];
-            for (int a = 0; a < NA; a++) act[a] = (int)ga.next((uint32_t)nact[a]);
+            draw_actions(ga, act);
             uint32_t res[NA];
             double rew[NA];
             env_step<true>(W.E, T, C, act, nullptr, res, rew);
             out[0]++;
             out[1] += compare(W.E, C, nonzero) != 0;
-            const int nord = W.E.norders();
-            const bool done = (W.E.ncompleted() == nord && nord > 0 && W.E.next_order() == nord) || W.E.step() >= C.max_steps;
+            const bool done = episode_over(W.E, C);
             W.E.set_step(W.E.step() + 1);
             if (done) {
-                reset_world(W, C, nord, gr);
+                reset_world(W, C, W.E.norders(), gr);
                 out[2]++;
                 out[0]++;
                 out[1] += compare(W.E, C, nonzero) != 0;
@@ -119,8 +79,7 @@ void station_i8_replay(int envs, int steps, int num_orders, uint64_t seed, int64
 // of station_i8 and of observe()'s i8(); status: the state's status word after station_i8 and after
 // observe() (which flags the overflow).
 void station_i8_case(int q0, int q1, int qp, int busy, int8_t* got, int8_t* want, uint32_t* status) {
-    static double lut[RLUT_SIZE];
-    const Cfg C = make_cfg(lut);
+    const Cfg C = default_cfg();
     Env E;
     env_clear(E, C);
     E.set_list(L_M0Q, 0, 0, q0);

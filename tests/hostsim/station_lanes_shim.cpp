@@ -3,50 +3,9 @@
 // tests/test_station_lanes_host.py.  The G lanes of an env run one after another here; the
 // reference is the S = 0..3 sequence K ran before (pack_due / pack_complete<0..3>, agv_pack_drop,
 // pack_execute / pack_finish<0..3>) on one Env.
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-#define FJSP_DEV inline
-#include "../../multi-agent-rl-for-fjsp_amd/csrc/fjsp_env.h"
-using namespace fjsp;
+#include "replay.h"
 
 namespace {
-
-struct World {   // one env with its tables (stride 1)
-    Env E;
-    uint32_t orders[MAX_ORDERS];
-    uint16_t scode[MAX_SLOTS];
-    uint8_t snext[MAX_SLOTS];
-    uint16_t scstep[MAX_SLOTS];
-    Tables tabs() { return Tables{orders, scode, snext, scstep, 1}; }
-};
-
-Cfg make_cfg(int pkg_cap, const double* lut) {
-    Cfg C;
-    C.step_size = 10; C.max_steps = 200; C.tray_cap = 5; C.mask_tray_cap = 5; C.storage_cap = 100;
-    C.pool0 = 1000; C.pkg_cap = pkg_cap; C.ptk_small = 6; C.ptk_big = 12; C.ptk_pack = 3;
-    C.lut = lut;
-    return C;
-}
-
-struct Lcg {
-    uint64_t s;
-    uint32_t next(uint32_t n) { s = s * 6364136223846793005ull + 1442695040888963407ull; return (uint32_t)(s >> 33) % n; }
-};
-
-void reset_world(World& W, const Cfg& C, int num_orders, Lcg& g) {
-    env_clear(W.E, C);
-    W.E.set_norders(num_orders);
-    for (int o = 0; o < num_orders; o++) {
-        const int n = 1 + (int)g.next(9), ty = 1 + (int)g.next(3), co = 1 + (int)g.next(3);
-        W.orders[o] = ow_make(n, ty, co);
-    }
-}
-
-bool same_tables(const World& A, const World& B) {
-    return memcmp(A.orders, B.orders, sizeof(A.orders)) == 0 && memcmp(A.scode, B.scode, sizeof(A.scode)) == 0 &&
-           memcmp(A.snext, B.snext, sizeof(A.snext)) == 0 && memcmp(A.scstep, B.scstep, sizeof(A.scstep)) == 0;
-}
 
 // events of one reference step (what the inputs contain, counted on the S = 0..3 sequence alone)
 struct Events {
@@ -167,10 +126,7 @@ bool both(const World& W, const Cfg& C, uint32_t a1, uint32_t pend, Events& ev) 
     Lanes<G> lanes;
     lanes.load(B.E);
     const KOut rb = lanes.step(B, C, a1, pend);
-    bool ok = lanes.store(B.E);
-    ok = ok && memcmp(A.E.w, B.E.w, sizeof(A.E.w)) == 0 && same_tables(A, B);
-    ok = ok && memcmp(ra.r, rb.r, sizeof(ra.r)) == 0 && ra.gs == rb.gs;
-    return ok;
+    return lanes.store(B.E) && same_world(A, B) && memcmp(ra.r, rb.r, sizeof(ra.r)) == 0 && ra.gs == rb.gs;
 }
 
 // constructed state of one station: 0 empty; 1 two runs queued; 2 a batch of two runs due now;
@@ -206,17 +162,15 @@ void build_station(World& W, const Cfg& C, int s, int state, int step) {
 }
 
 template <int G>
-void sweep_g(int64_t* out, char* msg, int msg_len, Events& ev) {
-    static double lut[RLUT_SIZE];
-    const Cfg C = make_cfg(6, lut);
+void sweep_g(int64_t* out, Mismatch& bad, Events& ev) {
+    Cfg C = default_cfg();
+    C.pkg_cap = 6;
     const int step = 17;
     for (int code = 0; code < NSTATES * NSTATES * NSTATES * NSTATES; code++)
     for (int acts = 0; acts < 81; acts++)
     for (int color = 0; color < 4; color++) {   // 0: no drop
         World W;
-        memset(&W, 0, sizeof(W));
-        memset(W.snext, 0x77, sizeof(W.snext));     // stale links: a missing store shows
-        memset(W.scstep, 0x55, sizeof(W.scstep));
+        poison_world(W);
         env_clear(W.E, C);
         W.E.set_norders(10);
         W.E.set_step(step);
@@ -242,9 +196,8 @@ void sweep_g(int64_t* out, char* msg, int msg_len, Events& ev) {
             pend = 1u | ((uint32_t)slot << 1) | ((uint32_t)tcode << 9) | ((uint32_t)color << 22);
         }
         out[0]++;
-        if (!both<G>(W, C, a1, pend, ev) && !out[1]++)
-            snprintf(msg, (size_t)msg_len, "G %d stations %d actions %d colour %d: the lane groups differ from the sequence",
-                     G, code, acts, color);
+        bad.check(both<G>(W, C, a1, pend, ev), "G %d stations %d actions %d colour %d: the lane groups differ from the sequence",
+                  G, code, acts, color);
     }
 }
 
@@ -254,82 +207,67 @@ void put_events(const Events& ev, int64_t* out) {
     out[6] = ev.drop_lost;
 }
 
+// S's step in K's schedule (the AGV's drop deferred to K), K's words on the lane groups between
+// the steps
 template <int G>
-void replay_g(int envs, int steps, int num_orders, int pkg_cap, uint64_t seed, int64_t* out, char* msg, int msg_len,
-              Events& ev) {
-    static double lut[RLUT_SIZE];
-    const double w[NW] = {100.0, 10.0, -0.1, 1.0, 5.0, -1.0, 2.0, -0.1, 10.0, -5.0, 5.0, 1.0, -2.0, 20.0, 2.0, -1.0};
-    build_reward_lut(w, 10, lut);
-    const Cfg C = make_cfg(pkg_cap, lut);
-    const int nact[NA] = {3, 8, 3, 3, 3, 3, 3, 3};
-    for (int e = 0; e < envs; e++) {
-        Lcg ga{seed * 1000003ull + (uint64_t)e}, gr_ref{seed + 77ull * (uint64_t)e}, gr_k = gr_ref;
-        // R: the plain step.  S: the step in K's schedule (the AGV's drop deferred to K), K's words
-        // on the lane groups between the steps.
-        World R, S;
-        memset(&R, 0, sizeof(R));
-        memset(&S, 0, sizeof(S));
-        reset_world(R, C, num_orders, gr_ref);
-        reset_world(S, C, num_orders, gr_k);
-        Tables TR = R.tabs(), TS = S.tabs();
-        Lanes<G> lanes;
-        lanes.load(S.E);
-        for (int k = 0; k < steps; k++) {
-            int act[NA];
-            for (int a = 0; a < NA; a++) act[a] = (int)ga.next((uint32_t)nact[a]);
-            uint32_t res_ref[NA];
-            double rew[NA];
-            const int tp0 = R.E.total_packaged(), nc0 = R.E.ncompleted();
-            env_step<true>(R.E, TR, C, act, nullptr, res_ref, rew);
-            // every other agent of the step on S (they leave K's words alone)
-            uint32_t res[NA], pend = 0;
-            int mv = 0, s0 = -1, s1 = -1;
-            res[0] = pickup_execute(S.E, TS, C, act[0]);
-            res[1] = agv_execute<true>(S.E, TS, C, act[1], &mv, &pend);
-            if (mv) S.E.set_loc(mv);
-            res[2] = machine_execute<0>(S.E, TS, act[2], &s0);
-            res[3] = machine_execute<1>(S.E, TS, act[3], &s1);
-            machines_run(S.E, TS, C, s0, s1);
-            const uint32_t a1 = (uint32_t)act[4] | ((uint32_t)act[5] << 8) | ((uint32_t)act[6] << 16) | ((uint32_t)act[7] << 24);
-            // K's step: the sequence on a copy (it counts the events and is compared too), the lanes on S
-            World Q = S;
-            bool ok = lanes.store(Q.E);
-            const KOut rq = k_step_ref(Q, C, a1, pend, ev);
-            const KOut rl = lanes.step(S, C, a1, pend);
-            ok = ok && lanes.store(S.E);
-            ok = ok && memcmp(Q.E.w, S.E.w, sizeof(Q.E.w)) == 0 && same_tables(Q, S);
-            ok = ok && memcmp(rq.r, rl.r, sizeof(rq.r)) == 0 && rq.gs == rl.gs;
-            // and against the plain step: state, results, the step's counts, the live tables
-            ok = ok && memcmp(R.E.w, S.E.w, sizeof(R.E.w)) == 0;
-            for (int a = 0; a < 4; a++) ok = ok && (res_ref[a] & 0xFFu) == (res[a] & 0xFFu);
-            for (int q = 0; q < 4; q++) ok = ok && rl.r[q] == ((res_ref[4 + q] & 0xFFu) | ((uint32_t)act[4 + q] << 8));
-            ok = ok && rl.gs == ((uint32_t)(R.E.ncompleted() - nc0) | ((uint32_t)(R.E.total_packaged() - tp0) << 16));
-            const int nslot = R.E.slot_next(), carry = R.E.carry();
-            ok = ok && memcmp(R.orders, S.orders, 4u * (size_t)num_orders) == 0 && memcmp(R.scode, S.scode, 2u * (size_t)nslot) == 0;
-            for (int s = 0; s < nslot; s++) ok = ok && (s == carry || R.snext[s] == S.snext[s]) && R.scstep[s] == S.scstep[s];
-            out[0]++;
-            if (!ok && !out[1]++)
-                snprintf(msg, (size_t)msg_len, "G %d env %d step %d (orders %d): the lane groups differ", G, e, k, num_orders);
-            const int nord = R.E.norders();
-            const bool done = (R.E.ncompleted() == nord && nord > 0 && R.E.next_order() == nord) || R.E.step() >= C.max_steps;
-            R.E.set_step(R.E.step() + 1);
-            S.E.set_step(S.E.step() + 1);
-            for (int g = 0; g < G; g++) lanes.L[g].set_step(lanes.L[g].step() + 1);
-            if (done) {
-                reset_world(R, C, nord, gr_ref);
-                reset_world(S, C, nord, gr_k);
-                // the wave's own reset of its lanes against a fresh load
-                Lanes<G> fresh;
-                fresh.load(S.E);
-                for (int g = 0; g < G; g++) {
-                    pack_lane_clear<G>(lanes.L[g]);
-                    if (memcmp(lanes.L[g].w, fresh.L[g].w, sizeof(fresh.L[g].w)) != 0 && !out[1]++)
-                        snprintf(msg, (size_t)msg_len, "G %d env %d step %d: reset of lane group %d", G, e, k, g);
-                }
-                out[2]++;
-            }
+struct KSchedule {
+    static constexpr int AHEAD = 0;
+    const Cfg& C;
+    Events& ev;
+    Lanes<G> lanes;
+
+    void begin(World& S) { lanes.load(S.E); }
+
+    bool step(Step& st, World& S) {
+        Tables TS = S.tabs();
+        const int* act = st.act;
+        // every other agent of the step on S (they leave K's words alone)
+        uint32_t res[NA], pend = 0;
+        int mv = 0, s0 = -1, s1 = -1;
+        res[0] = pickup_execute(S.E, TS, C, act[0]);
+        res[1] = agv_execute<true>(S.E, TS, C, act[1], &mv, &pend);
+        if (mv) S.E.set_loc(mv);
+        res[2] = machine_execute<0>(S.E, TS, act[2], &s0);
+        res[3] = machine_execute<1>(S.E, TS, act[3], &s1);
+        machines_run(S.E, TS, C, s0, s1);
+        const uint32_t a1 = (uint32_t)act[4] | ((uint32_t)act[5] << 8) | ((uint32_t)act[6] << 16) | ((uint32_t)act[7] << 24);
+        // K's step: the sequence on a copy (it counts the events and is compared too), the lanes on S
+        World Q = S;
+        bool ok = lanes.store(Q.E);
+        const KOut rq = k_step_ref(Q, C, a1, pend, ev);
+        const KOut rl = lanes.step(S, C, a1, pend);
+        ok = ok && lanes.store(S.E) && same_world(Q, S);
+        ok = ok && memcmp(rq.r, rl.r, sizeof(rq.r)) == 0 && rq.gs == rl.gs;
+        // and against the plain step: results and the step's counts (same_live has the rest)
+        for (int a = 0; a < 4; a++) ok = ok && (st.res_ref[a] & 0xFFu) == (res[a] & 0xFFu);
+        for (int q = 0; q < 4; q++) ok = ok && rl.r[q] == ((st.res_ref[4 + q] & 0xFFu) | ((uint32_t)act[4 + q] << 8));
+        const Env &R0 = st.R0.E, &R = st.R.E;
+        ok = ok && rl.gs == ((uint32_t)(R.ncompleted() - R0.ncompleted()) | ((uint32_t)(R.total_packaged() - R0.total_packaged()) << 16));
+        return ok;
+    }
+
+    void end_step(const Step& st, World& S, bool done, Mismatch& bad) {
+        for (int g = 0; g < G; g++) lanes.L[g].set_step(lanes.L[g].step() + 1);
+        if (!done) return;
+        // the wave's own reset of its lanes against a fresh load
+        Lanes<G> fresh;
+        fresh.load(S.E);
+        for (int g = 0; g < G; g++) {
+            pack_lane_clear<G>(lanes.L[g]);
+            bad.check(memcmp(lanes.L[g].w, fresh.L[g].w, sizeof(fresh.L[g].w)) == 0, "G %d env %d step %d: reset of lane group %d",
+                      G, st.env, st.k, g);
         }
     }
+};
+
+template <int G>
+Replayed replay_g(int envs, int steps, int num_orders, int pkg_cap, uint64_t seed, Mismatch& bad, Events& ev) {
+    Cfg C = default_cfg();
+    C.pkg_cap = pkg_cap;
+    KSchedule<G> m{C, ev};
+    char what[48];
+    snprintf(what, sizeof(what), "the lane groups differ (G %d)", G);
+    return replay(C, envs, steps, num_orders, seed, m, bad, what);
 }
 
 }  // namespace
@@ -341,27 +279,31 @@ extern "C" {
 // [two_stations, order_by_two, drop_to[0..3], drop_lost].  msg: the first mismatch.
 void lanes_sweep(int groups, int64_t* out, char* msg, int msg_len) {
     for (int i = 0; i < 9; i++) out[i] = 0;
-    msg[0] = 0;
+    Mismatch bad(out + 1, msg, msg_len);
     Events ev;
     memset(&ev, 0, sizeof(ev));
-    if (groups == 4) sweep_g<4>(out, msg, msg_len, ev);
-    else if (groups == 2) sweep_g<2>(out, msg, msg_len, ev);
-    else sweep_g<1>(out, msg, msg_len, ev);
+    if (groups == 4) sweep_g<4>(out, bad, ev);
+    else if (groups == 2) sweep_g<2>(out, bad, ev);
+    else sweep_g<1>(out, bad, ev);
     put_events(ev, out + 2);
 }
 
-// (b) `envs` envs x `steps` steps of uniform-random actions with auto-reset.  out: env-steps
-// compared, mismatches, resets, then the events as above.
+// (b) `envs` envs x `steps` steps of uniform-random actions with auto-reset, every env-step against
+// the sequence and against the plain step.  out: env-steps compared, mismatches, resets, then the
+// events as above.
 void lanes_replay(int groups, int envs, int steps, int num_orders, int pkg_cap, uint64_t seed, int64_t* out, char* msg,
                   int msg_len) {
     for (int i = 0; i < 10; i++) out[i] = 0;
-    msg[0] = 0;
+    Mismatch bad(out + 1, msg, msg_len);
     Events ev;
     memset(&ev, 0, sizeof(ev));
-    if (groups == 4) replay_g<4>(envs, steps, num_orders, pkg_cap, seed, out, msg, msg_len, ev);
-    else if (groups == 2) replay_g<2>(envs, steps, num_orders, pkg_cap, seed, out, msg, msg_len, ev);
-    else replay_g<1>(envs, steps, num_orders, pkg_cap, seed, out, msg, msg_len, ev);
+    const Replayed n = groups == 4   ? replay_g<4>(envs, steps, num_orders, pkg_cap, seed, bad, ev)
+                       : groups == 2 ? replay_g<2>(envs, steps, num_orders, pkg_cap, seed, bad, ev)
+                                     : replay_g<1>(envs, steps, num_orders, pkg_cap, seed, bad, ev);
+    out[0] = n.compared;
+    out[2] = n.resets;
     put_events(ev, out + 3);
 }
 
 }  // extern "C"
+

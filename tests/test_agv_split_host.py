@@ -7,21 +7,15 @@ left.  (a) sweeps a constructed product of actions, locations, carried trays, li
 caps and changes by the other agents; (b) replays random episodes in P's schedule against the
 plain step and counts how often agv_fin's two rare paths ran."""
 import ctypes
-import os
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SHIM = os.path.join(HERE, "hostsim", "agv_split_shim.cpp")
+from tests import hostsim_build as HB
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("agv_split") / "libagvsplit.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas",
-                    "-Wno-unused-function", "-o", so, SHIM], check=True)
-    lib = ctypes.CDLL(so)
+    lib = HB.build_shim(tmp_path_factory.mktemp("agv_split"), HB.source("agv_split_shim.cpp"), "agvsplit")
     I64P = ctypes.POINTER(ctypes.c_int64)
     lib.agv_sweep.restype = None
     lib.agv_sweep.argtypes = [I64P, ctypes.c_char_p, ctypes.c_int]

@@ -8,25 +8,19 @@ built from the reference's objects, row for row; the call must leave the state, 
 included, as it is.  On constructed states the code bits a SIGNAL and a drop leave behind must
 read as 0."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import hostsim_build as HB
 from tests import schedule_util as SU
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SHIM = os.path.join(HERE, "hostsim", "held_shim.cpp")
 HOLDS, BUSY = 1 << 13, 1 << 14
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("held") / "libheld.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas",
-                    "-Wno-unused-function", "-o", so, SHIM], check=True)
-    lib = ctypes.CDLL(so)
+    lib = HB.build_shim(tmp_path_factory.mktemp("held"), HB.source("held_shim.cpp"), "held")
     P = ctypes.c_void_p
     lib.held_replay.restype = None
     lib.held_replay.argtypes = [P, P, P, P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, P, ctypes.POINTER(ctypes.c_int64)]

@@ -3,27 +3,18 @@ by tests/hostsim, TEST-ONLY) against the oracle's event-heap restatement and the
 golden traces.  The GPU tests (test_gpu_parity.py) are the parity proof of the HIP path; this
 keeps the shared step logic covered in the CPU-only CI."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests import hostsim_build as HB
 from tests import parity_util as P
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SO = os.path.join(HERE, "hostsim", "libhostsim.so")
-SRC = [os.path.join(HERE, "hostsim", "hostsim.cpp"),
-       os.path.join(os.path.dirname(HERE), "multi-agent-rl-for-fjsp_amd", "csrc", "fjsp_env.h")]
 
 
 @pytest.fixture(scope="module")
-def L():
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                        "-o", SO, SRC[0]], check=True)
-    lib = ctypes.CDLL(SO)
+def L(tmp_path_factory):
+    lib = HB.build_shim(tmp_path_factory.mktemp("hostsim"), HB.source("hostsim.cpp"), "hostsim")
     Pt = ctypes.c_void_p
     lib.hs_create.restype = Pt
     lib.hs_create.argtypes = [Pt, ctypes.c_int]

@@ -9,21 +9,15 @@ machines_run<true> on one Env does; 1 group is that sequence with the queue fron
 known ahead against the plain one.  The shim counts, on the sequence alone, what the inputs
 contain: a pass on nothing fails."""
 import ctypes
-import os
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SHIM = os.path.join(HERE, "hostsim", "machine_lanes_shim.cpp")
+from tests import hostsim_build as HB
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("machine_lanes") / "libmachinelanes.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas",
-                    "-Wno-unused-function", "-o", so, SHIM], check=True)
-    lib = ctypes.CDLL(so)
+    lib = HB.build_shim(tmp_path_factory.mktemp("machine_lanes"), HB.source("machine_lanes_shim.cpp"), "machinelanes")
     I64P = ctypes.POINTER(ctypes.c_int64)
     lib.mlanes_sweep.restype = None
     lib.mlanes_sweep.argtypes = [ctypes.c_int, I64P, ctypes.c_char_p, ctypes.c_int]

@@ -15,12 +15,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import hostsim_build as HB
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-SHIM = os.path.join(HERE, "hostsim", "orders_shim.cpp")
-SAN_MAIN = os.path.join(HERE, "hostsim", "orders_san_main.cpp")
 GOLD = os.path.join(HERE, "golden", "orders.npz")
 RUNS = ["one", "nine", "full", "one_heur", "arrivals"]
-GXX = ["g++", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function"]
 P = ctypes.c_void_p
 
 
@@ -39,9 +38,7 @@ def word(n, ty, co):
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("orders") / "liborders.so")
-    subprocess.run(GXX + ["-O2", "-fPIC", "-shared", "-o", so, SHIM], check=True)
-    lib = ctypes.CDLL(so)
+    lib = HB.build_shim(tmp_path_factory.mktemp("orders"), HB.source("orders_shim.cpp"), "orders")
     lib.orders_replay.restype = None
     lib.orders_replay.argtypes = [ctypes.POINTER(OrdersRun)]
     lib.orders_world_bytes.restype = ctypes.c_int
@@ -201,9 +198,7 @@ def test_a_reset_keeps_the_cursor_and_clears_the_rest(shim):
 
 
 def test_sanitized_standalone_run(tmp_path):
-    exe = str(tmp_path / "orders_san")
-    subprocess.run(GXX + ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, SAN_MAIN],
-                   check=True)
+    exe = HB.build_program(tmp_path, [HB.source("orders_san_main.cpp")], sanitize=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert r.stdout.strip().endswith("OK")

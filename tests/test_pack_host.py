@@ -8,25 +8,19 @@ before the reset must equal the words the fixture built from the reference's obj
 row; the call must leave the state as it is; every row's sum of the four `completed` fields is the
 recorded total_products_packaged."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import hostsim_build as HB
 from tests import packaging_util as PU
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SHIM = os.path.join(HERE, "hostsim", "pack_shim.cpp")
 ST_DIVERGED, ST_PKG_WAIT, ST_PROD_LOST = 0x1, 0x4, 0x10
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("pack") / "libpack.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas",
-                    "-Wno-unused-function", "-o", so, SHIM], check=True)
-    lib = ctypes.CDLL(so)
+    lib = HB.build_shim(tmp_path_factory.mktemp("pack"), HB.source("pack_shim.cpp"), "pack")
     P = ctypes.c_void_p
     lib.pack_replay.restype = None
     lib.pack_replay.argtypes = [P, P, P, P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P, P,

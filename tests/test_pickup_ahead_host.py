@@ -7,21 +7,15 @@ left; on a sensitive lane the pickup run again on those words must.  (a) sweeps 
 product; (b) replays random episodes in the kernel's schedule against the plain step and counts how
 often the AGV's pop met a pickup run ahead of it."""
 import ctypes
-import os
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SHIM = os.path.join(HERE, "hostsim", "pickup_ahead_shim.cpp")
+from tests import hostsim_build as HB
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("pickup_ahead") / "libpickupahead.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas",
-                    "-Wno-unused-function", "-o", so, SHIM], check=True)
-    lib = ctypes.CDLL(so)
+    lib = HB.build_shim(tmp_path_factory.mktemp("pickup_ahead"), HB.source("pickup_ahead_shim.cpp"), "pickupahead")
     I64P = ctypes.POINTER(ctypes.c_int64)
     lib.pickup_sweep.restype = None
     lib.pickup_sweep.argtypes = [I64P, ctypes.c_char_p, ctypes.c_int]

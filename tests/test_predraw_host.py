@@ -15,15 +15,12 @@ equal word for word.  A reset regenerates 32 words per batch, so its g runs ahea
 the same block: pos is equal, and the rows are equal once the words between the two g are
 regenerated; against the sequential generator the block is completed the same way."""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SHIM = os.path.join(HERE, "hostsim", "predraw_shim.cpp")
-CXX = ["g++", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function"]
+from tests import hostsim_build as HB
 
 NUM_ORDERS = [0, 1, 2, 5, 30, 64]
 # (pos, g) of the live row: words [0, g) are current, pos <= g, g a multiple of 4 as every refill
@@ -40,9 +37,7 @@ READY_BY = {30: 128, 64: 190}   # steps from the episode's start within which th
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("predraw") / "libpredraw.so")
-    subprocess.run(CXX + ["-O2", "-fPIC", "-shared", "-o", so, SHIM], check=True)
-    lib = ctypes.CDLL(so)
+    lib = HB.build_shim(tmp_path_factory.mktemp("predraw"), HB.source("predraw_shim.cpp"), "predraw")
     lib.pd_sweep.restype = None
     lib.pd_sweep.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int64)]
     return lib
@@ -91,9 +86,7 @@ def test_table_ready_in_time(shim, epw, num_orders):
 
 def test_sweep_under_sanitizers(tmp_path):
     """The same sweep as a stand-alone program under ASan + UBSan (nothing loaded into Python)."""
-    exe = str(tmp_path / "predraw_san")
-    subprocess.run(CXX + ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DPREDRAW_SHIM_MAIN",
-                          "-o", exe, SHIM], check=True)
+    exe = HB.build_program(tmp_path, [HB.source("predraw_san_main.cpp")], sanitize=True)
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert " 0 failed checks" in r.stdout

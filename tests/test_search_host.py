@@ -8,18 +8,14 @@ the same loop driven through OracleEnv.step in trace, stop step, flags, infos an
 same shim is built once more with a stand-alone main under -fsanitize=address,undefined and run."""
 import ctypes
 import importlib
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests import hostsim_build as HB
 from tests import search_ref as R
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SHIM = os.path.join(HERE, "hostsim", "search_shim.cpp")
-SAN_MAIN = os.path.join(HERE, "hostsim", "search_san_main.cpp")
-GXX = ["g++", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function"]
 P, I32, U32, U64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64
 SEED = 0x5EED5EED12345
 CASES = [(3, 2), (7, 5), (11, 30), (5, 64), (0, 2), (9, 5), (2, 30), (4, 9)]    # (seed, num_orders) per env
@@ -27,9 +23,7 @@ CASES = [(3, 2), (7, 5), (11, 30), (5, 64), (0, 2), (9, 5), (2, 30), (4, 9)]    
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("search") / "libsearch.so")
-    subprocess.run(GXX + ["-O2", "-fPIC", "-shared", "-o", so, SHIM], check=True)
-    lib = ctypes.CDLL(so)
+    lib = HB.build_shim(tmp_path_factory.mktemp("search"), HB.source("search_shim.cpp"), "search")
     lib.search_world_bytes.restype = ctypes.c_int
     lib.search_world_reset.restype = ctypes.c_int
     lib.search_world_reset.argtypes = [P, P, ctypes.c_int]
@@ -187,9 +181,7 @@ def test_a_k_that_ends_before_the_episode(shim):
 
 
 def test_sanitized_standalone_run(tmp_path):
-    exe = str(tmp_path / "search_san")
-    subprocess.run(GXX + ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, SAN_MAIN],
-                   check=True)
+    exe = HB.build_program(tmp_path, [HB.source("search_san_main.cpp")], sanitize=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert r.stdout.strip().endswith("OK")

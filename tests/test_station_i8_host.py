@@ -6,22 +6,16 @@ Its twelve values must be what observe() hands its sink's i8(), truncated to int
 store them, on every state a rollout with auto-reset visits and on a constructed state whose queue
 words are above 127; and it must leave the state, its status word included, as it is."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SHIM = os.path.join(HERE, "hostsim", "station_i8_shim.cpp")
+from tests import hostsim_build as HB
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("station_i8") / "libstationi8.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas",
-                    "-Wno-unused-function", "-o", so, SHIM], check=True)
-    lib = ctypes.CDLL(so)
+    lib = HB.build_shim(tmp_path_factory.mktemp("station_i8"), HB.source("station_i8_shim.cpp"), "stationi8")
     lib.station_i8_replay.restype = None
     lib.station_i8_replay.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
                                       ctypes.POINTER(ctypes.c_int64)]

@@ -10,22 +10,17 @@ on a constructed product of station states, actions and drops, (b) in a replay o
 which is also compared with the plain step.  The shim counts on the sequence alone what the inputs
 contain, so a pass on nothing fails."""
 import ctypes
-import os
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SHIM = os.path.join(HERE, "hostsim", "station_lanes_shim.cpp")
+from tests import hostsim_build as HB
+
 GROUPS = [4, 2, 1]   # 16, 32, 64 envs per workgroup
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("station_lanes") / "libstationlanes.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas",
-                    "-Wno-unused-function", "-o", so, SHIM], check=True)
-    lib = ctypes.CDLL(so)
+    lib = HB.build_shim(tmp_path_factory.mktemp("station_lanes"), HB.source("station_lanes_shim.cpp"), "stationlanes")
     I64P = ctypes.POINTER(ctypes.c_int64)
     lib.lanes_sweep.restype = None
     lib.lanes_sweep.argtypes = [ctypes.c_int, I64P, ctypes.c_char_p, ctypes.c_int]

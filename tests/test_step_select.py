@@ -4,13 +4,10 @@ choice, row by row.  The plan's name is what fjsp_last_kernel reports and its va
 the launch switches on, so the GPU tests that pin a path by name rest on these rules."""
 import ctypes
 import itertools
-import os
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SHIM = os.path.join(HERE, "hostsim", "select_shim.cpp")
+from tests import hostsim_build as HB
 
 UNMASKED, MASKED, HEURISTIC = 0, 1, 2   # FJSP_ACTIONS_*
 MANY, PIPE, AG = 0, 1, 2                # StepFamily
@@ -25,10 +22,7 @@ NAMES = {"k_step_many", "k_step_many<lds>", "k_step_many<full>", "k_step_many<ld
 
 @pytest.fixture(scope="module")
 def select(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("select") / "libselect.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function",
-                    "-o", so, SHIM], check=True)
-    lib = ctypes.CDLL(so)
+    lib = HB.build_shim(tmp_path_factory.mktemp("select"), HB.source("select_shim.cpp"), "select")
     lib.sel_step_many.restype = ctypes.c_char_p
     lib.sel_step_many.argtypes = [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)] * 2
 
