@@ -746,7 +746,7 @@ class _GatherRuns(torch.autograd.Function):
 
 def _run_sums(g, gy):
     """gy [R, C, S] per sample -> [R, C, Umax] per group of the RowGroups g: runs of the sorted
-    order summed (on the GPU: fjsp_a2c_run_sums, f64 sums in sorted order; else an f64 prefix sum
+    order summed (on the GPU: fjsp_a2c_run_sums, each run's own f64 sum in sorted order; else an f64 prefix sum
     differenced at the run ends)."""
     R, C, S = gy.shape
     if g.gsorted is not None:

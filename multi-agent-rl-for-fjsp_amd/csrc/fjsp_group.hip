@@ -99,14 +99,24 @@ __global__ void __launch_bounds__(256) k_group_rep(const int64_t* __restrict__ i
 // vals[j][perm[a][pos]] (* scale[j], in f32, as the gradient is scaled before the sum), summed in
 // f64, stored as f32.  The backward of a per-group gather (each group's samples' gradients
 // summed: a2c_vec._GatherRuns, _ActorHead): deterministic, one pass over the values.
-// k_run_chunks: a workgroup takes RS_CH sorted positions of one row, forms their f64 prefix sums
-// (per thread 4, then a block scan of the thread totals in a fixed order), and each run of one
-// group inside the chunk is the difference of the prefixes at its two ends (the group ids of a
-// row's sorted positions rise by one per run, so run k of the chunk is group g0 + k).  A run that
-// crosses a chunk end leaves its chunk part (cont / first_part, last_part / last_g); k_run_carry
-// adds those over chunks with the same construction one level up (prefix sums and a prefix max
-// of the run-start chunks, one workgroup per row).
+// k_run_chunks: a workgroup takes RS_CH sorted positions of one row and forms their SEGMENTED f64
+// prefix sums, restarting at every run start (per thread 4, then a block scan of the thread totals
+// in a fixed order): the value at a run's last position is that run's own sum, so a run's error
+// is 2^-53 of its own terms whatever its neighbours hold (the difference of two plain prefix sums
+// lost 2^-53 of the chunk's prefix: one gradient of 1e29 in a row cost every other group of the
+// chunk 1e13).  The group ids of a row's sorted positions rise by one per run, so run k of the
+// chunk is group g0 + k.  A run that crosses a chunk end leaves its chunk part (cont / first_part,
+// last_part / last_g); k_run_carry adds those over chunks with the same construction one level
+// up (a segmented scan that restarts where a crossing run starts, and a prefix max of those
+// chunks, one workgroup per row).
 constexpr int RS_CH = 1024, RS_T = 256;
+
+// a segmented sum: v = the sum since the last segment start, f = a start lies inside
+struct SegSum {
+    double v;
+    int f;
+};
+__device__ __forceinline__ SegSum seg_add(SegSum x, SegSum y) { return SegSum{y.f ? y.v : x.v + y.v, x.f | y.f}; }
 
 // inclusive scan of v over the RS_T threads of a workgroup (Kogge-Stone, fixed order); sc: LDS
 template <class T, class Op>
@@ -131,8 +141,8 @@ __global__ void __launch_bounds__(RS_T) k_run_chunks(const float* __restrict__ v
                                                    int64_t nch, float* __restrict__ out, double* __restrict__ first_part,
                                                    uint8_t* __restrict__ cont, double* __restrict__ last_part,
                                                    int32_t* __restrict__ last_g) {
-    __shared__ double s_sc[RS_T];
-    __shared__ double s_lo[RS_CH], s_hi[RS_CH];   // per run k: the prefix before its first / at its last position
+    __shared__ SegSum s_sc[RS_T];
+    __shared__ double s_hi[RS_CH];   // per run k: the segmented prefix at its last position = its sum in the chunk
     const int64_t c = blockIdx.x;
     const int j = (int)blockIdx.y, t = (int)threadIdx.x;
     const int64_t a = rowmap[j];
@@ -143,24 +153,27 @@ __global__ void __launch_bounds__(RS_T) k_run_chunks(const float* __restrict__ v
     const float* vr = vals + (int64_t)j * S;
     int32_t g[4];
     double pre[4];
-    double acc = 0.0;
+    int started[4];   // a run starts at or before position i of this thread's four (the chunk's first position counts)
+    SegSum acc{0.0, 0};
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const int64_t p = pos0 + 4 * t + i;
         g[i] = p < pend ? gs[p] : -1;
-        acc += p < pend ? (double)(vr[pm[p]] * sc) : 0.0;
-        pre[i] = acc;
+        const double x = p < pend ? (double)(vr[pm[p]] * sc) : 0.0;
+        const bool start = p < pend && (p == pos0 || gs[p - 1] != g[i]);
+        acc = start ? SegSum{x, 1} : SegSum{acc.v + x, acc.f};
+        pre[i] = acc.v;
+        started[i] = acc.f;
     }
-    const double incl = block_scan(acc, s_sc, [](double x, double y) { return x + y; });
-    const double off = incl - acc;   // the prefix before this thread's positions
+    // s_sc: the inclusive segmented sums of the thread totals
+    (void)block_scan(acc, s_sc, [](SegSum x, SegSum y) { return seg_add(x, y); });
+    const double off = t > 0 ? s_sc[t - 1].v : 0.0;   // the open run's sum before this thread's positions
     const int32_t g0 = gs[pos0];
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const int64_t p = pos0 + 4 * t + i;
         if (p >= pend) break;
-        const int k = g[i] - g0;
-        if (p == pos0 || gs[p - 1] != g[i]) s_lo[k] = i == 0 ? off : off + pre[i - 1];
-        if (p + 1 == pend || gs[p + 1] != g[i]) s_hi[k] = off + pre[i];
+        if (p + 1 == pend || gs[p + 1] != g[i]) s_hi[g[i] - g0] = started[i] ? pre[i] : off + pre[i];
     }
     __syncthreads();
     const int32_t glast = gs[pend - 1];
@@ -169,7 +182,7 @@ __global__ void __launch_bounds__(RS_T) k_run_chunks(const float* __restrict__ v
     const int32_t next_g = pend < S ? gs[pend] : -2;
     const int64_t jc = (int64_t)j * nch + c;
     for (int k = t; k < m; k += RS_T) {
-        const double sum = s_hi[k] - s_lo[k];
+        const double sum = s_hi[k];
         const bool from_prev = k == 0 && prev_g == g0, into_next = k == m - 1 && next_g == glast;
         if (from_prev) {
             first_part[jc] = sum;
@@ -183,54 +196,58 @@ __global__ void __launch_bounds__(RS_T) k_run_chunks(const float* __restrict__ v
     }
 }
 
-// Per row (one workgroup): over its chunks, Q = inclusive prefix sums of the continuation parts
-// (first_part where cont != 0) and M = the last chunk <= c where a crossing run starts; a chunk e
-// whose first run ends there (cont == 1) completes the run that started in chunk M[e - 1]:
-// last_part[M] + Q[e] - Q[M].  Q is kept in qbuf [J][nch] for the lookups.
+// Per row (one workgroup): over its chunks, a segmented sum that restarts with last_part[c] in every
+// chunk c where a crossing run starts (after that chunk's own continuation part) and adds the
+// continuation parts (first_part where cont != 0), and M = the last chunk <= c where a crossing run
+// starts; a chunk e whose first run ends there (cont == 1) completes the run that started in chunk
+// M[e - 1]: its sum is the segmented sum through e's continuation part, last_part[M] +
+// first_part[M + 1] + .. + first_part[e], with no other run's parts in it.  (qbuf is unused.)
 __global__ void __launch_bounds__(RS_T) k_run_carry(int64_t nch, int64_t umax, const double* __restrict__ first_part,
                                                   const uint8_t* __restrict__ cont, const double* __restrict__ last_part,
                                                   const int32_t* __restrict__ last_g, double* __restrict__ qbuf,
                                                   float* __restrict__ out) {
-    __shared__ double s_sc[RS_T];
+    __shared__ SegSum s_sc[RS_T];
     __shared__ int64_t s_mx[RS_T];
     const int64_t j = blockIdx.x, base = j * nch;
     const int t = (int)threadIdx.x;
-    double qcarry = 0.0;
+    SegSum qcarry{0.0, 0};
     int64_t mcarry = -1;
     for (int64_t c0 = 0; c0 < nch; c0 += RS_CH) {
-        double q[4], acc = 0.0;
+        double q[4];
+        int qs[4];   // a crossing run started in this thread's chunks before chunk i's continuation part
+        SegSum acc{0.0, 0};
         int64_t mx[4], m = -1;
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const int64_t c = c0 + 4 * t + i;
             const bool in = c < nch;
-            acc += in && cont[base + c] ? first_part[base + c] : 0.0;
-            q[i] = acc;
-            if (in && last_g[base + c] >= 0) m = c;
+            acc.v += in && cont[base + c] ? first_part[base + c] : 0.0;
+            q[i] = acc.v;
+            qs[i] = acc.f;
+            if (in && last_g[base + c] >= 0) {
+                m = c;
+                acc = SegSum{last_part[base + c], 1};
+            }
             mx[i] = m;
         }
-        const double qi = block_scan(acc, s_sc, [](double x, double y) { return x + y; });
+        // s_sc: the inclusive segmented sums of the thread totals
+        (void)block_scan(acc, s_sc, [](SegSum x, SegSum y) { return seg_add(x, y); });
         (void)block_scan(m, s_mx, [](int64_t x, int64_t y) { return x > y ? x : y; });   // s_mx: inclusive maxima
-        const double qoff = qcarry + (qi - acc);
+        // the open run's sum before this thread's chunks: the tiles before, then the threads before
+        const double qoff = t > 0 ? seg_add(qcarry, s_sc[t - 1]).v : qcarry.v;
         // the running max before this thread: the inclusive max of the thread before it
         const int64_t mprev_t = t > 0 ? s_mx[t - 1] : -1;
         const int64_t moff = mprev_t > mcarry ? mprev_t : mcarry;
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const int64_t c = c0 + 4 * t + i;
-            if (c < nch) qbuf[base + c] = qoff + q[i];
-        }
-        __syncthreads();   // this tile's Q is visible to the workgroup
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int64_t c = c0 + 4 * t + i;
             if (c >= nch || cont[base + c] != 1) continue;
             int64_t st = i == 0 ? moff : (mx[i - 1] > moff ? mx[i - 1] : moff);   // last start chunk < c
             if (st < 0) continue;   // cannot happen: a continued run started in an earlier chunk
-            const double s = last_part[base + st] + (qoff + q[i]) - qbuf[base + st];
+            const double s = qs[i] ? q[i] : qoff + q[i];
             if (last_g[base + st] < umax) out[j * umax + last_g[base + st]] = (float)s;
         }
-        qcarry += s_sc[RS_T - 1];
+        qcarry = seg_add(qcarry, s_sc[RS_T - 1]);
         mcarry = s_mx[RS_T - 1] > mcarry ? s_mx[RS_T - 1] : mcarry;
         __syncthreads();
     }

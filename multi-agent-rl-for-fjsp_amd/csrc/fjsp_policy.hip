@@ -1704,6 +1704,11 @@ __global__ void __launch_bounds__(256) k_shard_keys(const uint64_t* __restrict__
 // under the float mask m and the taken action act, and g[j] = dL / dp_j for a loss whose entropy
 // term is es * entropy (es = -c / count, times the record's sample count in k_record_head) and
 // whose policy term has the gradient dlogp(logp) = dL / dlogp.
+// The renormalisation's backward, d(p m / sr) / dp, is g[j] += m[j] != 0 ? m[j] ((gpm[j] - dot / sr) / sr)
+// : 0 with gpm = dL / dpm and dot = sum gpm p m: two divisions by sr and no sr * sr, which
+// underflows to 0 once the valid actions' mass is below 2^-75 (dot, analytically 0, is rounding
+// noise: noise / 0 made the whole update NaN), and a select, not m[j] * (...), so that a masked
+// action gets 0 even where gpm / sr overflows (tests/test_gpu_actor_heads.py, E7 / E8).
 template <class DLogp>
 __device__ __forceinline__ void head_core(const float (&p)[8], const float (&m)[8], int act, float es, DLogp dlogp,
                                           float (&g)[8], float& ent, float& logp) {
@@ -1742,7 +1747,7 @@ __device__ __forceinline__ void head_core(const float (&p)[8], const float (&m)[
             dot += gpm[j] * (p[j] * m[j]);
         }
 #pragma unroll
-        for (int j = 0; j < 8; j++) g[j] += m[j] * (gpm[j] / sr - dot / (sr * sr));
+        for (int j = 0; j < 8; j++) g[j] += m[j] != 0.0f ? m[j] * ((gpm[j] - dot / sr) / sr) : 0.0f;
     }
 }
 
