@@ -160,6 +160,41 @@ constexpr int NWORDS = 40;   // rows of the HBM state buffer (30 used)
 //   W24/25 completed[0..3] (16 bits each)                W26+s queue length at the last START
 constexpr int NSTATE = 30;
 
+// W0, W1 and W5 at word level: for a site that holds the word without an Env (a posted copy, a
+// host read-back).  Env's accessors below call them.
+constexpr int W0_STEP_BITS = 16, W0_NORD_SH = 16, W0_NORD_BITS = 8, W0_NEXT_SH = 24, W0_NEXT_BITS = 8;
+constexpr uint32_t W0_STEP_MASK = 0xFFFFu, W0_NORD_MASK = 0xFFu, W0_BELOW_NEXT = 0x00FFFFFFu;
+constexpr int W1_NCOMP_BITS = 8, W1_PACKAGED_SH = 8;
+constexpr uint32_t W1_NCOMP_MASK = 0xFFu;
+constexpr int W5_SLOT_SH = 24, W5_SLOT_BITS = 8;
+FJSP_HD constexpr int w0_step(uint32_t w0) { return (int)(w0 & W0_STEP_MASK); }
+FJSP_HD constexpr int w0_norders(uint32_t w0) { return (int)((w0 >> W0_NORD_SH) & W0_NORD_MASK); }
+FJSP_HD constexpr int w0_next_order(uint32_t w0) { return (int)(w0 >> W0_NEXT_SH); }
+// next_order replaced; bits of `no` above the field fall off the word
+FJSP_HD constexpr uint32_t w0_with_next_order(uint32_t w0, uint32_t no) { return (w0 & W0_BELOW_NEXT) | (no << W0_NEXT_SH); }
+FJSP_HD constexpr int w1_ncompleted(uint32_t w1) { return (int)(w1 & W1_NCOMP_MASK); }
+FJSP_HD constexpr int w1_total_packaged(uint32_t w1) { return (int)(w1 >> W1_PACKAGED_SH); }
+FJSP_HD constexpr int w5_slot_next(uint32_t w5) { return (int)(w5 >> W5_SLOT_SH); }
+static_assert(W0_STEP_MASK == (1u << W0_STEP_BITS) - 1u && W0_NORD_MASK == (1u << W0_NORD_BITS) - 1u &&
+                  W0_NORD_SH == W0_STEP_BITS && W0_NEXT_SH == W0_NORD_SH + W0_NORD_BITS && W0_NEXT_SH + W0_NEXT_BITS == 32 &&
+                  W0_BELOW_NEXT == (1u << W0_NEXT_SH) - 1u,
+              "W0's fields tile the word");
+static_assert(W1_NCOMP_MASK == (1u << W1_NCOMP_BITS) - 1u && W1_PACKAGED_SH == W1_NCOMP_BITS && W5_SLOT_SH + W5_SLOT_BITS == 32,
+              "W1's and W5's fields");
+static_assert(MAX_ORDERS <= (int)W0_NORD_MASK && MAX_ORDERS <= (int)W1_NCOMP_MASK && MAX_SLOTS < (1 << W5_SLOT_BITS),
+              "MAX_ORDERS fits norders, next_order and ncompleted; the slot index fits slot_next");
+static_assert(w0_step(0xFFFFu) == 0xFFFF && w0_step(0xFFFF0000u) == 0 && w0_norders(0x00FF0000u) == 0xFF &&
+                  w0_norders(0xFF00FFFFu) == 0 && w0_next_order(0xFF000000u) == 0xFF && w0_next_order(0x00FFFFFFu) == 0 &&
+                  w0_next_order(w0_with_next_order(0x12345678u, 0xFFu)) == 0xFF &&
+                  w0_next_order(w0_with_next_order(0xFFFFFFFFu, 0u)) == 0 && w1_ncompleted(0xFFu) == 0xFF &&
+                  w1_ncompleted(0xFFFFFF00u) == 0 && w1_total_packaged(0xFFFFFF00u) == 0xFFFFFF && w5_slot_next(0xFF000000u) == 0xFF,
+              "decoders at the fields' extremes");
+static_assert(w0_step(0xA1B2C3D4u) == (int)(0xA1B2C3D4u & 0xFFFFu) && w0_norders(0xA1B2C3D4u) == (int)((0xA1B2C3D4u >> 16) & 0xFFu) &&
+                  w0_next_order(0xA1B2C3D4u) == (int)(0xA1B2C3D4u >> 24) &&
+                  w0_with_next_order(0xA1B2C3D4u, 0x107u) == ((0xA1B2C3D4u & 0x00FFFFFFu) | (0x107u << 24)) &&
+                  w1_ncompleted(0xA1B2C3D4u) == (int)(0xA1B2C3D4u & 0xFFu) && w5_slot_next(0xA1B2C3D4u) == (int)(0xA1B2C3D4u >> 24),
+              "the decoders equal the hand-spelled expressions they replace");
+
 struct Env {
     uint32_t w[NSTATE];
     FJSP_DIAG(uint64_t st_acc[8], st_t0;)
@@ -169,16 +204,16 @@ struct Env {
         w[i] = (w[i] & ~m) | ((v << o) & m);
     }
     // episode
-    FJSP_DEV int step() const { return bf(0, 0, 16); }
-    FJSP_DEV void set_step(int v) { sbf(0, 0, 16, v); }
-    FJSP_DEV int norders() const { return bf(0, 16, 8); }
-    FJSP_DEV void set_norders(int v) { sbf(0, 16, 8, v); }
-    FJSP_DEV int next_order() const { return w[0] >> 24; }
-    FJSP_DEV void set_next_order(int v) { sbf(0, 24, 8, v); }
-    FJSP_DEV int ncompleted() const { return bf(1, 0, 8); }
-    FJSP_DEV void set_ncompleted(int v) { sbf(1, 0, 8, v); }
-    FJSP_DEV int total_packaged() const { return w[1] >> 8; }
-    FJSP_DEV void set_total_packaged(int v) { sbf(1, 8, 24, v); }
+    FJSP_DEV int step() const { return w0_step(w[0]); }
+    FJSP_DEV void set_step(int v) { sbf(0, 0, W0_STEP_BITS, v); }
+    FJSP_DEV int norders() const { return w0_norders(w[0]); }
+    FJSP_DEV void set_norders(int v) { sbf(0, W0_NORD_SH, W0_NORD_BITS, v); }
+    FJSP_DEV int next_order() const { return w0_next_order(w[0]); }
+    FJSP_DEV void set_next_order(int v) { sbf(0, W0_NEXT_SH, W0_NEXT_BITS, v); }
+    FJSP_DEV int ncompleted() const { return w1_ncompleted(w[1]); }
+    FJSP_DEV void set_ncompleted(int v) { sbf(1, 0, W1_NCOMP_BITS, v); }
+    FJSP_DEV int total_packaged() const { return w1_total_packaged(w[1]); }
+    FJSP_DEV void set_total_packaged(int v) { sbf(1, W1_PACKAGED_SH, 32 - W1_PACKAGED_SH, v); }
     FJSP_DEV uint32_t status() const { return w[2]; }
     FJSP_DEV void flag(uint32_t b) { w[2] |= b; }
     FJSP_DEV int mti() const { return (int)w[3]; }
@@ -204,8 +239,8 @@ struct Env {
     FJSP_DEV void set_tray_order(int v) { sbf(5, 0, 8, v); }
     FJSP_DEV int pool() const { return bf(5, 8, 16); }
     FJSP_DEV void set_pool(int v) { sbf(5, 8, 16, v); }
-    FJSP_DEV int slot_next() const { return w[5] >> 24; }
-    FJSP_DEV void set_slot_next(int v) { sbf(5, 24, 8, v); }
+    FJSP_DEV int slot_next() const { return w5_slot_next(w[5]); }
+    FJSP_DEV void set_slot_next(int v) { sbf(5, W5_SLOT_SH, W5_SLOT_BITS, v); }
     // AGV (AGVAgent.py:41-45): location, carried tray slot (NIL = none), cached tray facts
     FJSP_DEV int loc() const { return bf(6, 0, 3); }
     FJSP_DEV void set_loc(int v) { sbf(6, 0, 3, v); }
@@ -258,6 +293,29 @@ struct Env {
     // is derived from it (pack_progress), so the step itself never computes it
     FJSP_DEV int p_startn(int s) const { return (int)w[26 + s]; }
 };
+
+// The episode-end rule of FJSPSimulation.step (FJSPSimulation.py:225-231), read before the step
+// counter moves: terminated = every order completed and none left to start; truncated = the step
+// counter at max_steps.  The raw form takes W0 and the completed count from wherever a wave holds
+// them (k_step_ag: AM's posted W0, K's posted W1).
+FJSP_HD constexpr bool all_orders_done(uint32_t w0, uint32_t w1) {
+    const int nord = w0_norders(w0);
+    return w1_ncompleted(w1) == nord && nord > 0 && w0_next_order(w0) == nord;
+}
+FJSP_HD constexpr bool step_truncated(int step, int max_steps) { return step >= max_steps; }
+struct EpisodeEnd {
+    int all_done, truncated;
+};
+FJSP_DEV EpisodeEnd episode_end(const Env& E, const Cfg& C) {
+    const int nord = E.norders();
+    const int all_done = E.ncompleted() == nord && nord > 0 && E.next_order() == nord;   // all_orders_done(W0, W1)
+    const int truncated = E.step() >= C.max_steps;
+    return EpisodeEnd{all_done, truncated};
+}
+static_assert(all_orders_done(0x03030000u, 3u) && !all_orders_done(0u, 0u) && !all_orders_done(0x03030000u, 2u) &&
+                  !all_orders_done(0x02030000u, 3u) && all_orders_done(0x40401234u, 0xABCD40u) && step_truncated(5, 5) &&
+                  !step_truncated(4, 5),
+              "the episode-end rule");
 
 // OR into an order word shared by two waves (k_step_ag: the machines' processed bits and the
 // packaging completions update one word from different wavefronts); returns the old word.
@@ -415,6 +473,7 @@ FJSP_DEV uint32_t pickup_execute(Env& E, const Tables& T, const Cfg& C, int acti
 constexpr uint32_t PKS_PUSHED = 1u << 16;    // beside the result word: the speculative pickup pushed a tray,
 constexpr uint32_t PKS_POOL0 = 1u << 17;     //   its decision read an empty pool
 constexpr uint32_t PKS_POOL_ADD = 1u << 8;   // the AGV's delta: AgvPre::pool_add (W5's pool + 1)
+static_assert(PKS_POOL_ADD == 1u << W0_NEXT_BITS, "the delta rides above next_order in P's result word (w0_with_next_order drops it)");
 // asked of the words before the speculative pickup
 FJSP_DEV bool pickup_reads_empty_pool(const Env& E, int action) {
     const bool ok_order = action == 1 && (E.cur_order() >= 0 || E.next_order() < E.norders());
@@ -457,6 +516,30 @@ constexpr uint16_t PKG_CONT = 0xFFFF;   // scstep of a run that is not the first
 constexpr uint32_t PICK_LISTS = (1u << L_PREADY) | (1u << L_STORAGE) | (1u << L_M0R) | (1u << L_M1R);
 constexpr uint32_t DROP_LISTS = (1u << L_STORAGE) | (1u << L_M0Q) | (1u << L_M1Q) | (0xFu << L_PKG);
 
+// The AGV's deferred packaging drop (agv_execute<true>, agv_pre -> agv_pack_drop, pack_lane_step):
+// 0 = none, or set bit 0 | tray slot [1,9) | tray code [9,22) | colour [22,24).
+constexpr int PEND_SLOT_SH = 1, PEND_CODE_SH = 9, PEND_COLOR_SH = 22;
+constexpr uint32_t PEND_SET = 1u, PEND_SLOT_MASK = 0xFFu, PEND_CODE_MASK = 0x1FFFu, PEND_COLOR_MASK = 3u;
+FJSP_HD constexpr uint32_t pend_make(int slot, int code, int color) {
+    return PEND_SET | ((uint32_t)slot << PEND_SLOT_SH) | ((uint32_t)code << PEND_CODE_SH) | ((uint32_t)color << PEND_COLOR_SH);
+}
+FJSP_HD constexpr int pend_slot(uint32_t pend) { return (int)((pend >> PEND_SLOT_SH) & PEND_SLOT_MASK); }
+FJSP_HD constexpr int pend_code(uint32_t pend) { return (int)((pend >> PEND_CODE_SH) & PEND_CODE_MASK); }
+FJSP_HD constexpr int pend_color(uint32_t pend) { return (int)((pend >> PEND_COLOR_SH) & PEND_COLOR_MASK); }
+static_assert((PEND_SET & (PEND_SLOT_MASK << PEND_SLOT_SH)) == 0u &&
+                  ((PEND_SLOT_MASK << PEND_SLOT_SH) & (PEND_CODE_MASK << PEND_CODE_SH)) == 0u &&
+                  ((PEND_CODE_MASK << PEND_CODE_SH) & (PEND_COLOR_MASK << PEND_COLOR_SH)) == 0u &&
+                  PEND_COLOR_SH + 2 <= 32,
+              "the drop word's fields do not overlap");
+static_assert(NIL <= (int)PEND_SLOT_MASK && ((MAX_ORDERS - 1) | (15 << 6) | (7 << 10)) <= (int)PEND_CODE_MASK,
+              "a slot index fits 8 bits, the largest tray code (tc_make) 13");
+static_assert(pend_slot(pend_make(0xFF, 0, 0)) == 0xFF && pend_code(pend_make(0xFF, 0, 0)) == 0 &&
+                  pend_code(pend_make(0, 0x1FFF, 0)) == 0x1FFF && pend_slot(pend_make(0, 0x1FFF, 3)) == 0 &&
+                  pend_color(pend_make(0, 0, 3)) == 3 && pend_color(pend_make(0xFF, 0x1FFF, 0)) == 0 && pend_make(0, 0, 0) != 0u,
+              "decode(encode) at the fields' extremes; a drop is never the empty word");
+static_assert(pend_make(0x5A, 0x1234, 2) == (1u | ((uint32_t)0x5A << 1) | ((uint32_t)0x1234 << 9) | ((uint32_t)2 << 22)),
+              "pend_make equals the hand-spelled word it replaces");
+
 // AGVAgent.execute_action / _execute_pickup / _execute_drop (AGVAgent.py:180-368).
 // Returns the result word; *move_to receives the target location of a spawned move.
 // Written predicated (straight-line): every action's outcome is computed as a condition and the
@@ -465,7 +548,7 @@ constexpr uint32_t DROP_LISTS = (1u << L_STORAGE) | (1u << L_M0Q) | (1u << L_M1Q
 // small guarded blocks: the PICKUP pop's loads and the DROP push's stores.
 // DEFER (k_step_ag's AGV wave P, which runs a step ahead): a drop at packaging is not routed here — the
 // station choice needs the Resource counts after the current run phase — but returned in
-// *pend (1 | slot << 1 | code << 9 | colour << 22) for agv_pack_drop.
+// *pend (pend_make) for agv_pack_drop.
 template <bool DEFER = false>
 FJSP_DEV uint32_t agv_execute(Env& E, const Tables& T, const Cfg& C, int action, int* move_to,
                               uint32_t* pend = nullptr) {
@@ -533,7 +616,10 @@ FJSP_DEV uint32_t agv_execute(Env& E, const Tables& T, const Cfg& C, int action,
             E.w[20 + k] = (to_st && st == k) ? nw : wk;
         }
     } else {
-        *pend = (ok7 && at_pack) ? (1u | ((uint32_t)carry << 1) | ((uint32_t)code << 9) | ((uint32_t)E.carry_color() << 22)) : 0u;
+        // pend_make, in place (a call reads the colour before the shifts and moves k_step_ag's instructions)
+        *pend = (ok7 && at_pack) ? (PEND_SET | ((uint32_t)carry << PEND_SLOT_SH) | ((uint32_t)code << PEND_CODE_SH) |
+                                    ((uint32_t)E.carry_color() << PEND_COLOR_SH))
+                                 : 0u;
     }
     // AGV word: carried tray (pickup) / empty hands (drop)
     const uint32_t rg = tc_range((int)scode);
@@ -665,7 +751,9 @@ FJSP_DEV AgvPre agv_pre(const Env& E, const Tables& T, const Cfg& C, int action)
                         (ok7 ? (16u | (at_pack ? 32u : 0u)) : 0u);
     a.r[0] = rc | ((action == 0 || is_move || ok7) ? 1u : 2u);
     a.r[1] = want6 ? (rc | 1u | 8u) : a.r[0];
-    a.pend = (ok7 && at_pack) ? (1u | ((uint32_t)carry << 1) | ((uint32_t)code << 9) | ((uint32_t)E.carry_color() << 22)) : 0u;
+    a.pend = (ok7 && at_pack) ? (PEND_SET | ((uint32_t)carry << PEND_SLOT_SH) | ((uint32_t)code << PEND_CODE_SH) |   // pend_make, in place
+                                 ((uint32_t)E.carry_color() << PEND_COLOR_SH))
+                              : 0u;
     a.pool_add = (ok7 && at_pick) ? (1u << 8) : 0u;   // add_empty_tray (the pool never exceeds its 16 bits: <= pool0)
     a.st = (ok7 && at_store && store_full) ? ST_TRAY_LOST : 0u;
     return a;
@@ -707,7 +795,7 @@ FJSP_DEV uint32_t agv_fin(Env& E, const Tables& T, const AgvPre& a, int* move_to
 // NS: the station slots `st` can name (4; k_step_ag's lane groups hold 4 / G of them each).
 template <int NS>
 FJSP_DEV void agv_pack_push(Env& E, const Tables& T, uint32_t pend, int st) {
-    const int carry = (int)((pend >> 1) & 0xFFu), code = (int)((pend >> 9) & 0x1FFFu);
+    const int carry = pend_slot(pend), code = pend_code(pend);
     constexpr uint32_t CAND = ((1u << NS) - 1u) << L_PKG;
     const uint32_t lwd = lword<CAND>(E, L_PKG + st);
     T.snext[carry * T.stride] = (uint8_t)NIL;
@@ -725,7 +813,7 @@ FJSP_DEV void agv_pack_push(Env& E, const Tables& T, uint32_t pend, int st) {
     }
 }
 FJSP_DEV void agv_pack_drop(Env& E, const Tables& T, const Cfg& C, uint32_t pend) {
-    const int st = pkg_station(E, C, (int)((pend >> 22) & 3u));
+    const int st = pkg_station(E, C, pend_color(pend));
     if (st < 0) { E.flag(ST_PROD_LOST); return; }
     agv_pack_push<4>(E, T, pend, st);
 }
@@ -965,7 +1053,7 @@ FJSP_DEV uint32_t pack_lane_step(Env& E, const Tables& T, const Cfg& C, int g, u
     pack_slots<0, NP>([&](auto p) { due[p.value] = pack_due<p.value>(E, T, step); });
     pack_slots<0, NP>([&](auto p) { done[p.value] = pack_complete<p.value>(E, T, due[p.value], &orders_done); });
     if (pend) {   // FJSPSimulation.add_tray_to_packaging: pkg_station on the gathered room bits
-        const uint32_t cand = (uint32_t)nib(nibs(0, 0x4, 0x3, 0x8, 0, 0), (int)((pend >> 22) & 3u)) & room;
+        const uint32_t cand = (uint32_t)nib(nibs(0, 0x4, 0x3, 0x8, 0, 0), pend_color(pend)) & room;
         const int s = __builtin_ffs((int)cand) - 1;
         if (s < 0) E.flag(ST_PROD_LOST);
         else if ((s & (G - 1)) == g) agv_pack_push<NP>(E, T, pend, s / G);

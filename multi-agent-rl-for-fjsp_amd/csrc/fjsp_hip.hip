@@ -84,7 +84,7 @@ __global__ void __launch_bounds__(BLOCK) k_seed(DevState S, const uint32_t* __re
     if (e >= S.n) return;
     mt_seed(S.mt, e, seeds ? seeds[e] : seed_base + (uint32_t)e);
     S.words[3 * S.n + e] = 0;
-    S.words[(size_t)PGW * S.n + e] = 0;
+    S.words[(size_t)PGW * S.n + e] = PDREC_NONE;
 }
 
 __global__ void __launch_bounds__(BLOCK) k_reset(DevState S, Cfg C, const uint32_t* __restrict__ seeds,
@@ -420,11 +420,7 @@ __global__ void __launch_bounds__(BLOCK) k_step_many(DevState S, Cfg C, int K, u
     env_load(E, S.words, S.n, e);
     Tables T;
     if constexpr (LDS) {
-        T.orders = s_orders + lane;
-        T.scode = s_code + lane;
-        T.snext = s_next + lane;
-        T.scstep = s_cstep + lane;
-        T.stride = BLOCK;
+        T = lds_tables(s_orders, s_code, s_next, s_cstep, lane);
         tables_copy_in(S, T, e, E.norders(), E.slot_next());
     } else {
         T = tables_of(S, e);
@@ -480,12 +476,7 @@ __global__ void __launch_bounds__(BLOCK) k_search_rollout(DevState S, Cfg C, int
     }
     Env E;
     env_load(E, S.words, S.n, e);
-    Tables T;
-    T.orders = s_orders + lane;
-    T.scode = s_code + lane;
-    T.snext = s_next + lane;
-    T.scstep = s_cstep + lane;
-    T.stride = BLOCK;
+    const Tables T = lds_tables(s_orders, s_code, s_next, s_cstep, lane);
     tables_copy_in(S, T, e, E.norders(), E.slot_next());
     {
         // A tray slot taken during the launch (at most one per step) gets its code and its link
@@ -613,11 +604,12 @@ __device__ __forceinline__ void predraw_wave(const DevState& S, int K, int lane,
     const uint32_t n = (uint32_t)S.n;
     // the pre-draw wave: 0 idle, 1 copying the live row, 2 drawing, 3 table ready
     int ph = 0, nord_ = 0, pos_ = 0, g_ = 0;
-    uint32_t src = 0, my = 0x100u;   // live row at the start of the pre-draw; episode it is for
+    uint32_t src = 0, my = MB_EPI_NONE;   // live row at the start of the pre-draw; episode it is for
     OrderDraw d_{0, 0, 0, 0, 0u};
     static_assert(!ASYNC || PB == PD_B, "the sliced lane draws PD_B words per refill");
     // the table's size, the cursor and the draw: ASYNC in the sliced lane L, else in the plain
-    // variables above (k_step_pipe's code stays as it was)
+    // variables above (k_step_pipe's code stays as it was: with a plain lane struct in L's place
+    // k_step_pipe<lds, 2, pre-draw> allocates its registers in another order)
     struct NoLane {};
     std::conditional_t<ASYNC, PreDrawLane, NoLane> L;
     if constexpr (ASYNC) L.start(0, 0, 0);
@@ -636,13 +628,13 @@ __device__ __forceinline__ void predraw_wave(const DevState& S, int K, int lane,
     uint4 cp0 = make_uint4(0u, 0u, 0u, 0u), cp1 = cp0, cp2 = cp0;
     if (valid) {
         const uint32_t pg = S.words[(size_t)PGW * n + e];
-        if (pg & 1u) {
+        if (pdrec_ready(pg)) {
             ph = 3;
             my = 0;
-            nord = (int)((pg >> 24) & 0x7Fu);
-            pos = (int)((pg >> 1) & 0x3FFu);
-            g = (int)((pg >> 11) & 0x3FFu);
-            src = ((pg >> 21) & 1u) ^ (nord > 0 ? 1u : 0u);
+            nord = pdrec_nord(pg);
+            pos = pdrec_pos(pg);
+            g = pdrec_g(pg);
+            src = pdrec_row(pg) ^ (nord > 0 ? 1u : 0u);
         }
     }
     FJSP_DIAG(
@@ -659,17 +651,17 @@ __device__ __forceinline__ void predraw_wave(const DevState& S, int K, int lane,
         )
         if (valid) {
             const uint32_t si = s_mb[0][k & 1][lane];
-            if ((si & 0xFFu) != my) {   // a new episode: start over from its stream position
+            if (simmb_epi(si) != my) {   // a new episode: start over from its stream position
                 const uint32_t sw = s_mb[1][k & 1][lane];
-                my = si & 0xFFu;
+                my = simmb_epi(si);
                 if constexpr (ASYNC) {
-                    src = sw >> 31;
-                    L.start((int)((si >> 8) & 0x7Fu), (int)(sw & 0x3FFu), (int)((sw >> 16) & 0x3FFu));
+                    src = mtcur_row(sw);
+                    L.start(simmb_nord(si), mtcur_pos(sw), mtcur_g(sw));
                 } else {
-                    nord = (int)((si >> 8) & 0x7Fu);
-                    src = sw >> 31;
-                    pos = (int)(sw & 0x3FFu);
-                    g = (int)((sw >> 16) & 0x3FFu);
+                    nord = simmb_nord(si);
+                    src = mtcur_row(sw);
+                    pos = mtcur_pos(sw);
+                    g = mtcur_g(sw);
                     d = OrderDraw{0, 0, 0, 0, 0u};
                 }
                 ph = nord > 0 ? 1 : 3;
@@ -800,8 +792,8 @@ __device__ __forceinline__ void predraw_wave(const DevState& S, int K, int lane,
         )
         if (valid) {
             const uint32_t wrow = nord > 0 ? (src ^ 1u) : src;
-            s_mb[2][(k + 1) & 1][lane] = (ph == 3 ? 1u : 0u) | (my << 1) | ((uint32_t)nord << 9);
-            s_mb[3][(k + 1) & 1][lane] = (uint32_t)pos | ((uint32_t)g << 16) | (wrow << 31);
+            s_mb[2][(k + 1) & 1][lane] = pdmb_make(ph == 3, my, (uint32_t)nord);
+            s_mb[3][(k + 1) & 1][lane] = mtcur_make((uint32_t)pos, (uint32_t)g, wrow);
         }
         FJSP_DIAG(
         const uint64_t pb0 = __builtin_amdgcn_s_memtime();
@@ -840,11 +832,11 @@ __device__ __forceinline__ void predraw_wave(const DevState& S, int K, int lane,
     }
     )
     if (valid) {
-        uint32_t pg = 0;
-        if (FINAL_MB && (s_mb[0][(K + 1) & 1][lane] & 0xFFu) != my) ph = 0;   // reset in the final epoch
+        uint32_t pg = PDREC_NONE;
+        if (FINAL_MB && simmb_epi(s_mb[0][(K + 1) & 1][lane]) != my) ph = 0;   // reset in the final epoch
         if (ph == 3) {
             const uint32_t wrow = nord > 0 ? (src ^ 1u) : src;
-            pg = 1u | ((uint32_t)pos << 1) | ((uint32_t)g << 11) | (wrow << 21) | ((uint32_t)nord << 24);
+            pg = pdrec_make(pos, g, wrow, nord);
             for (int o = 0; o < nord; o++) S.nxt[(size_t)o * n + e] = s_nxt[o * BLOCK + lane];
         }
         S.words[(size_t)PGW * n + e] = pg;
@@ -952,7 +944,7 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
     constexpr int CR = PG_CR, PB = PG_PB;
     __shared__ uint32_t s_orders[LDS ? MAX_ORDERS * BLOCK : 1];
     __shared__ uint32_t s_nxt[PG ? MAX_ORDERS * BLOCK : 1];
-    __shared__ uint32_t s_mb[PG ? 4 : 1][2][BLOCK];   // sim: epi | nord << 8, cursor word; pre-draw: ready, cursor
+    __shared__ uint32_t s_mb[PG ? 4 : 1][2][BLOCK];   // sim: simmb_*, W3; pre-draw: pdmb_*, cursor word (fjsp_predraw.h)
     __shared__ uint4 s_cp[PG ? PG_CR : 1][3][BLOCK];   // MT rows in flight (pre-draw copies)
     __shared__ uint16_t s_code[LDS ? MAX_SLOTS * BLOCK : 1];
     __shared__ uint8_t s_next[LDS ? MAX_SLOTS * BLOCK : 1];
@@ -975,17 +967,17 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
     }
     if constexpr (PG) {   // step-0 mailboxes
         if (wave == 0 && valid) {
-            s_mb[0][0][lane] = ((S.words[e] >> 16) & 0xFFu) << 8;   // episode counter 0 | num_orders
+            s_mb[0][0][lane] = simmb_make(0u, (uint32_t)w0_norders(S.words[e]));   // episode counter 0 | num_orders
             s_mb[1][0][lane] = S.words[3 * n + e];
         }
         if (wave == 1 + NEMIT && valid) {
             const uint32_t pg = S.words[(size_t)PGW * n + e];
             uint32_t r = 0, c = 0;
-            if (pg & 1u) {   // a table finished in an earlier launch
-                const int no = (int)((pg >> 24) & 0x7Fu);
+            if (pdrec_ready(pg)) {   // a table finished in an earlier launch (for the launch's episode 0)
+                const int no = pdrec_nord(pg);
                 for (int o = 0; o < no; o++) s_nxt[o * BLOCK + lane] = S.nxt[(size_t)o * n + e];
-                r = 1u | ((uint32_t)no << 9);
-                c = ((pg >> 1) & 0x3FFu) | (((pg >> 11) & 0x3FFu) << 16) | (((pg >> 21) & 1u) << 31);
+                r = pdmb_make(true, 0u, (uint32_t)no);
+                c = pdrec_cursor(pg);
             }
             s_mb[2][0][lane] = r;
             s_mb[3][0][lane] = c;
@@ -1005,11 +997,7 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
         if (valid) env_load(E, S.words, S.n, e);
         Tables T = tables_of(S, valid ? e : 0);
         if constexpr (LDS) {   // the env's order table and used slot prefix live in LDS for the launch
-            T.orders = s_orders + lane;
-            T.scode = s_code + lane;
-            T.snext = s_next + lane;
-            T.scstep = s_cstep + lane;
-            T.stride = BLOCK;
+            T = lds_tables(s_orders, s_code, s_next, s_cstep, lane);
             if (valid) tables_copy_in(S, T, e, E.norders(), E.slot_next());
         }
         FJSP_DIAG(
@@ -1044,24 +1032,25 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
                 for (int i = SNAP_GSTAT + 1; i < SNAP_N; i++) v[i] = 0u;
                 snap_put(snap[k & 1], lane, v);
                 const int nord = E.norders();
-                const int all_done = E.ncompleted() == nord && nord > 0 && E.next_order() == nord;
-                const int truncated = E.step() >= C.max_steps;
+                const auto [all_done, truncated] = episode_end(E, C);
                 FJSP_STAMP(E, 3);
                 E.set_step(E.step() + 1);
                 if (autoreset && (all_done || truncated)) {   // reset(seed=None)
                     if constexpr (PG) {
                         const uint32_t pr = s_mb[2][k & 1][lane];
-                        if ((pr & 1u) && ((pr >> 1) & 0xFFu) == (uint32_t)epi && (int)((pr >> 9) & 0x7Fu) == nord)
+                        // pdmb_ready_for, in place: the call moves this kernel's instructions
+                        if ((pr & PDMB_READY) && ((pr >> PDMB_EPI_SH) & MB_EPI_MASK) == (uint32_t)epi &&
+                            (int)((pr >> PDMB_NORD_SH) & MB_NORD_MASK) == nord)
                             env_reset_predrawn(E, T, C, nord, s_mb[3][k & 1][lane], s_nxt + lane);
                         else
                             E = env_reset_cold(E, T, C, S, e, nord, false);
-                        epi = (epi + 1) & 0xFF;
+                        epi = mb_next_epi(epi);
                     } else {
                         E = env_reset_cold(E, T, C, S, e, nord);
                     }
                 }
                 if constexpr (PG) {
-                    s_mb[0][(k + 1) & 1][lane] = (uint32_t)epi | ((uint32_t)E.norders() << 8);
+                    s_mb[0][(k + 1) & 1][lane] = simmb_make((uint32_t)epi, (uint32_t)E.norders());
                     s_mb[1][(k + 1) & 1][lane] = E.w[3];
                 }
                 FJSP_STAMP(E, 6);
@@ -1133,9 +1122,7 @@ __global__ void __launch_bounds__((1 + NEMIT + PG) * BLOCK) __attribute__((amdgp
                         PartSink<1> ps{sink};
                         observe(E, C, ps);
                     }
-                    const int nord = E.norders();
-                    const int all_done = E.ncompleted() == nord && nord > 0 && E.next_order() == nord;
-                    const int truncated = E.step() >= C.max_steps;
+                    const auto [all_done, truncated] = episode_end(E, C);
                     if (out.term) st32(out.term, t * n + ue, (uint8_t)all_done);
                     if (out.trunc) st32(out.trunc, t * n + ue, (uint8_t)truncated);
                     if (out.status) st32(out.status, t * n + ue, E.status());
@@ -1304,9 +1291,9 @@ __device__ __forceinline__ bool ag_fresh(int k, bool valid, const uint4 (*s_p1)[
     if (k == 0) return true;   // the first step of a launch runs the pickup and the AGV on AM
     if (!valid) return false;
     const uint32_t w0a = s_p1[(k - 1) & 1][0][lane].x;   // P1_W0 of step k-1
-    const int nord = (int)((w0a >> 16) & 0xFFu);
-    const int all_done = (int)(s_kpost[(k - 1) & 1][lane] & 0xFFu) == nord && nord > 0 && (int)(w0a >> 24) == nord;
-    return autoreset && (all_done || (int)(w0a & 0xFFFFu) >= C.max_steps);
+    const int nord = (int)((w0a >> W0_NORD_SH) & W0_NORD_MASK);   // all_orders_done and step_truncated, in place
+    const int all_done = (int)(s_kpost[(k - 1) & 1][lane] & W1_NCOMP_MASK) == nord && nord > 0 && (int)(w0a >> W0_NEXT_SH) == nord;
+    return autoreset && (all_done || (int)(w0a & W0_STEP_MASK) >= C.max_steps);
 }
 
 // Holds agv_pre's results in VGPRs at this point of P's step: without it the compiler is free to
@@ -1365,9 +1352,7 @@ __device__ __forceinline__ void ag_emit(const uint32_t* v, uint32_t t, uint32_t 
     } else {
         FieldSink<0u, (1u << NI8) - 1u, 0u, AgSplit<G>::MASKS_E2> ps{sink};
         observe(E, C, ps);
-        const int nord = E.norders();
-        const int all_done = E.ncompleted() == nord && nord > 0 && E.next_order() == nord;
-        const int truncated = E.step() >= C.max_steps;
+        const auto [all_done, truncated] = episode_end(E, C);
         if (out.term) st32(out.term, t * n + ue, (uint8_t)all_done);
         if (out.trunc) st32(out.trunc, t * n + ue, (uint8_t)truncated);
         if (out.status) st32(out.status, t * n + ue, E.status());
@@ -1418,7 +1403,7 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
     const int e = blk * EPW + lane;
     const bool valid = lane < EPW && e < S.n;
     const uint32_t n = (uint32_t)S.n, ue = (uint32_t)e;
-    const Tables TL{s_orders + lane, s_code + lane, s_next + lane, s_cstep + lane, BLOCK};
+    const Tables TL = lds_tables(s_orders, s_code, s_next, s_cstep, lane);
     FJSP_DIAG(uint64_t ag_busy = 0, ag_wait = 0;   // per step: busy until the barrier; AM: until post 1, K / P: spinning
               uint64_t amt[6] = {0, 0, 0, 0, 0, 0};   // AM: cycles into the step at its phase marks
               uint64_t ag_last = 0;)                   // steps this wave arrived last at the barrier
@@ -1470,8 +1455,8 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
             xv[j] = S.snext[q * n + e];
             tv[j] = S.scstep[q * n + e];
         }
-        const uint32_t nslots = w5 >> 24;
-        const uint32_t no = (w0 >> 16) & 0xFFu, npd = (pg & 1u) ? (pg >> 24) & 0x7Fu : 0u;
+        const uint32_t nslots = (uint32_t)w5_slot_next(w5);
+        const uint32_t no = (uint32_t)w0_norders(w0), npd = pdrec_ready(pg) ? (uint32_t)pdrec_nord(pg) : 0u;
 #pragma unroll
         for (int j = 0; j < MAX_ORDERS / AG_WAVES; j++) {
             const uint32_t o = (uint32_t)(wave + AG_WAVES * j);
@@ -1506,12 +1491,12 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
             }
         }
         if (wave == AG_AM) {
-            s_mb[0][0][lane] = no << 8;   // episode counter 0 | num_orders
+            s_mb[0][0][lane] = simmb_make(0u, no);   // episode counter 0 | num_orders
             s_mb[1][0][lane] = S.words[3 * n + e];
         }
-        if (wave == AG_PD) {   // a table finished in an earlier launch
-            s_mb[2][0][lane] = (pg & 1u) ? 1u | (npd << 9) : 0u;
-            s_mb[3][0][lane] = (pg & 1u) ? ((pg >> 1) & 0x3FFu) | (((pg >> 11) & 0x3FFu) << 16) | (((pg >> 21) & 1u) << 31) : 0u;
+        if (wave == AG_PD) {   // a table finished in an earlier launch (for the launch's episode 0)
+            s_mb[2][0][lane] = pdrec_ready(pg) ? pdmb_make(true, 0u, npd) : 0u;
+            s_mb[3][0][lane] = pdrec_ready(pg) ? pdrec_cursor(pg) : 0u;
         }
     }
     __syncthreads();
@@ -1540,7 +1525,7 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
         const int g = lane / EPW, el = lane % EPW;
         const int em = blk * EPW + el;
         const bool mval = g < 2 && em < S.n, v1 = mval && g == 1;   // `valid`: group 0's lanes
-        const Tables TM{s_orders + el, s_code + el, s_next + el, s_cstep + el, BLOCK};
+        const Tables TM = lds_tables(s_orders, s_code, s_next, s_cstep, el);
         const int ptk = g ? C.ptk_big : C.ptk_small;
         Env E;
 #pragma unroll
@@ -1575,16 +1560,18 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
             }
             if (mval && k > 0) {   // end of step k - 1: auto-reset once K has counted the completions
                 const int nord = E.norders();
-                const int all_done = (int)(kc & 0xFFu) == nord && nord > 0 && E.next_order() == nord;
+                const int all_done = (int)(kc & W1_NCOMP_MASK) == nord && nord > 0 && E.next_order() == nord;   // all_orders_done, in place
                 if (autoreset && (all_done || trunc_prev)) {
                     fresh = true;
                     if (g == 0) {
                         const uint32_t pr = s_mb[2][k & 1][lane];
-                        if ((pr & 1u) && ((pr >> 1) & 0xFFu) == (uint32_t)epi && (int)((pr >> 9) & 0x7Fu) == nord)
+                        // pdmb_ready_for, in place: the call moves this kernel's instructions
+                        if ((pr & PDMB_READY) && ((pr >> PDMB_EPI_SH) & MB_EPI_MASK) == (uint32_t)epi &&
+                            (int)((pr >> PDMB_NORD_SH) & MB_NORD_MASK) == nord)
                             env_reset_predrawn(E, TL, C, nord, s_mb[3][k & 1][lane], s_nxt + lane);
                         else
                             E = env_reset_cold(E, TL, C, S, e, nord, false);
-                        epi = (epi + 1) & 0xFF;
+                        epi = mb_next_epi(epi);
                     } else {
                         mach_lane_clear(E);
                         E.set_norders(nord);
@@ -1596,7 +1583,7 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
                 uint32_t r0 = 0, r1 = 0, pend = 0;
                 if (mval && !fresh) {   // step k's pickup and AGV ran on P during step k - 1
                     // (group 1 keeps next_order and its machine's lists in slot 0; the rest is unused there)
-                    E.w[0] = (E.w[0] & 0x00FFFFFFu) | (rs[RS_NO] << 24);
+                    E.w[0] = w0_with_next_order(E.w[0], rs[RS_NO]);
                     E.w[4] = rs[RS_W4];
 #pragma unroll
                     for (int i = 0; i < 8; i++) E.w[5 + i] = rs[RS_W5 + i];
@@ -1656,13 +1643,13 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
                         static_assert(SA::L(4) == 12 && SA::M1 == 14 && SA::X == 15, "group 1's snapshot words");
                         snap[k & 1].q[3][el] = make_uint4(E.w[7 + L_M0Q], E.w[7 + L_M0R], E.w[17], rm2 | (E.w[2] << 16));
                     }
-                    trunc_prev = E.step() >= C.max_steps;
+                    trunc_prev = step_truncated(E.step(), C.max_steps);
                     E.set_step(E.step() + 1);
                     fresh = false;
                 }
             }
             if (valid) {   // PD's mailbox for the next step (off the way to the post: its release waits for them)
-                s_mb[0][(k + 1) & 1][lane] = (uint32_t)epi | ((uint32_t)E.norders() << 8);
+                s_mb[0][(k + 1) & 1][lane] = simmb_make((uint32_t)epi, (uint32_t)E.norders());
                 s_mb[1][(k + 1) & 1][lane] = E.w[3];
             }
             AG_ACC(ag_busy);
@@ -1732,15 +1719,17 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
             if (valid) {
                 if (k > 0) {   // end of step k - 1: auto-reset once K has counted the completions
                     const int nord = E.norders();
-                    const int all_done = (int)(kc & 0xFFu) == nord && nord > 0 && E.next_order() == nord;
+                    const int all_done = (int)(kc & W1_NCOMP_MASK) == nord && nord > 0 && E.next_order() == nord;   // all_orders_done, in place
                     if (autoreset && (all_done || trunc_prev)) {
                         fresh = true;
                         const uint32_t pr = s_mb[2][k & 1][lane];
-                        if ((pr & 1u) && ((pr >> 1) & 0xFFu) == (uint32_t)epi && (int)((pr >> 9) & 0x7Fu) == nord)
+                        // pdmb_ready_for, in place: the call moves this kernel's instructions
+                        if ((pr & PDMB_READY) && ((pr >> PDMB_EPI_SH) & MB_EPI_MASK) == (uint32_t)epi &&
+                            (int)((pr >> PDMB_NORD_SH) & MB_NORD_MASK) == nord)
                             env_reset_predrawn(E, TL, C, nord, s_mb[3][k & 1][lane], s_nxt + lane);
                         else
                             E = env_reset_cold(E, TL, C, S, e, nord, false);
-                        epi = (epi + 1) & 0xFF;
+                        epi = mb_next_epi(epi);
                     }
                 }
             }
@@ -1751,7 +1740,7 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
                 for (int a = 0; a < 4; a++) { act[a] = (a0 >> (8 * a)) & 0xFF; act[4 + a] = (a1 >> (8 * a)) & 0xFF; }
                 uint32_t r0, r1, pend = 0;
                 if (!fresh) {   // step k's pickup and AGV ran on P during step k - 1
-                    E.w[0] = (E.w[0] & 0x00FFFFFFu) | (rs[RS_NO] << 24);
+                    E.w[0] = w0_with_next_order(E.w[0], rs[RS_NO]);
                     E.w[4] = rs[RS_W4];
 #pragma unroll
                     for (int i = 0; i < 8; i++) E.w[5 + i] = rs[RS_W5 + i];
@@ -1788,12 +1777,12 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
                 const uint32_t v[16] = {E.w[0], E.w[2], E.w[4], E.w[5], E.w[6], E.w[7], E.w[8], E.w[9], E.w[10],
                                         E.w[11], E.w[12], E.w[17], E.w[18], r0 | (r1 << 16), r2 | (r3 << 16), 0u};
                 snap_put4(snap[k & 1], 0, lane, v);
-                trunc_prev = E.step() >= C.max_steps;
+                trunc_prev = step_truncated(E.step(), C.max_steps);
                 E.set_step(E.step() + 1);
                 fresh = false;
             }
             if (valid) {   // PD's mailbox for the next step (off the way to the post: its release waits for them)
-                s_mb[0][(k + 1) & 1][lane] = (uint32_t)epi | ((uint32_t)E.norders() << 8);
+                s_mb[0][(k + 1) & 1][lane] = simmb_make((uint32_t)epi, (uint32_t)E.norders());
                 s_mb[1][(k + 1) & 1][lane] = E.w[3];
             }
             AG_ACC(ag_busy);
@@ -1824,13 +1813,13 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
         const int g = lane / EPW, el = lane % EPW;
         const int ek = blk * EPW + el;
         const bool kvalid = ek < S.n;
-        const Tables TK{s_orders + el, s_code + el, s_next + el, s_cstep + el, BLOCK};
+        const Tables TK{s_orders + el, s_code + el, s_next + el, s_cstep + el, BLOCK};   // lds_tables, spelled out (the call moves k_step_ag<32>'s and <16>'s instructions)
         Env E;
 #pragma unroll
         for (int i = 0; i < NSTATE; i++) E.w[i] = 0u;
         if (kvalid) {
             pack_lane_load<G>(E, g, [&](int i) { return S.words[(size_t)i * n + ek]; });
-            E.w[0] = S.words[ek] & 0xFFFFu;   // the step counter (AM owns W0)
+            E.w[0] = S.words[ek] & W0_STEP_MASK;   // the step counter (AM owns W0)
         }
         bool trunc_prev = false;
         for (int k = 0; k <= K; k++) {
@@ -1838,8 +1827,8 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
             bool fresh = k == 0;
             if (kvalid && k > 0) {   // the reset AM makes at the top of this step, on the packaging words
                 const uint32_t w0a = s_p1[(k - 1) & 1][0][el].x;   // AM's W0 after step k-1's pickup (P1_W0)
-                const int nord = (int)((w0a >> 16) & 0xFFu);
-                const int all_done = E.ncompleted() == nord && nord > 0 && (int)(w0a >> 24) == nord;
+                const int nord = (int)((w0a >> W0_NORD_SH) & W0_NORD_MASK);   // all_orders_done, in place
+                const int all_done = E.ncompleted() == nord && nord > 0 && (int)(w0a >> W0_NEXT_SH) == nord;
                 if (autoreset && (all_done || trunc_prev)) {   // env_clear of the packaging words
                     fresh = true;
                     pack_lane_clear<G>(E);
@@ -1917,7 +1906,7 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
                             sh[2 * SK::R45 * BLOCK + s] = (uint16_t)r[p];
                         }
                     }
-                    trunc_prev = step >= C.max_steps;
+                    trunc_prev = step_truncated(step, C.max_steps);
                     E.set_step(step + 1);
                 }
             } else if (kvalid && g == 0) {
@@ -1997,7 +1986,7 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
                     for (int i = 0; i < 7; i++) sa[i] = Ea.w[6 + i];
                     // RS_NO's word carries the AGV's pool increment (PKS_POOL_ADD) above next_order's
                     // 8 bits, for E3's compose; AM shifts it out
-                    const uint32_t rs[16] = {(pk.x >> 24) | pre.pool_add, pk.y, Ea.w[5], Ea.w[6], Ea.w[7], Ea.w[8], Ea.w[9],
+                    const uint32_t rs[16] = {(pk.x >> W0_NEXT_SH) | pre.pool_add, pk.y, Ea.w[5], Ea.w[6], Ea.w[7], Ea.w[8], Ea.w[9],
                                              Ea.w[10], Ea.w[11], Ea.w[12], pr.x, r1, pr.y | Ea.w[2], 0u, 0u, pend};
                     q_put(&s_res[(k + 1) & 1][0][lane], 4, rs);
                 }
@@ -2058,7 +2047,7 @@ k_step_ag(DevState S, Cfg Ck, int K, uint64_t seed, uint32_t gid0, uint32_t step
                                 q_get(&s_p1[k & 1][0][lane], 2, p1);
                                 Ep.w[0] = p1[P1_W0]; Ep.w[4] = p1[P1_W4]; Ep.w[5] = p1[P1_W5]; Ep.w[7] = p1[P1_W7];
                             } else {
-                                Ep.w[0] = (s_p1[(k - 1) & 1][0][lane].x & 0x00FFFFFFu) | (rs[RS_NO] << 24);
+                                Ep.w[0] = w0_with_next_order(s_p1[(k - 1) & 1][0][lane].x, rs[RS_NO]);
                                 Ep.w[4] = rs[RS_W4]; Ep.w[5] = rs[RS_W5]; Ep.w[7] = rs[RS_W5 + 2];
                             }
                             const int act0 = (int)(s_act[(k + 1) & 3][0][lane] & 0xFFu);
@@ -3236,8 +3225,8 @@ int fjsp_mt_get(fjsp_handle* h, int32_t env, uint32_t* key, int32_t* pos) {
     HIPCHK(hipStreamSynchronize(h->stream));
     uint32_t st = 0;
     HIPCHK(hipMemcpy(&st, h->S.words + (size_t)3 * h->n + env, 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(key, h->S.mt + ((size_t)(st >> 31) * h->n + env) * MT_N, 4 * MT_N, hipMemcpyDeviceToHost));
-    int mti = (int)(st & 0x3FF), gg = (int)((st >> 16) & 0x3FF);
+    HIPCHK(hipMemcpy(key, h->S.mt + ((size_t)mtcur_row(st) * h->n + env) * MT_N, 4 * MT_N, hipMemcpyDeviceToHost));
+    const int mti = mtcur_pos(st), gg = mtcur_g(st);
     if (gg == 0) { *pos = MT_N; return 0; }
     for (int i = gg; i < MT_N; i++) {   // finish the in-place twist of the current block
         const int i1 = (i + 1 == MT_N) ? 0 : i + 1;
@@ -3256,11 +3245,11 @@ int fjsp_mt_set(fjsp_handle* h, int32_t env, const uint32_t* key, int32_t pos) {
     if (pos < 0 || pos > MT_N) return fail("pos must be in 0..624");
     DeviceGuard g(h->device);
     HIPCHK(hipStreamSynchronize(h->stream));
-    const uint32_t st = pos >= MT_N ? 0u : ((uint32_t)pos | ((uint32_t)MT_N << 16));
+    const uint32_t st = pos >= MT_N ? mtcur_make(0u, 0u, 0u) : mtcur_make((uint32_t)pos, (uint32_t)MT_N, 0u);   // into row 0
     HIPCHK(hipMemcpy(h->S.mt + (size_t)env * MT_N, key, 4 * MT_N, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->S.words + (size_t)3 * h->n + env, &st, 4, hipMemcpyHostToDevice));
-    const uint32_t zero = 0;   // a pre-drawn table belongs to the replaced stream
-    HIPCHK(hipMemcpy(h->S.words + (size_t)PGW * h->n + env, &zero, 4, hipMemcpyHostToDevice));
+    const uint32_t none = PDREC_NONE;   // a pre-drawn table belongs to the replaced stream
+    HIPCHK(hipMemcpy(h->S.words + (size_t)PGW * h->n + env, &none, 4, hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -3276,11 +3265,11 @@ int fjsp_read_env(fjsp_handle* h, int32_t env, fjsp_env_view* v) {
     HIPCHK(hipMemcpy2D(w, 4, h->S.words + env, (size_t)h->n * 4, 4, NWORDS, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy2D(orders, 4, h->S.orders + env, (size_t)h->n * 4, 4, MAX_ORDERS, hipMemcpyDeviceToHost));
     memset(v, 0, sizeof(*v));
-    v->current_step = (int32_t)(w[0] & 0xFFFF);
-    v->num_orders = (int32_t)((w[0] >> 16) & 0xFF);
-    v->next_order = (int32_t)(w[0] >> 24);
-    v->orders_completed = (int32_t)(w[1] & 0xFF);
-    v->total_packaged = (int32_t)(w[1] >> 8);
+    v->current_step = w0_step(w[0]);
+    v->num_orders = w0_norders(w[0]);
+    v->next_order = w0_next_order(w[0]);
+    v->orders_completed = w1_ncompleted(w[1]);
+    v->total_packaged = w1_total_packaged(w[1]);
     v->status = w[2];
     const int loc = (int)(w[6] & 7), carry = (int)((w[6] >> 3) & 0xFF), code = (int)((w[6] >> 11) & 0x1FFF);
     v->agv_row = loc_row(loc);

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "fjsp_env.h"
+#include "fjsp_predraw.h"
 
 namespace fjsp {
 
@@ -41,7 +42,7 @@ FJSP_HD bool put_orders_env(Env& E, const Tables& T, const Cfg& C, const uint32_
         T.orders[(base + k) * T.stride] = ow_make((int)(w & 15u), (int)((w >> 4) & 3u), (int)((w >> 6) & 3u));
     }
     E.set_norders(base + rows);
-    *pgw = 0u;
+    *pgw = PDREC_NONE;
     return true;
 }
 

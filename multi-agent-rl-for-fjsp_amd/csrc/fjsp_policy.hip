@@ -944,8 +944,7 @@ __device__ __forceinline__ void tile_step(const PolicyArgs& A, const StepArgs& S
         else if (St.rewards) fjsp::st32(St.rewards, (uint32_t)a * n + ue, r);
     }
     const int nord = E.norders();
-    const int all_done = E.ncompleted() == nord && nord > 0 && E.next_order() == nord;
-    const int truncated = E.step() >= C.max_steps;
+    const auto [all_done, truncated] = fjsp::episode_end(E, C);
     if (STAGED) {
         rb[fjsp::NMASK * 64 + lane] = (uint8_t)all_done;
         rb[(fjsp::NMASK + 1) * 64 + lane] = (uint8_t)truncated;

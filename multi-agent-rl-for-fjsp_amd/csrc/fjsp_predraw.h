@@ -18,6 +18,102 @@ inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return
 
 constexpr int MT_N = 624;
 
+// ---------------------------------------------------------------- packed words of the stream
+// Each layout is stated here once; kernels and host code go through these functions, or, where a
+// call would move a kernel's instructions, spell the same expression from the named constants.
+//
+// MT cursor word W3: pos (mti, the next word to consume) [0,10) | g (words [0, g) of the row are
+// current) [16,26) | live row of the env's two MT rows, bit 31.
+constexpr int MTCUR_G_SH = 16, MTCUR_ROW_SH = 31;
+constexpr uint32_t MTCUR_IDX_MASK = 0x3FFu, MTCUR_ROW_BIT = 0x80000000u;
+FJSP_HD constexpr int mtcur_pos(uint32_t w3) { return (int)(w3 & MTCUR_IDX_MASK); }
+FJSP_HD constexpr int mtcur_g(uint32_t w3) { return (int)((w3 >> MTCUR_G_SH) & MTCUR_IDX_MASK); }
+FJSP_HD constexpr uint32_t mtcur_row(uint32_t w3) { return w3 >> MTCUR_ROW_SH; }
+FJSP_HD constexpr uint32_t mtcur_make(uint32_t pos, uint32_t g, uint32_t row) { return pos | (g << MTCUR_G_SH) | (row << MTCUR_ROW_SH); }
+// the cursor moved, the live row kept
+FJSP_HD constexpr uint32_t mtcur_moved(uint32_t w3, int pos, int g) {
+    return (uint32_t)pos | ((uint32_t)g << MTCUR_G_SH) | (w3 & MTCUR_ROW_BIT);
+}
+static_assert(MT_N <= (int)MTCUR_IDX_MASK && MTCUR_ROW_BIT == 1u << MTCUR_ROW_SH && (MTCUR_IDX_MASK << MTCUR_G_SH) < MTCUR_ROW_BIT &&
+                  MTCUR_IDX_MASK < (1u << MTCUR_G_SH),
+              "MT_N fits the cursor's 10-bit fields, which do not overlap");
+static_assert(mtcur_pos(mtcur_make(MT_N, 0, 0)) == MT_N && mtcur_g(mtcur_make(MT_N, 0, 0)) == 0 && mtcur_g(mtcur_make(0, MT_N, 1)) == MT_N &&
+                  mtcur_pos(mtcur_make(0, MT_N, 1)) == 0 && mtcur_row(mtcur_make(0, 0, 1)) == 1u && mtcur_row(mtcur_make(MT_N, MT_N, 0)) == 0u &&
+                  mtcur_moved(mtcur_make(1, 2, 1), 3, 4) == mtcur_make(3, 4, 1),
+              "cursor word: decode(encode) at the fields' extremes");
+static_assert(mtcur_pos(0x826F0123u) == (int)(0x826F0123u & 0x3FF) && mtcur_g(0x826F0123u) == (int)((0x826F0123u >> 16) & 0x3FF) &&
+                  mtcur_row(0x826F0123u) == 0x826F0123u >> 31 &&
+                  mtcur_moved(0x826F0123u, 5, 9) == ((uint32_t)5 | ((uint32_t)9 << 16) | (0x826F0123u & 0x80000000u)),
+              "the cursor codec equals the hand-spelled expressions it replaces");
+
+// Pre-draw record W[PGW] (fjsp_stepdev.h): 0 = no table, or ready, bit 0 | the cursor after the
+// pre-drawn orders: pos [1,11), g [11,21), row bit 21 | num_orders [24,31), the orders in S.nxt.
+constexpr int PDREC_POS_SH = 1, PDREC_G_SH = 11, PDREC_ROW_SH = 21, PDREC_NORD_SH = 24;
+constexpr uint32_t PDREC_NONE = 0u, PDREC_READY = 1u, PDREC_NORD_MASK = 0x7Fu;
+FJSP_HD constexpr bool pdrec_ready(uint32_t pg) { return (pg & PDREC_READY) != 0u; }
+FJSP_HD constexpr int pdrec_nord(uint32_t pg) { return (int)((pg >> PDREC_NORD_SH) & PDREC_NORD_MASK); }
+FJSP_HD constexpr int pdrec_pos(uint32_t pg) { return (int)((pg >> PDREC_POS_SH) & MTCUR_IDX_MASK); }
+FJSP_HD constexpr int pdrec_g(uint32_t pg) { return (int)((pg >> PDREC_G_SH) & MTCUR_IDX_MASK); }
+FJSP_HD constexpr uint32_t pdrec_row(uint32_t pg) { return (pg >> PDREC_ROW_SH) & 1u; }
+FJSP_HD constexpr uint32_t pdrec_make(int pos, int g, uint32_t row, int nord) {
+    return PDREC_READY | ((uint32_t)pos << PDREC_POS_SH) | ((uint32_t)g << PDREC_G_SH) | (row << PDREC_ROW_SH) |
+           ((uint32_t)nord << PDREC_NORD_SH);
+}
+// the record's cursor as a cursor word (W3 after a reset from the table)
+FJSP_HD constexpr uint32_t pdrec_cursor(uint32_t pg) {
+    return ((pg >> PDREC_POS_SH) & MTCUR_IDX_MASK) | (((pg >> PDREC_G_SH) & MTCUR_IDX_MASK) << MTCUR_G_SH) |
+           (((pg >> PDREC_ROW_SH) & 1u) << MTCUR_ROW_SH);
+}
+static_assert(MAX_ORDERS <= (int)PDREC_NORD_MASK && PDREC_NORD_SH + 7 <= 32 && (MTCUR_IDX_MASK << PDREC_POS_SH) < (1u << PDREC_G_SH) &&
+                  (MTCUR_IDX_MASK << PDREC_G_SH) < (1u << PDREC_ROW_SH) && PDREC_ROW_SH < PDREC_NORD_SH && PDREC_POS_SH > 0,
+              "MAX_ORDERS fits the record's 7-bit field; the record's fields do not overlap");
+static_assert(pdrec_ready(pdrec_make(0, 0, 0, 0)) && !pdrec_ready(0u) && pdrec_pos(pdrec_make(MT_N, 0, 0, 0)) == MT_N &&
+                  pdrec_g(pdrec_make(MT_N, 0, 0, 0)) == 0 && pdrec_g(pdrec_make(0, MT_N, 0, 0)) == MT_N &&
+                  pdrec_row(pdrec_make(0, MT_N, 0, 0)) == 0u && pdrec_row(pdrec_make(0, 0, 1, 0)) == 1u &&
+                  pdrec_nord(pdrec_make(0, 0, 1, 0)) == 0 && pdrec_nord(pdrec_make(0, 0, 0, MAX_ORDERS)) == MAX_ORDERS &&
+                  pdrec_nord(pdrec_make(MT_N, MT_N, 1, 0x7F)) == 0x7F && pdrec_cursor(pdrec_make(7, MT_N, 1, 30)) == mtcur_make(7, MT_N, 1),
+              "pre-draw record: decode(encode) at the fields' extremes");
+static_assert(pdrec_make(0x155, 0x26F, 1u, 0x2A) == (1u | ((uint32_t)0x155 << 1) | ((uint32_t)0x26F << 11) | (1u << 21) | ((uint32_t)0x2A << 24)) &&
+                  pdrec_cursor(0x2A3377ABu) == (((0x2A3377ABu >> 1) & 0x3FFu) | (((0x2A3377ABu >> 11) & 0x3FFu) << 16) | (((0x2A3377ABu >> 21) & 1u) << 31)),
+              "the record codec equals the hand-spelled expressions it replaces");
+
+// The per-lane mailboxes between the sim side and the pre-draw wave (predraw_wave, s_mb[0..3]).
+//   sim side, word 0: episode counter of the launch (mod 256) [0,8) | num_orders [8,15);
+//             word 1: the env's cursor word W3.
+//   pre-draw side, word 2: table ready, bit 0 | the episode it is for [1,9) | its num_orders [9,16);
+//             word 3: the cursor word after the table (mtcur_make).
+constexpr int SIMMB_NORD_SH = 8, PDMB_EPI_SH = 1, PDMB_NORD_SH = 9;
+constexpr uint32_t MB_EPI_MASK = 0xFFu, MB_NORD_MASK = 0x7Fu, PDMB_READY = 1u;
+constexpr uint32_t MB_EPI_NONE = MB_EPI_MASK + 1u;   // matches no episode counter
+FJSP_HD constexpr int mb_next_epi(int epi) { return (epi + 1) & (int)MB_EPI_MASK; }
+FJSP_HD constexpr uint32_t simmb_make(uint32_t epi, uint32_t nord) { return epi | (nord << SIMMB_NORD_SH); }
+FJSP_HD constexpr uint32_t simmb_epi(uint32_t si) { return si & MB_EPI_MASK; }
+FJSP_HD constexpr int simmb_nord(uint32_t si) { return (int)((si >> SIMMB_NORD_SH) & MB_NORD_MASK); }
+FJSP_HD constexpr uint32_t pdmb_make(bool ready, uint32_t epi, uint32_t nord) {
+    return (ready ? PDMB_READY : 0u) | (epi << PDMB_EPI_SH) | (nord << PDMB_NORD_SH);
+}
+FJSP_HD constexpr bool pdmb_ready(uint32_t pr) { return (pr & PDMB_READY) != 0u; }
+FJSP_HD constexpr uint32_t pdmb_epi(uint32_t pr) { return (pr >> PDMB_EPI_SH) & MB_EPI_MASK; }
+FJSP_HD constexpr int pdmb_nord(uint32_t pr) { return (int)((pr >> PDMB_NORD_SH) & MB_NORD_MASK); }
+// the table is ready for this episode of the launch and this table size
+FJSP_HD constexpr bool pdmb_ready_for(uint32_t pr, int epi, int nord) {
+    return (pr & PDMB_READY) && ((pr >> PDMB_EPI_SH) & MB_EPI_MASK) == (uint32_t)epi && (int)((pr >> PDMB_NORD_SH) & MB_NORD_MASK) == nord;
+}
+static_assert(MAX_ORDERS <= (int)MB_NORD_MASK && MB_EPI_MASK < (1u << SIMMB_NORD_SH) && PDMB_EPI_SH > 0 &&
+                  (MB_EPI_MASK << PDMB_EPI_SH) < (1u << PDMB_NORD_SH) && PDMB_NORD_SH + 7 <= 32,
+              "MAX_ORDERS fits the mailboxes' 7-bit fields; the mailbox fields do not overlap");
+static_assert(simmb_epi(simmb_make(0xFF, 0)) == 0xFFu && simmb_nord(simmb_make(0xFF, 0)) == 0 && simmb_epi(simmb_make(0, 0x7F)) == 0u &&
+                  simmb_nord(simmb_make(0, 0x7F)) == 0x7F && pdmb_ready(pdmb_make(true, 0, 0)) && !pdmb_ready(pdmb_make(false, 0xFF, 0x7F)) &&
+                  pdmb_epi(pdmb_make(false, 0xFF, 0)) == 0xFFu && pdmb_nord(pdmb_make(true, 0xFF, 0)) == 0 &&
+                  pdmb_nord(pdmb_make(false, 0, 0x7F)) == 0x7F && pdmb_epi(pdmb_make(true, 0, 0x7F)) == 0u &&
+                  pdmb_ready_for(pdmb_make(true, 0xFF, MAX_ORDERS), 0xFF, MAX_ORDERS) && !pdmb_ready_for(pdmb_make(false, 3, 30), 3, 30) &&
+                  !pdmb_ready_for(pdmb_make(true, 3, 30), 4, 30) && !pdmb_ready_for(pdmb_make(true, 3, 30), 3, 31),
+              "mailbox words: decode(encode) at the fields' extremes, and the match");
+static_assert(simmb_make(0xA5, 0x2A) == ((uint32_t)0xA5 | ((uint32_t)0x2A << 8)) &&
+                  pdmb_make(true, 0xA5, 0x2A) == (1u | (0xA5u << 1) | ((uint32_t)0x2A << 9)) &&
+                  pdmb_ready_for(0x55ABu, 0xD5, 0x2A) == ((0x55ABu & 1u) && ((0x55ABu >> 1) & 0xFFu) == (uint32_t)0xD5 && (int)((0x55ABu >> 9) & 0x7Fu) == 0x2A),
+              "the mailbox codec equals the hand-spelled expressions it replaces");
+
 // Batched reader of the lazily twisted stream for resets.  A refill of B words starts at the
 // 16-byte aligned word pa = pos & ~3 and loads the words it needs as two runs of B/4 + 1 uint4
 // (words [pa, pa+B+4) and [pa+396, pa+B+400), wrapped into the row; 624 is a multiple of 4

@@ -89,9 +89,7 @@ FJSP_DEV LaneEnd search_lane(Env& E, const Tables& T, const Cfg& C, int K, int e
         uint32_t res[NA];
         (void)env_advance<true>(E, T, C, act, nullptr, res);
         flag_obs_overflow(E);
-        const int nord = E.norders();
-        const bool all_done = E.ncompleted() == nord && nord > 0 && E.next_order() == nord;
-        const bool truncated = E.step() >= C.max_steps;
+        const auto [all_done, truncated] = episode_end(E, C);
         r.orders_completed = E.ncompleted();
         r.packaged = E.total_packaged();
         r.sim_time = (double)(E.step() + 1) * (double)C.step_size;

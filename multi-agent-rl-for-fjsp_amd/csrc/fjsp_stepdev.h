@@ -56,7 +56,7 @@ static_assert(NWORDS >= NSTATE, "state buffer rows");
 // Per-env state: 624 words, env-major (row e = mt + e * 624, 16-byte aligned), so the words a
 // lane streams through are contiguous for that lane (lanes of a wave sit at different stream
 // positions: a word-major layout would make every load touch 64 rows).
-// Cursor word W3: mti (bits 0..9) | g (bits 16..25).  Words [0, g) of the row already hold the
+// Cursor word W3 (mtcur_*, fjsp_predraw.h): mti | g.  Words [0, g) of the row already hold the
 // current block, [g, 624) still the previous one; mti <= g is the next word to consume.
 // Word i of a new block is generated on demand with the same in-place recurrence as numpy's
 // sequential twist (mt[i+1] is still old, mt[i+397 mod 624] is new iff i >= 227), so the k-th
@@ -81,14 +81,14 @@ __device__ inline void mt_seed(uint32_t* __restrict__ mt, int e, uint32_t seed) 
 // draw_orders) and the pre-draw lane's slices are in fjsp_predraw.h, which also compiles for the
 // host.
 
-// MT rows: two per env ([2][N][624]); bit 31 of the cursor word W3 selects the live one (the
-// other is the pre-draw wave's working copy, see k_step_pipe).  W[PGW] = the pre-draw record:
-// 0, or ready (bit 0) | cursor after the pre-drawn orders (mti bits 1..10, g bits 11..20) |
-// row (bit 21) | num_orders (bits 24..30), with the orders in S.nxt.
+// MT rows: two per env ([2][N][624]); the row bit of the cursor word W3 selects the live one (the
+// other is the pre-draw wave's working copy, see k_step_pipe).  W[PGW] = the pre-draw record
+// (pdrec_*, fjsp_predraw.h): 0, or the cursor after the pre-drawn orders, its row and num_orders,
+// with the orders in S.nxt.
 constexpr int PGW = NSTATE;
 static_assert(NWORDS > PGW, "state buffer rows");
 __device__ __forceinline__ uint32_t* mt_row(const DevState& S, uint32_t w3, int e) {
-    return S.mt + ((size_t)(w3 >> 31) * S.n + e) * MT_N;
+    return S.mt + ((size_t)mtcur_row(w3) * S.n + e) * MT_N;
 }
 
 // FJSPSimulation.reset body after the optional reseed (FJSPSimulation.py:301-320): clear the
@@ -100,7 +100,7 @@ __device__ __forceinline__ void env_reset(Env& E, const Tables& T, const Cfg& C,
     E.set_norders(num_orders);
     const uint32_t w3 = (uint32_t)E.mti();
     uint32_t* roww = mt_row(S, w3, e);
-    int pos = (int)(w3 & 0x3FF), g = (int)((w3 >> 16) & 0x3FF);
+    int pos = mtcur_pos(w3), g = mtcur_g(w3);
     OrderDraw d{0, 0, 0, 0, 0u};
     while (d.o < num_orders) {
         uint32_t v[MTB];
@@ -109,8 +109,8 @@ __device__ __forceinline__ void env_reset(Env& E, const Tables& T, const Cfg& C,
         pos += draw_orders<MTB>(v, pos - pa, cnt, num_orders, d, T.orders, T.stride);
         if (pos == MT_N) { pos = 0; g = 0; }
     }
-    E.set_mti((int)((uint32_t)pos | ((uint32_t)g << 16) | (w3 & 0x80000000u)));
-    if (clear_pg) S.words[(size_t)PGW * S.n + e] = 0u;
+    E.set_mti((int)mtcur_moved(w3, pos, g));
+    if (clear_pg) S.words[(size_t)PGW * S.n + e] = PDREC_NONE;
 }
 
 // reset(seed=None) from a pre-drawn table (lane's slots nxt[o * BLOCK]): the same state as
@@ -141,6 +141,16 @@ __device__ __forceinline__ Tables tables_of(const DevState& S, int e) {
     T.snext = S.snext + e;
     T.scstep = S.scstep + e;
     T.stride = S.n;
+    return T;
+}
+// a lane's tables in a kernel's LDS staging arrays (element i of the lane at base[i * BLOCK + lane])
+__device__ __forceinline__ Tables lds_tables(uint32_t* orders, uint16_t* scode, uint8_t* snext, uint16_t* scstep, int lane) {
+    Tables T;
+    T.orders = orders + lane;
+    T.scode = scode + lane;
+    T.snext = snext + lane;
+    T.scstep = scstep + lane;
+    T.stride = BLOCK;
     return T;
 }
 
@@ -207,8 +217,7 @@ __device__ __forceinline__ void step_and_emit(Env& E, const Tables& T, const Cfg
     observe(E, C, sink);
     FJSP_STAMP(E, 4);
     const int nord = E.norders();
-    const int all_done = E.ncompleted() == nord && nord > 0 && E.next_order() == nord;
-    const int truncated = E.step() >= C.max_steps;
+    const auto [all_done, truncated] = episode_end(E, C);
     if (out.term) st32(out.term, t * n + ue, (uint8_t)all_done);
     if (out.trunc) st32(out.trunc, t * n + ue, (uint8_t)truncated);
     if (FULL && out.orders_completed) st32(out.orders_completed, t * n + ue, E.ncompleted());

@@ -45,7 +45,7 @@ KOut k_step_ref(World& W, const Cfg& C, uint32_t a1, uint32_t pend, Events& ev) 
         if (completed && by >= 2) ev.order_by_two++;
     }
     if (pend) {
-        const int st = pkg_station(E, C, (int)((pend >> 22) & 3u));
+        const int st = pkg_station(E, C, pend_color(pend));
         if (st < 0) ev.drop_lost++;
         else ev.drop_to[st]++;
         agv_pack_drop(E, T, C, pend);
@@ -193,7 +193,7 @@ void sweep_g(int64_t* out, Mismatch& bad, Events& ev) {
             Tables T = W.tabs();
             const int tcode = tc_make(8, 0, 3);
             const int slot = slot_new(W.E, T, tcode);
-            pend = 1u | ((uint32_t)slot << 1) | ((uint32_t)tcode << 9) | ((uint32_t)color << 22);
+            pend = pend_make(slot, tcode, color);
         }
         out[0]++;
         bad.check(both<G>(W, C, a1, pend, ev), "G %d stations %d actions %d colour %d: the lane groups differ from the sequence",
